@@ -271,6 +271,8 @@ class DropIn:
         self.rasts = [dgr.GaussianRasterizer(raster_settings=rs) for rs in settings_list]
         self.P = params["means3D"].shape[0]
         self.i = 0
+        self.keep_outputs = False          # --dump-outputs: hold the last step's forward outputs in self.last
+        self.last = None
         self.reset_stats()
 
     def reset_stats(self):
@@ -289,6 +291,8 @@ class DropIn:
         self.L_sum += color.grad_fn.num_rendered
         self.n += 1
         self.radii[j] = radii
+        if self.keep_outputs:
+            self.last = dict(color=color, invdepth=invd, radii=radii, means2D=screenspace_points)
         if self.do_depth:
             torch.autograd.backward([color, invd], [self.gc, self.gd])   # loss.backward() with dL/dcolor, dL/dinvdepth given
         else:
@@ -303,6 +307,36 @@ class DropIn:
     def mean_V(self):
         vs = [int((r > 0).sum().item()) for r in self.radii.values()]
         return sum(vs) / max(len(vs), 1)
+
+
+DUMP_BYTES = 64_000_000   # --dump-outputs writes at most this much in all, .npy headers included
+DUMP_ROWS = 1 << 15        # per-Gaussian arrays: this many rows, a fixed seeded sample
+
+
+def dump_outputs(out_dir, images, rows):
+    """Writes one step's outputs to out_dir/<name>.npy in float32.  ``rows`` (name -> tensor with one row per Gaussian)
+    are reduced to the same fixed seeded sample of DUMP_ROWS rows; ``images`` (name -> (C, H, W) tensor, one H x W for
+    all) are written whole, or as the same fixed seeded sample of pixels, (C, n), if whole they would not fit into
+    DUMP_BYTES next to the rows.  The samples depend only on P, H and W: two runs with the same arguments compare
+    array for array."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    P = next(iter(rows.values())).shape[0]
+    ri = np.sort(np.random.default_rng(0).choice(P, size=min(P, DUMP_ROWS), replace=False))
+    out = {}
+    for name, t in rows.items():
+        out[name] = t.detach()[torch.from_numpy(ri).to(t.device)].float().cpu().numpy()
+    left = DUMP_BYTES - sum(a.nbytes for a in out.values()) - 256 * (len(rows) + len(images))
+    H, W = next(iter(images.values())).shape[1:]
+    channels = sum(t.shape[0] for t in images.values())
+    pi = None
+    if channels * H * W * 4 > left:
+        pi = np.sort(np.random.default_rng(1).choice(H * W, size=left // (4 * channels), replace=False))
+    for name, t in images.items():
+        a = t.detach().float().cpu().numpy()
+        out[name] = a if pi is None else a.reshape(a.shape[0], H * W)[:, pi]
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def _settings(dgr, cam, dev, sh_degree=3, **over):
@@ -869,7 +903,13 @@ def main():
                          "~15 s); the committed summary of the same build is used instead.  Implied by --no-extras")
     ap.add_argument("--cpu-baseline-only", type=int, default=0, metavar="L",
                     help="internal: time the CPU oracle for a frame with L tile instances, print JSON, exit")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step of the reported schedule returned to its "
+                         "caller (image, inverse depth, radii, the means2D and parameter gradients) to DIR/<name>.npy in "
+                         "float32, rank 0 only; per-Gaussian arrays as a fixed seeded sample of rows, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.cpu_baseline_only:
         from hgs import synth
@@ -992,6 +1032,8 @@ def main():
                                           colors_precomp=rgbs[j].requires_grad_(True), opacities=params["opacities"],
                                           scales=params["scales"], rotations=params["rotations"])
                 info["L"], info["radii"] = color.grad_fn.num_rendered, radii
+                if args.dump_outputs:
+                    state["last"] = dict(color=color, invdepth=invd, radii=radii)
                 torch.autograd.backward([color, invd], [gc, gd])        # every gradient lands in a buffer
             # N > 1: the (opacity, scale, rotation) slice of the bucket is final once the last view's per-Gaussian backward
             # has run -- it goes on the wire (ordered after that backward) while the batched SH backward still runs
@@ -1006,6 +1048,8 @@ def main():
                                           opacities=params["opacities"], scales=params["scales"],
                                           rotations=params["rotations"])
                 info["L"], info["radii"] = color.grad_fn.num_rendered, radii
+                if args.dump_outputs:
+                    state["last"] = dict(color=color, invdepth=invd, radii=radii)
                 torch.autograd.backward([color, invd], [gc, gd])
             early = None
             if rc.defer_sh_backward:
@@ -1035,7 +1079,7 @@ def main():
                     work.wait()
         return _OnStream()
 
-    def measure(step, steps, warmup, dominant_timing, reset=None):
+    def measure(step, steps, warmup, dominant_timing, reset=None, after_timed=None):
         for _ in range(warmup):
             step()
         barrier()
@@ -1057,6 +1101,8 @@ def main():
         elapsed = time.perf_counter() - t0
         info["host_ms_per_step"] = host / steps * 1e3       # time spent INSIDE step(): Python, ctypes, launches, host waits
         measure.last_host_ms = info["host_ms_per_step"]
+        if after_timed is not None:
+            after_timed()                # sees the last timed step's results, before the stage-timing steps below
         stages = {}
         if dominant_timing:
             _lib.timing_enable(False)
@@ -1080,14 +1126,31 @@ def main():
     # chip that sat idle while the scene was generated on the host is still ramping its clocks then; the primary
     # measurement itself stays "W untimed steps, then exactly K timed steps"
     order = ([] if args.no_secondary else [s_ for s_ in ("dropin", "batched") if s_ != primary]) + [primary]
+
+    def dump_dropin():
+        last = dropin.last
+        dump_outputs(args.dump_outputs, dict(color=last["color"], invdepth=last["invdepth"]),
+                     dict(radii=last["radii"], means2D_grad=last["means2D"].grad,
+                          **{kk + "_grad": v.grad for kk, v in params.items()}))
+        dropin.keep_outputs, dropin.last = False, None
+
+    def dump_batched():
+        last = state["last"]
+        dump_outputs(args.dump_outputs, dict(color=last["color"], invdepth=last["invdepth"]),
+                     dict(radii=last["radii"], means2D_grad=state["rc"].grad_buffers["means2D"],
+                          **{kk + "_grad": v for kk, v in state["bucket"].views.items()}))
+
+    dumping = bool(args.dump_outputs) and rank == 0
     for sched in order:
         is_primary = sched == primary
         if sched == "dropin":
             steps = args.steps if is_primary else max(20, min(args.steps, 40))
             from diff_gaussian_rasterization import _C as dgrC
             miss0 = dgrC.stats["capacity_misses"]
+            dropin.keep_outputs = dumping and is_primary
             elapsed, stages = measure(step_dropin, steps, args.warmup if is_primary else 20, timing and is_primary,
-                                      reset=dropin.reset_stats)
+                                      reset=dropin.reset_stats,
+                                      after_timed=dump_dropin if dumping and is_primary else None)
             info["dropin_L"], info["dropin_V"] = dropin.mean_L(), dropin.mean_V()
             info["dropin_misses"] = dgrC.stats["capacity_misses"] - miss0      # warm-up + timed + stage-timing steps
             views = 1
@@ -1096,7 +1159,8 @@ def main():
         else:
             setup_batched()
             steps = args.steps if is_primary else max(6, min(args.steps, (args.steps * 2 + k - 1) // k))
-            elapsed, stages = measure(step_batched, steps, args.warmup if is_primary else 6, timing and is_primary)
+            elapsed, stages = measure(step_batched, steps, args.warmup if is_primary else 6, timing and is_primary,
+                                      after_timed=dump_batched if dumping and is_primary else None)
             views = k
             state.clear()
         res[sched] = dict(value=world * views * steps / elapsed, ms_per_step=elapsed / steps * 1e3, steps=steps,

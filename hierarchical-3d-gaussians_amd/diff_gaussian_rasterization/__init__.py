@@ -1,7 +1,7 @@
 """Drop-in ``diff_gaussian_rasterization`` for AMD MI355X (gfx950).
 
 Same import names and call surface as the reference's hierarchy-rasterizer submodule
-(/root/reference/.gitmodules:4-6), as used by gaussian_renderer/__init__.py:14,17,44-64,
+(.gitmodules:4-6), as used by gaussian_renderer/__init__.py:14,17,44-64,
 105-113,247-277,319-389:
 
     GaussianRasterizationSettings(image_height=..., ..., num_node_kids=...)   # 17 keyword fields

@@ -3,7 +3,7 @@
 TEST INFRASTRUCTURE ONLY (see oracle/raster_oracle.py header).
 
 PARITY UNPINNED: the reference implementation lives in the un-vendored
-submodule ``graphdeco-inria/gaussian-hierarchy`` (/root/reference/.gitmodules:10-12,
+submodule ``graphdeco-inria/gaussian-hierarchy`` (.gitmodules:10-12,
 empty directory, SHA unknown); the reference has no tests for it.  What is
 restated here is fixed by the call sites and by the consumer's semantics:
 

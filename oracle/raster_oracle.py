@@ -6,7 +6,7 @@ TEST INFRASTRUCTURE ONLY.  Nothing under ``oracle/`` is product code: only
 
 PARITY UNPINNED: the reference's implementation of this path lives in the
 un-vendored submodule ``graphdeco-inria/hierarchy-rasterizer`` (declared at
-/root/reference/.gitmodules:4-6, directory empty, pinned SHA unknown) and the
+.gitmodules:4-6, directory empty, pinned SHA unknown) and the
 reference ships no tests or golden vectors for it.  This file restates the
 public tile-based 3D-Gaussian-splatting rasterization algorithm that the
 submodule's Python call sites imply, and is pinned only by
@@ -289,7 +289,7 @@ def lod_opacity(opacity, interp_w, kids):
     quantity is alpha = o*G, and off-centre ``1-(1-o'G)^k != o*G`` (o = 0.9, k = 2, G = 0.5: 0.567 against 0.45) --
     the k children are MORE opaque than their parent there.  The exact invariant belongs to a per-PIXEL remap of
     alpha (``lod_alpha`` below, ``rasterize(..., lod_mode="alpha")``, oracle only).  Which of the two the upstream
-    kernel applies cannot be seen from /root/reference (gaussian_renderer/__init__.py:258-265 only passes the two
+    kernel applies cannot be seen from the reference (gaussian_renderer/__init__.py:258-265 only passes the two
     tensors on); tests/test_oracle_kat.py::test_lod_remap_parent_vs_children measures both against the rationale, and
     the pin kit's ``upstream_raster_post.npz`` discriminates between them on arrival.
     """

@@ -1,5 +1,5 @@
 """Generates tests/golden/ref_adam_golden.npz by running the REFERENCE optimiser itself: scene/OurAdam.py is pure
-Python, so its Adam class is loaded from /root/reference (read-only; by file path, to skip scene/__init__.py's
+Python, so its Adam class is loaded from the reference checkout HGS_REFERENCE names (by file path, to skip scene/__init__.py's
 unrelated imports) and stepped on CPU with seeded float32 inputs.  Run in the build container:
 
     python tests/golden/make_adam_golden.py
@@ -14,7 +14,7 @@ import os
 import numpy as np
 import torch
 
-REF_FILE = "/root/reference/scene/OurAdam.py"
+REF_FILE = os.path.join(os.environ["HGS_REFERENCE"], "scene", "OurAdam.py")
 SHAPES = dict(xyz=(3,), f_dc=(1, 3), f_rest=(15, 3), opacity=(1,), scaling=(3,), rotation=(4,))
 LRS = dict(xyz=1.6e-4, f_dc=2.5e-3, f_rest=1.25e-4, opacity=5e-2, scaling=5e-3, rotation=1e-3)
 

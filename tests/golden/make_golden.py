@@ -1,6 +1,6 @@
 """Generates tests/golden/ref_utils_golden.npz by IMPORTING the reference's own Python utilities
-from /root/reference (read-only) -- the only in-tree numerical pins of the rasterizer's conventions
-(SURVEY.md §8(c)).  Run in the build container (the GPU box has no /root/reference):
+from the reference checkout HGS_REFERENCE names -- the only in-tree numerical pins of the rasterizer's conventions
+(SURVEY.md §8(c)).  Run wherever such a checkout exists:
 
     python tests/golden/make_golden.py
 
@@ -17,7 +17,7 @@ import sys
 import numpy as np
 import torch
 
-REF = "/root/reference"
+REF = os.environ["HGS_REFERENCE"]
 sys.path.insert(0, REF)
 from utils import sh_utils, graphics_utils  # noqa: E402
 import utils.general_utils as gu  # noqa: E402

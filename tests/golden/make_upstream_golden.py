@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """PIN KIT -- run this where the UPSTREAM extensions are installed (an NVIDIA machine with the reference's
-``pip install submodules/hierarchy-rasterizer submodules/gaussianhierarchy``, /root/reference/requirements.txt:10-12):
+``pip install submodules/hierarchy-rasterizer submodules/gaussianhierarchy``, requirements.txt:10-12):
 
     python tests/golden/make_upstream_golden.py            # writes tests/golden/upstream_*.npz
     git add tests/golden/upstream_*.npz                    # tests/test_upstream_pins.py then consumes them

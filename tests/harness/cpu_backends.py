@@ -1,9 +1,8 @@
 """Oracle-backed stand-ins for the three native extension layers, for running the REFERENCE'S OWN Python (render glue
-and the three entry scripts, unmodified, from /root/reference) on a machine without a GPU.
+and the three entry scripts, unmodified, from a reference checkout) on a machine without a GPU.
 
-TEST INFRASTRUCTURE ONLY.  The product packages have no CPU path; these classes exist because the build container has
-no GPU and /root/reference does not exist on the GPU box, so the container is the only place where the reference's
-callers can meet this repository's call signatures.  What they prove is the SURFACE: argument order, which tensors are
+TEST INFRASTRUCTURE ONLY.  The product packages have no CPU path; these classes exist so that the reference's callers can
+meet this repository's call signatures.  What they prove is the SURFACE: argument order, which tensors are
 filled, return shapes / dtypes, autograd contract, files written -- the arithmetic behind them is the CPU oracle, not
 the HIP kernels (those are checked against the same oracle by the ``-m gpu`` tests)."""
 import types

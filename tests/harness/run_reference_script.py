@@ -14,7 +14,7 @@ What this launcher adds around the script, and nothing else:
   * the oracle-backed extension layers of tests/harness/cpu_backends.py (TEST ONLY: no GPU here);
   * a torch-function mode that maps ``device="cuda"`` / ``.cuda()`` / ``.to("cuda")`` to the CPU, and no-op stand-ins for
     the handful of ``torch.cuda.*`` calls the scripts make (Event, max_memory_allocated, empty_cache, set_device).
-The reference's files are executed from /root/reference as they are."""
+The reference's files are executed as they are from the checkout HGS_REFERENCE names."""
 import os
 import runpy
 import sys

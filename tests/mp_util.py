@@ -3,8 +3,12 @@
 `run_world` starts `world` processes running ``worker(rank, world, port, queue, *extra)`` and returns the `world` items the
 workers put on the queue.  The port is probed (bind to 0, close) and can be taken by somebody else before rank 0 binds
 it, and a worker that dies during initialisation leaves its peers waiting in the rendezvous: both show as a worker exiting
-non-zero, and the attempt is repeated with a fresh port (the survivors are terminated by their own process handles).  A
-genuine failure inside a worker fails every attempt and then the test."""
+non-zero, and the attempt is repeated with a fresh port (the survivors are terminated by their own process handles, and
+killed if they do not stop, before the next attempt starts).  A genuine failure inside a worker fails every attempt and
+then the test.
+
+At most MAX_WORLD workers: with the GPU tests' own process, which holds the device too, no more than 6 processes may
+have the GPU open at once on the shared test machines."""
 import queue as _queue
 import socket
 import time
@@ -13,11 +17,15 @@ import pytest
 import torch.multiprocessing as mp
 
 
+MAX_WORLD = 5
+
+
 def free_port():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
 
 def run_world(worker, world, extra=(), timeout=500, join_timeout=120, attempts=3):
+    assert 1 <= world <= MAX_WORLD, f"{world} workers: at most {MAX_WORLD} may run at once"
     last = ""
     for _ in range(attempts):
         ctx = mp.get_context("spawn")
@@ -52,4 +60,7 @@ def run_world(worker, world, extra=(), timeout=500, join_timeout=120, attempts=3
                 if p.is_alive():
                     p.terminate()
                     p.join(10)
+                if p.is_alive():
+                    p.kill()
+                    p.join()
     pytest.fail(f"{world}-process run failed {attempts} times: {last}")

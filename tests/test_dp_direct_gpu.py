@@ -14,7 +14,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from mp_util import run_world
+from mp_util import MAX_WORLD, run_world
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -72,10 +72,12 @@ def _worker(rank, world, port, q, extra_env=None):
 
 
 @pytest.mark.timeout(600)
-@pytest.mark.parametrize("world,env", [(2, None), (3, None), (8, {"HGS_P2P_VERIFY": "2"}), (2, {"HGS_P2P_FINEGRAINED": "1"})])
+@pytest.mark.parametrize("world,env", [(2, None), (3, None), (MAX_WORLD, {"HGS_P2P_VERIFY": "2"}),
+                                       (2, {"HGS_P2P_FINEGRAINED": "1"})])
 def test_direct_all_reduce_between_processes_sharing_the_gpu(gpu, world, env):
-    """world 8: the shard arithmetic of a full node (HGS_P2P_MAX_WORLD), with the HGS_P2P_VERIFY self-check armed for
-    the GradBucket exchanges; the last case allocates the buckets fine-grained."""
+    """world MAX_WORLD (5): the most ranks one GPU may host next to the test process, an odd count that divides neither
+    the bucket nor its float4 count, with the HGS_P2P_VERIFY self-check armed for the GradBucket exchanges; the last
+    case allocates the buckets fine-grained."""
     res = dict(run_world(_worker, world, extra=(env,), timeout=500, join_timeout=120))
     n = 1_000_003
     for epoch in range(4):

@@ -4,7 +4,7 @@ path -- tests/test_dp_step_gpu.py runs the same protocol through them); what is 
 SURVEY.md section 8(e):
   * the split SUM all-reduce of the gradient bucket,
   * the three densification reductions (MAX of |means2D.grad|, SUM of the visibility count, MAX of the radii:
-    /root/reference/scene/gaussian_model.py:687-689, train_single.py:147),
+    scene/gaussian_model.py:687-689, train_single.py:147),
   * ``relevant`` taken from the REDUCED opacity gradient (train_single.py:170-174),
   * every rank ends the step with bit-identical parameters, equal to one process stepping through all views."""
 import os

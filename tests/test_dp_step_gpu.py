@@ -14,7 +14,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from mp_util import run_world
+from mp_util import MAX_WORLD, run_world
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -113,17 +113,17 @@ def test_two_ranks_on_one_gpu_agree_and_match_one_process(gpu, route):
 
 
 @pytest.mark.timeout(900)
-def test_eight_ranks_on_one_gpu_direct_route(gpu):
-    """The shape of a full node: 8 ranks (sharing the one GPU here), one view per rank per step, gradient exchange by
-    the direct peer-pointer all-reduce.  All ranks bit-identical after 3 steps and equal to one process accumulating
-    the 8 views itself."""
-    world = 8
+def test_five_ranks_on_one_gpu_direct_route(gpu):
+    """MAX_WORLD (5) ranks, the most one GPU may host next to the test process, one view per rank per step, gradient
+    exchange by the direct peer-pointer all-reduce.  All ranks bit-identical after 3 steps and equal to one process
+    accumulating the 5 views itself."""
+    world = MAX_WORLD
     got = {}
     for r, params, accum in run_world(_worker, world, extra=("direct", 1,), timeout=800, join_timeout=120):
         got[r] = ({k: torch.from_numpy(v) for k, v in params.items()}, {k: torch.from_numpy(v) for k, v in accum.items()})
     sys.path.insert(0, HERE)
     import dp_common as dc
-    ref_params, ref_accum = _run_steps(0, 1, 3, 8)
+    ref_params, ref_accum = _run_steps(0, 1, 3, world)
     for k in dc.NAMES:
         for r in range(1, world):
             assert torch.equal(got[0][0][k], got[r][0][k]), f"{k}: rank {r} diverged"
@@ -131,7 +131,7 @@ def test_eight_ranks_on_one_gpu_direct_route(gpu):
         err = float((got[0][0][k] - ref_params[k]).abs().max())
         assert err <= 2e-6 * scale, (k, err, scale)
     for k, v in ref_accum.items():
-        assert torch.equal(got[0][1][k], got[7][1][k]) and torch.allclose(got[0][1][k], v, rtol=1e-6, atol=0), k
+        assert torch.equal(got[0][1][k], got[world - 1][1][k]) and torch.allclose(got[0][1][k], v, rtol=1e-6, atol=0), k
 
 
 @pytest.mark.timeout(900)

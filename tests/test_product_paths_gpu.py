@@ -2,7 +2,7 @@
 
   * the speculative single-call forward's CAPACITY MISS (``hgs_raster_fwd`` -> ``HGS_ERR_CAPACITY`` -> exact two-stage
     retry, diff_gaussian_rasterization/_C.py) -- plain call shape and the ``lod=`` shape key (coarse -> fine cut);
-  * ``render_coarse``'s call shape (/root/reference/gaussian_renderer/__init__.py:296-389: M = 4 coefficients,
+  * ``render_coarse``'s call shape (gaussian_renderer/__init__.py:296-389: M = 4 coefficients,
     ``debug=True`` always, ``do_depth`` False, skybox rows at the head) and the other short SH blocks, M in {1, 4, 9}
     (M = 9: the ``3M % 4 != 0`` scalar SH path of preprocess.hip);
   * 30 seeded cases of the soak tool tests/tools/fuzz_parity.py;
@@ -165,7 +165,7 @@ def test_short_sh_blocks_with_debug(gpu, deg_stored, deg_active):
 
 
 def test_render_coarse_call_shape(gpu):
-    """render_coarse (/root/reference/gaussian_renderer/__init__.py:296-407) as train_coarse.py:94 drives it:
+    """render_coarse (gaussian_renderer/__init__.py:296-407) as train_coarse.py:94 drives it:
     GaussianModel(1) -> 4 SH coefficients, sh_degree 1, debug=True unconditionally (:331), do_depth left at its
     default, random background, the skybox rows at the HEAD of the arrays (far, large, README.md:490); the third
     output is ignored (:381) and the visibility filter is the bool mask ``radii > 0`` (:393-407)."""

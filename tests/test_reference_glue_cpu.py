@@ -1,11 +1,11 @@
 """Runs the REFERENCE'S OWN render glue (gaussian_renderer/__init__.py: render, render_post,
-render_coarse -- unmodified, imported from /root/reference) on top of this repo's
+render_coarse -- unmodified, imported from the reference checkout HGS_REFERENCE names) on top of this repo's
 ``diff_gaussian_rasterization`` package, on CPU, to prove the op surface is a drop-in: keyword
 names, the 17 settings fields, empty CPU LOD tensors, 3-tuple return, autograd contract
 (grads reach every parameter and ``viewspace_points``).
 
-No GPU exists in the build container and /root/reference does not exist on the GPU box, so this is
-the only place the reference's glue can be exercised.  For that purpose -- and only inside this test
+The checkout is read in place (HGS_REFERENCE, by default the build machine's copy): the repository carries none of
+its code, and no GPU test may read it.  Without a GPU this is the only place the reference's glue can be exercised.  For that purpose -- and only inside this test
 -- the extension-module layer (`diff_gaussian_rasterization._C`) is swapped for an oracle-backed
 stand-in and ``device="cuda"`` is mapped to the CPU.  The product package itself has no such path.
 """
@@ -16,9 +16,9 @@ import types
 import pytest
 import torch
 
-REF = "/root/reference"
+REF = os.environ.get("HGS_REFERENCE", "/root/reference")
 pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "gaussian_renderer")),
-                                reason="reference checkout not present (GPU box)")
+                                reason="no reference checkout (HGS_REFERENCE)")
 
 
 from harness.cpu_backends import OracleRasterC as _OracleC   # oracle-backed extension layer (test only)
@@ -113,7 +113,7 @@ def test_render_render_post_render_coarse_run_unmodified(glue):
     assert pkg["viewspace_points"].grad[:, :2].abs().sum() > 0          # densification statistic is alive
 
     # every gradient the glue produces against the oracle chained (float64) through the activations it applied
-    # (scene/gaussian_model.py:108-128); the twin of tests/test_reference_on_gpu.py, where the op is the HIP one
+    # (scene/gaussian_model.py:108-128)
     import parity as pa
     pc = _PC(scene)
     with torch.no_grad():

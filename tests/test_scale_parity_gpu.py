@@ -2,7 +2,7 @@
 oracle at 300 k / 1080p (config 2), 1 M / 1080p (the metric configuration), the render_post call shape at 1080p
 (config 3: interpolation_weights / num_node_kids non-empty, do_depth False) and 8 M / 3840x2160 (towards config 5).
 
-The call being matched: /root/reference/train_single.py:97,123 (forward + ``loss.backward()`` at full resolution)
+The call being matched: train_single.py:97,123 (forward + ``loss.backward()`` at full resolution)
 and train_post.py:119-142.
 
 A dense oracle over a whole 1080p frame is out of reach on a CPU (2e12 pixel x Gaussian pairs), so the comparison is

@@ -5,8 +5,9 @@ reference's own extension computed; the three semantics that were restated from 
 ``interpolation_weights`` / ``num_node_kids`` (gaussian_renderer/__init__.py:262-263), the cut rule and weight formula
 (train_post.py:91-113) and the ``.hier`` byte layout (scene/gaussian_model.py:329,420-427) -- are then PINNED.
 
-No golden is committed yet (the build environment has no CUDA stack): every pin test SKIPS and says so, and parity
-stays "unpinned" (DESIGN.md section 5).  ``test_pin_kit_plumbing`` runs always: it drives the generator's own case
+No golden is committed yet (the build environment has no CUDA stack): the CPU pin tests SKIP and say so, and parity
+stays "unpinned" (DESIGN.md section 5).  The ``-m gpu`` tests then hold the HIP path to the kit's cases as the oracle
+computes them (the generator driven through the oracle-backed stand-ins), so that the HIP side of the kit runs.  ``test_pin_kit_plumbing`` runs always: it drives the generator's own case
 functions with the oracle-backed stand-ins in place of the upstream modules and feeds the resulting files to the same
 checks -- that proves the kit's keys, shapes and call signatures fit together, NOT any value."""
 import io
@@ -31,6 +32,40 @@ def _golden(name, directory=None):
         pytest.skip(f"parity unpinned: {os.path.relpath(path, os.path.dirname(HERE))} absent -- generate it with "
                     "tests/golden/make_upstream_golden.py on a machine with the upstream CUDA extensions")
     return np.load(path, allow_pickle=False)
+
+
+KIT_CASES = {"raster_config1": "case_config1", "lod_cut": "case_lod_cut", "raster_post": "case_raster_post",
+             "raster_needles": "case_needles", "hier_file": "case_hier_file"}
+
+
+def _kit_case(name):
+    """The pin kit's case ``name`` computed by the generator itself with the oracle-backed stand-ins (tests/harness) in
+    place of the upstream modules, on the CPU: the oracle's values in the golden's format."""
+    import importlib.util
+    sys.path.insert(0, HERE)
+    from harness import cpu_backends
+    import diff_gaussian_rasterization as dgr
+    import gaussian_hierarchy._C as gh
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(dgr, "_C", cpu_backends.OracleRasterC)
+        mp.setattr(gh, "expand_to_size", cpu_backends.expand_to_size)
+        mp.setattr(gh, "get_interpolation_weights", cpu_backends.get_interpolation_weights)
+        spec = importlib.util.spec_from_file_location("_pin_kit", os.path.join(HERE, "golden", "make_upstream_golden.py"))
+        kit = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(kit)
+        mp.setattr(kit, "DEV", "cpu")
+        return getattr(kit, KIT_CASES[name])()
+
+
+def _golden_for_hip(name):
+    """(golden, pinned): the upstream golden when it is committed; until then the kit's case as the oracle computes it,
+    so that the HIP side of the kit runs and holds the HIP path to the oracle on the kit's cases (parity unpinned)."""
+    if os.path.exists(os.path.join(GOLDEN_DIR, f"upstream_{name}.npz")):
+        return _golden(name), True
+    buf = io.BytesIO()
+    np.savez(buf, **_kit_case(name))
+    buf.seek(0)
+    return np.load(buf, allow_pickle=False), False
 
 
 def _scene_cam(G):
@@ -95,14 +130,15 @@ def check_raster_hip(G, what, gpu):
                     {k: v.numpy() for k, v in hip["grads"].items()}, G, f"HIP, {what}")
 
 
-def check_needles(G, what, hip_color=None):
+def check_needles(G, what, hip_color=None, verdict=True):
     """Which rule for an exponent that ROUNDING made positive does upstream follow -- "power > 0 -> skip" (SURVEY App.
     A.8, the public lineage) or the clamp at 0 of this library's kernels?  In float64 the exponent
     of a positive definite conic is never positive and the two coincide; a float32 conic loses positive definiteness only
     on extreme needles (3 000 px x 0.5 px: a c - b^2 cancels to its last bits; measured: none up to 2 500 px), and then
     on whole stripes of the image.  The oracle is run ALL in float32 under both rules (its operation order is not
     upstream's, so single pixels need not coincide -- how many pixels are far off under each rule is what tells) and, when
-    given, the HIP image is held to the golden outside the pixels where the two float32 evaluations disagree."""
+    given, the HIP image is held to the golden outside the pixels where the two float32 evaluations disagree.  ``verdict``:
+    fail when upstream follows the other rule (meaningless for a golden that is not upstream's)."""
     import parity as pa
     scene, cam = _scene_cam(G)
     args = (scene, cam, torch.from_numpy(G["bg"]), torch.from_numpy(G["gc"]), torch.from_numpy(G["gd"]))
@@ -122,7 +158,7 @@ def check_needles(G, what, hip_color=None):
     if hip_color is not None:
         off = np.abs(np.asarray(hip_color, np.float64) - gold).max(axis=0) > 1e-4
         assert not (off & ~differ).any(), f"{what}: {int((off & ~differ).sum())} HIP pixels differ from upstream where the rules agree"
-        if follows == "skip" and (off & differ).any():
+        if verdict and follows == "skip" and (off & differ).any():
             pytest.fail(f"{what}: upstream SKIPS a Gaussian whose float32 exponent is positive; the kernels clamp it: "
                         f"{int((off & differ).sum())} pixels differ -- replace the clamp in render.hip (fwd_pair_live / "
                         "bwd_pair_live) by the skip")
@@ -204,52 +240,46 @@ def test_hier_io_matches_upstream_file():
 
 
 # ---- GPU: the HIP path against upstream -------------------------------------------------------------------------------
+# (without an upstream golden the kit's case as the oracle computes it stands in: see _golden_for_hip)
+def _source(pinned):
+    return "" if pinned else " [oracle kit case, parity unpinned]"
+
+
 @pytest.mark.gpu
 def test_hip_matches_upstream_rasterizer_config1(gpu):
-    check_raster_hip(_golden("raster_config1"), "config 1", gpu)
+    G, pinned = _golden_for_hip("raster_config1")
+    check_raster_hip(G, "config 1" + _source(pinned), gpu)
 
 
 @pytest.mark.gpu
 def test_hip_matches_upstream_rasterizer_with_lod_tensors(gpu):
-    check_raster_hip(_golden("raster_post"), "render_post-shaped call (pins lod_opacity)", gpu)
+    G, pinned = _golden_for_hip("raster_post")
+    check_raster_hip(G, "render_post-shaped call (pins lod_opacity)" + _source(pinned), gpu)
 
 
 @pytest.mark.gpu
 def test_hip_needles_against_upstream(gpu):
     import parity as pa
-    G = _golden("raster_needles")
+    G, pinned = _golden_for_hip("raster_needles")
     scene, cam = _scene_cam(G)
     hip = pa.run_hip(scene, cam, torch.from_numpy(G["bg"]), torch.from_numpy(G["gc"]), torch.from_numpy(G["gd"]), gpu,
                      do_depth=True, grad_mask=None)
-    check_needles(G, "needles (HIP)", hip["color"].numpy())
+    check_needles(G, "needles (HIP)" + _source(pinned), hip["color"].numpy(), verdict=pinned)
 
 
 @pytest.mark.gpu
 def test_hip_matches_upstream_cut_and_weights(gpu):
-    check_lod_hip(_golden("lod_cut"), gpu)
+    G, pinned = _golden_for_hip("lod_cut")
+    check_lod_hip(G, gpu)
 
 
 # ---- the kit itself -----------------------------------------------------------------------------------------------------
-def test_pin_kit_plumbing(tmp_path, monkeypatch):
+def test_pin_kit_plumbing(tmp_path):
     """Generator case functions -> .npz -> the checks above, with the oracle-backed stand-ins (tests/harness) playing the
     upstream modules on the CPU.  Values are the oracle's own, so this pins NOTHING; it proves that the generator's
     keys / shapes / call signatures and the consumer fit, so that the first real golden does not die on a typo."""
-    import importlib.util
-    sys.path.insert(0, HERE)
-    from harness import cpu_backends
-    import diff_gaussian_rasterization as dgr
-    import gaussian_hierarchy._C as gh
-    monkeypatch.setattr(dgr, "_C", cpu_backends.OracleRasterC)
-    monkeypatch.setattr(gh, "expand_to_size", cpu_backends.expand_to_size)
-    monkeypatch.setattr(gh, "get_interpolation_weights", cpu_backends.get_interpolation_weights)
-    spec = importlib.util.spec_from_file_location("_pin_kit", os.path.join(HERE, "golden", "make_upstream_golden.py"))
-    kit = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kit)
-    monkeypatch.setattr(kit, "DEV", "cpu")
-    for name, fn in (("raster_config1", kit.case_config1), ("lod_cut", kit.case_lod_cut),
-                     ("raster_post", kit.case_raster_post), ("raster_needles", kit.case_needles),
-                     ("hier_file", kit.case_hier_file)):
-        np.savez_compressed(os.path.join(tmp_path, f"upstream_{name}.npz"), **fn())
+    for name in KIT_CASES:
+        np.savez_compressed(os.path.join(tmp_path, f"upstream_{name}.npz"), **_kit_case(name))
     d = str(tmp_path)
     check_raster_oracle(_golden("raster_config1", d), "config 1 (plumbing)")
     G = _golden("raster_post", d)
