@@ -582,4 +582,28 @@ int hgs_sort_pairs(const uint64_t* keys_in, const uint32_t* vals_in, uint64_t* k
   return sort_pairs(keys_in, vals_in, keys_out, vals_out, tmp, n, end_bit, static_cast<hipStream_t>(stream), false);
 }
 
+constexpr int32_t kHierBuildMaxP = 1 << 30;
+
+size_t hgs_hier_build_tmp_bytes(int32_t P) {
+  if (P < 1 || P > kHierBuildMaxP) return 0;
+  return hier_build_tmp_bytes(P);
+}
+
+int hgs_hier_build(const float* xyz, const float* scales, const float* rots, const float* opacity, const float* shs,
+                   int32_t P, int32_t M, float* out_xyz, float* out_shs, float* out_alpha, float* out_log_scales,
+                   float* out_rots, int32_t* out_nodes, float* out_boxes, void* tmp, hgs_stream_t stream, int device) {
+  if (P < 1 || P > kHierBuildMaxP) { set_error("bad sizes: P=%d not in [1, 2^30]", P); return HGS_ERR_INVALID; }
+  if (M != 1 && M != 4 && M != 9 && M != 16) { set_error("bad sizes: M=%d not in {1, 4, 9, 16}", M); return HGS_ERR_INVALID; }
+  if (!xyz || !scales || !rots || !opacity || !shs || !out_xyz || !out_shs || !out_alpha || !out_log_scales ||
+      !out_rots || !out_nodes || !out_boxes || !tmp) {
+    set_error("null argument");
+    return HGS_ERR_INVALID;
+  }
+  if (((uintptr_t)out_shs | (uintptr_t)out_rots | (uintptr_t)out_boxes) & 15u) { set_error("out_shs / out_rots / out_boxes must be 16-byte aligned"); return HGS_ERR_INVALID; }
+  if ((uintptr_t)tmp & (kAlign - 1)) { set_error("tmp must be %d-byte aligned", (int)kAlign); return HGS_ERR_INVALID; }
+  HGS_HIP(hipSetDevice(device));
+  return launch_hier_build(xyz, scales, rots, opacity, shs, P, M, out_xyz, out_shs, out_alpha, out_log_scales, out_rots,
+                           out_nodes, out_boxes, tmp, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -299,5 +299,10 @@ int sort_pairs(const uint64_t* keys_in, const uint32_t* vals_in, uint64_t* keys_
 // device, n then being a capacity
 int sort_pairs32(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out, uint32_t* vals_out,
                  void* tmp, uint32_t n, const uint32_t* n_dev, int end_bit, hipStream_t s, bool debug);
+// hierarchy construction (hier_build.hip): sizes checked by the caller (1 <= P <= 2^30, M in {1, 4, 9, 16})
+size_t hier_build_tmp_bytes(int32_t P);
+int launch_hier_build(const float* xyz, const float* scales, const float* rots, const float* opacity, const float* shs,
+                      int32_t P, int32_t M, float* out_xyz, float* out_shs, float* out_alpha, float* out_log_scales,
+                      float* out_rots, int32_t* out_nodes, float* out_boxes, void* tmp, hipStream_t s);
 
 }  // namespace hgs

@@ -102,6 +102,9 @@ SIGNATURES = {
                                        C.POINTER(RasterViews)]),
     "hgs_sort_tmp_bytes": (C.c_size_t, [C.c_uint32]),
     "hgs_sort_pairs": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_int, _P, C.c_int]),
+    "hgs_hier_build_tmp_bytes": (C.c_size_t, [C.c_int32]),
+    "hgs_hier_build": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                 C.c_int]),
     "hgs_timing_enable": (C.c_int, [C.c_int]),
     "hgs_timing_stage_count": (C.c_int, []),
     "hgs_timing_stage_name": (C.c_char_p, [C.c_int]),

@@ -1,10 +1,11 @@
-"""Synthetic Gaussian hierarchies for the LOD-cut path (BASELINE.json configs 3 and 5).
+"""Gaussian hierarchies for the LOD-cut path (BASELINE.json configs 3 and 5).
 
 The reference builds hierarchies offline with its GaussianHierarchyCreator / Merger tools
-(scripts/full_train.py:138-139,188-196,242-250 -- C++ sources absent, out of scope).  This
-module only produces *inputs* for ``expand_to_size`` / ``get_interpolation_weights`` /
-``render_post``-style rendering: a balanced binary BVH over Morton-sorted leaves, interior
-nodes holding a moment-matched merge of their children.  Layout = DESIGN.md '.hier layout':
+(scripts/full_train.py:138-139,188-196,242-250 -- C++ sources absent).  This module defines this
+project's own construction rule (``build_hierarchy``, the float64 numpy spec; ``build_hierarchy_gpu``,
+the same rule on the device, behind ``python -m hgs.create_hierarchy``): a balanced binary BVH over
+Morton-sorted leaves, interior nodes holding a moment-matched merge of their children.
+Layout = DESIGN.md '.hier layout':
 
   one Gaussian per node, Gaussian index == node index (``start`` = node id)
   nodes int32 [N,7] = depth, parent, start, count_leafs, count_merged, start_children, count_children
@@ -166,6 +167,41 @@ def build_hierarchy(scene) -> Hierarchy:
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
     return Hierarchy(xyz=t(mu), shs=t(sh), alpha=t(op[:, None]), log_scales=t(np.log(scales)), rots=t(quat),
                      nodes=torch.from_numpy(nodes), boxes=torch.from_numpy(boxes))
+
+
+def build_hierarchy_gpu(scene, device=None) -> Hierarchy:
+    """``build_hierarchy`` on the GPU (csrc/hier_build.hip, hgs_hier_build): same input (an hgs.synth.Scene of activated
+    rows, M in {1, 4, 9, 16} SH coefficients), same topology, numbering and merge rule, a ``Hierarchy`` of tensors on
+    ``device`` (default: the current GPU).  nodes, boxes and the leaf rows of xyz / shs / alpha / rots are bit-exact
+    against ``build_hierarchy``; interior rows agree to rounding.  No CPU fallback: raises without
+    libhgs.so or a GPU."""
+    import ctypes as C
+    from . import _lib
+    lib = _lib.lib()
+    if not torch.cuda.is_available():
+        raise RuntimeError("build_hierarchy_gpu needs a GPU (there is no CPU fallback; build_hierarchy is the numpy spec)")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    P = int(scene.means3D.shape[0])
+    M = int(scene.shs.shape[1])
+    if P < 1:
+        raise ValueError("build_hierarchy_gpu needs at least one Gaussian")
+    if M not in (1, 4, 9, 16):
+        raise ValueError(f"M = {M} SH coefficients; 1, 4, 9 or 16 expected")
+    f = lambda t, *shape: t.detach().to(dev, torch.float32).reshape(*shape).contiguous()
+    xyz, scales, rots = f(scene.means3D, P, 3), f(scene.scales, P, 3), f(scene.rotations, P, 4)
+    opacity, shs = f(scene.opacities, P), f(scene.shs, P, M, 3)
+    N = 2 * P - 1
+    e = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
+    out = Hierarchy(xyz=e(N, 3), shs=e(N, 16, 3), alpha=e(N, 1), log_scales=e(N, 3), rots=e(N, 4),
+                    nodes=e(N, 7, dtype=torch.int32), boxes=e(N, 2, 4))
+    tmp = e(lib.hgs_hier_build_tmp_bytes(P), dtype=torch.uint8)
+    p = _lib.ptr
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.hgs_hier_build(p(xyz), p(scales), p(rots), p(opacity), p(shs), P, M, p(out.xyz), p(out.shs),
+                                      p(out.alpha), p(out.log_scales), p(out.rots), p(out.nodes), p(out.boxes), p(tmp),
+                                      stream, dev.index or 0), "hgs_hier_build")
+    return out
 
 
 def build_hierarchy_on_device(P, cam, device, seed=0, sh_degree=3, s_px=(0.5, 4.0), z_range=(2.0, 20.0)) -> Hierarchy:

@@ -398,6 +398,23 @@ int hgs_hier_write(const char* path, const hgs_hier_host* in);
 void hgs_hier_free(hgs_hier_host* h);
 
 /* ---------------------------------------------------------------------------
+ * Hierarchy construction on the device: the rule of hgs.hierarchy.build_hierarchy.
+ * Inputs (device, activated): xyz [P,3], scales [P,3] linear, rots [P,4] (w,x,y,z), opacity [P] in [0,1],
+ * shs [P,M,3] with M in {1,4,9,16}; 1 <= P <= 2^30.  Outputs (device) for N = 2P - 1 nodes, Gaussian index == node
+ * index, BFS numbering with contiguous children: xyz [N,3], shs [N,16,3] (zero-padded), alpha [N], log_scales [N,3],
+ * rots [N,4], nodes int32 [N,7], boxes [N,2,4]; out_shs / out_rots / out_boxes 16-byte aligned.  Leaves keep their
+ * input rotation and log of their input scales; interior nodes hold the w = alpha * s0 * s1 * s2 weighted moment match
+ * of their children, rotation and scales from an eigen-solve of the merged covariance.  nodes, boxes and the leaf rows
+ * of xyz / shs / alpha / rots equal build_hierarchy's bit for bit.
+ * hgs_hier_build_tmp_bytes: host only (no GPU needed); 0 for a P outside [1, 2^30].
+ * hgs_hier_build: asynchronous on `stream` (level sizes are host arithmetic: no host round trip); sizes are checked
+ * before any HIP call. */
+size_t hgs_hier_build_tmp_bytes(int32_t P);
+int hgs_hier_build(const float* xyz, const float* scales, const float* rots, const float* opacity, const float* shs,
+                   int32_t P, int32_t M, float* out_xyz, float* out_shs, float* out_alpha, float* out_log_scales,
+                   float* out_rots, int32_t* out_nodes, float* out_boxes, void* tmp, hgs_stream_t stream, int device);
+
+/* ---------------------------------------------------------------------------
  * Direct (two-shot) SUM all-reduce over peer pointers: the exchange step of per-view data parallelism (SURVEY.md
  * section 8(e); the reference itself is single-GPU: train_single.py:57-59 renders one camera per step, nothing to
  * replace).  One process per GPU; every rank allocates its gradient bucket and a small flag block with hgs_p2p_alloc,
