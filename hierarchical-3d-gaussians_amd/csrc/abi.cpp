@@ -163,13 +163,15 @@ void set_error(const char* fmt, ...) {
 size_t GeomWs::bytes(int32_t P) {
   const size_t p = (size_t)(P > 0 ? P : 1);
   const size_t nblk = (p + kPreBlock - 1) / kPreBlock;
+  const size_t jac_rows = (p + 63) / 64 * 64;   // K1's H48 route stores the Jacobians of whole 64-row waves
   return align_up(p * kRecFloats * 4) + align_up(p * 4) + align_up(p * 8) + 3 * align_up(p * 4) +
-         align_up((nblk + 1) * 4) + align_up((nblk + 1) * kBands * 4) + align_up(p * kJacStride * 4) +
+         align_up((nblk + 1) * 4) + align_up((nblk + 1) * kBands * 4) + align_up(jac_rows * kJacStride * 4) +
          align_up((size_t)(1 + kBands) * scan_chunks(nblk) * 8) + kAlign;
 }
 GeomWs GeomWs::carve_from(void* base, int32_t P) {
   const size_t p = (size_t)(P > 0 ? P : 1);
   const size_t nblk = (p + kPreBlock - 1) / kPreBlock;
+  const size_t jac_rows = (p + 63) / 64 * 64;   // (as in bytes())
   char* c = static_cast<char*>(base);
   GeomWs g;
   g.records = carve<float>(c, p * kRecFloats);
@@ -180,7 +182,7 @@ GeomWs GeomWs::carve_from(void* base, int32_t P) {
   g.flags = carve<uint32_t>(c, p);
   g.block_sums = carve<uint32_t>(c, nblk + 1);
   g.block_band = carve<uint32_t>(c, (nblk + 1) * kBands);
-  g.shjac = carve<float>(c, p * kJacStride);
+  g.shjac = carve<float>(c, jac_rows * kJacStride);
   g.scan_chain = carve<unsigned long long>(c, (size_t)(1 + kBands) * scan_chunks(nblk));
   return g;
 }

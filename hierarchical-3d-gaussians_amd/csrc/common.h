@@ -66,7 +66,7 @@ struct GeomWs {
   uint32_t* block_sums;    // [nblk+1] exclusive scan of per-workgroup instance counts (index order); [nblk] = L
   uint32_t* block_band;    // [kBands][nblk+1] the same per tile band: column b = exclusive scan of the workgroups' counts of
                            // instances whose tile lies in band b; [b][nblk] = the band's total
-  float* shjac;            // [P,kJacStride] d(rgb)/d(view direction): 9 values, rows = direction component (hgs_raster_args.prepare_backward)
+  float* shjac;            // [ceil64(P),kJacStride] d(rgb)/d(view direction): 9 values, rows = direction component (hgs_raster_args.prepare_backward)
   unsigned long long* scan_chain;  // [(1 + kBands) * scan_chunks(nblk)] published chunk totals of the K2 scans (K1 clears it)
   static size_t bytes(int32_t P);
   static GeomWs carve_from(void* base, int32_t P);

@@ -513,7 +513,8 @@ __device__ __forceinline__ void wave_store_rows(float4* __restrict__ dst, size_t
 
 // The 36-byte Jacobian rows of the wave's 64 Gaussians the same way: nine words per lane at a stride of nine (odd: no
 // bank conflict), read back as the 144 consecutive 16-byte pieces they are in memory.  A wave with no visible row
-// stores nothing; otherwise all 64 rows are written (the rows of culled Gaussians are never read).
+// stores nothing; otherwise all 64 rows are written (the rows of culled Gaussians are never read) -- in the last wave
+// also the rows from P up to the next multiple of 64, which is why GeomWs sizes shjac for ceil(P / 64) * 64 rows.
 __device__ __forceinline__ void wave_store_jac(float* __restrict__ dst, size_t row0, const float (&J)[9],
                                                unsigned long long mask, float4* wave_lds) {
   const int lane = threadIdx.x & 63;
