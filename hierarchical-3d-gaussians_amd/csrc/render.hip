@@ -7,7 +7,14 @@
 // CDNA4 design (not the CUDA 256-threads-one-pixel-each shape):
 //  * ONE WAVE RENDERS A WHOLE 16x16 TILE and every lane owns four pixels -- no workgroup barrier, no inter-wave
 //    accumulation.
-//  * QUADRANT STREAMS (round 3).  A tile instance of the benchmark scene touches ~25 of the tile's 256 pixels; walking the
+//  * CELL STREAMS in K6.  The forward cuts the tile finer: its sixteen QUADS (4 lanes each) own the sixteen 4x4 CELLS of
+//    the tile and walk sixteen lists (cell_hit: K1's box in column / row bands AND the quadrant's exact test), a lane
+//    keeps a column of four pixels as two packed pairs, so the visit below is the same instruction stream and an
+//    iteration serves up to sixteen instances: 0.28 iterations per instance of the benchmark scene instead of 0.40
+//    (tests/tools/cell_stats.py; K6 146 -> 124 us).  The same layout in K7 (batch 32, 128 pair slots, quad-local DPP
+//    sums) measured 253 -> 280 us -- the staging of sixteen lists and the per-pair stores cost more than the iterations
+//    it saves -- so the backward keeps the quadrants described next.
+//  * QUADRANT STREAMS (round 3; K7).  A tile instance of the benchmark scene touches ~25 of the tile's 256 pixels; walking the
 //    tile's list wave-uniformly (rounds 1-2: every visited instance costs a pass over a 16x8 half = 128 pixel slots)
 //    leaves four lanes in five idle.  Here the four DPP ROWS of the wave (16 lanes each) own the four 8x8 QUADRANTS of
 //    the tile and each row walks ITS OWN list: the lane that stages an instance of the 64-instance batch tests K1's
@@ -147,7 +154,21 @@ __device__ __forceinline__ LaneGeom lane_geom(int lane) {
   return g;
 }
 
-// What the staging lane decides for its instance: which quadrants can hold a candidate pixel at all.
+// K6: quad (= lane >> 2) = 4x4 CELL c of the tile, cell (c & 3, c >> 2) of the tile's 4x4 grid of cells (the DPP row of
+// the lane is the cell row).  Lane l owns the column x = 4 (c & 3) + (l & 3) of its cell, rows y0 .. y0 + 3 with
+// y0 = 4 (c >> 2); the pixel pairs are (y0, y0 + 1) and (y0 + 2, y0 + 3).
+struct CellGeom {
+  int c, lx, ly0;   // cell, x inside the tile, y of pixel 0 inside the tile
+};
+__device__ __forceinline__ CellGeom cell_geom(int lane) {
+  CellGeom g;
+  g.c = lane >> 2;
+  g.lx = ((g.c & 3) << 2) + (lane & 3);
+  g.ly0 = (g.c >> 2) << 2;
+  return g;
+}
+
+// What the staging lane decides for its instance: which quadrants (K7) / cells (K6) can hold a candidate pixel at all.
 //  1. K1's alpha >= 1/255 BOX (ext_x, ext_y around the tile-relative centre) against the quadrants' pixel ranges;
 //  2. the exact test "max of the exponent over the quadrant's rectangle >= skip threshold": the box of a
 //     slanted ellipse reaches quadrants the ellipse itself misses (7 % of the visits on the benchmark scene, 12 % on the
@@ -156,6 +177,9 @@ __device__ __forceinline__ LaneGeom lane_geom(int lane) {
 //     runs through the rectangle, along it the exponent grows): one 1-D maximisation per facing edge, at most two per
 //     quadrant.  Continuous rectangle >= its pixel centres, plus a guard of 0.02 in the base-2 exponent: conservative;
 //     the per-pixel candidate and alpha tests still take every decision.  A NaN (degenerate conic) counts as a hit.
+//  K6's cells: K1's box in four column x four row bands AND the quadrant's exact test (cell_hit).  The same exact test per
+//  CELL would keep 99.8 % of what the per-pixel floor saves over the quadrants instead of 83 % (66 % on the heavy scene,
+//  tests/tools/cell_stats.py), but costs sixteen rectangle maximisations per staged instance: more than it saves.
 struct QuadHit {
   bool q0, q1, q2, q3;
 };
@@ -191,6 +215,21 @@ __device__ __forceinline__ QuadHit quad_hit(float gxt, float gyt, float ex, floa
   }
   h.q0 = h.q0 && e[0]; h.q1 = h.q1 && e[1]; h.q2 = h.q2 && e[2]; h.q3 = h.q3 && e[3];
   return h;
+}
+// bit c of the result: cell c can hold a candidate pixel (box bands AND the quadrant's exact test)
+__device__ __forceinline__ uint32_t cell_hit(float gxt, float gyt, float ex, float ey, float A2, float B2, float C2,
+                                             float thr) {
+  const QuadHit h = quad_hit(gxt, gyt, ex, ey, A2, B2, C2, thr);
+  uint32_t xb = 0, yb = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    xb |= (uint32_t)((gxt - ex <= (float)(4 * i + 3)) && (gxt + ex >= (float)(4 * i))) << i;
+    yb |= (uint32_t)((gyt - ey <= (float)(4 * i + 3)) && (gyt + ey >= (float)(4 * i))) << i;
+  }
+  // columns x rows: the box's cells; the quadrants' cells: q0 {0,1,4,5}, q1 {2,3,6,7}, q2 {8,9,12,13}, q3 {10,11,14,15}
+  const uint32_t box = xb * ((yb & 1u) | ((yb & 2u) << 3) | ((yb & 4u) << 6) | ((yb & 8u) << 9));
+  const uint32_t qm = (h.q0 ? 0x0033u : 0u) | (h.q1 ? 0x00ccu : 0u) | (h.q2 ? 0x3300u : 0u) | (h.q3 ? 0xcc00u : 0u);
+  return box & qm;
 }
 
 // ================================================================================
@@ -235,14 +274,16 @@ __device__ __forceinline__ void fwd_pair_live(FwdPair<DEPTH>& p, f2 pw, const fl
   p.T = f2{blend0 ? Tn.x : p.T.x, blend1 ? Tn.y : p.T.y};
   p.last0 = blend0 ? idx1 : p.last0;
   p.last1 = blend1 ? idx1 : p.last1;
-  p.fly.x = stop0 ? kBig : p.fly.x;      // a saturated pixel leaves the tile (see above); whether a whole quadrant
+  p.fly.x = stop0 ? kBig : p.fly.x;      // a saturated pixel leaves the tile (see above); whether a whole cell
   p.fly.y = stop1 ? kBig : p.fly.y;      // is finished is checked once per batch, not per stop event
 }
 
-// (6 waves per SIMD at 78 registers: 8 160 one-wave tiles on 1 024 SIMDs are 1.33 rounds; fewer resident waves cost more
-// than whole rounds win, a 64-register build spills -- profiles/r05_occupancy_vs_rounds.txt)
+// (6 waves per SIMD, at most 80 registers: 8 160 one-wave tiles on 1 024 SIMDs are 1.33 rounds; fewer resident waves cost
+// more than whole rounds win, a 64-register build spills -- profiles/r05_occupancy_vs_rounds.txt.  Stated to the compiler:
+// left to itself it schedules the sixteen cells' staging tests side by side at 90 registers)
+constexpr int kK6Waves = 6;
 template <bool DEPTH, bool LODA>
-__global__ __launch_bounds__(64) void render_fwd_quad_kernel(
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kK6Waves, kK6Waves))) void render_fwd_quad_kernel(
     const uint32_t* __restrict__ ranges, const uint32_t* __restrict__ point_list,
     const float4* __restrict__ records, int W, int H, int gx, int T, const float* __restrict__ bg,
     float* __restrict__ out_color, float* __restrict__ out_invdepth, float* __restrict__ final_T,
@@ -252,15 +293,15 @@ __global__ __launch_bounds__(64) void render_fwd_quad_kernel(
   // float4 per staged Gaussian: (gxt,gyt,A2,B2) (C2,o,r,g) (b,1/z,thr,-); LODA: + (weight, 1 / siblings or 0, -, -)
   constexpr int kLds = LODA ? 4 : 3;
   __shared__ float4 lrec[(kB + 1) * kLds];
-  // entry `it`: 16 bits per quadrant q = the it-th instance of q's list as the BYTE OFFSET of its record in `lrec`
+  // entry `it`: 16 bits per cell c = the it-th instance of c's list as the BYTE OFFSET of its record in `lrec`
   // (instance kB: none); three spare entries for the look-ahead
-  __shared__ uint2 qlist[kB + 3];
+  __shared__ uint4 qlist[(kB + 3) * 2];
   constexpr uint32_t kRecBytes = kLds * 16;
 
   TileGeom tg;
   if (!block_to_tile(T, gx, order, tg)) return;
   const int lane = threadIdx.x;
-  const LaneGeom lg = lane_geom(lane);
+  const CellGeom lg = cell_geom(lane);
   const int px = tg.tx * kTile + lg.lx;
   const int py0 = tg.ty * kTile + lg.ly0;
   const float flx = (float)lg.lx;
@@ -268,16 +309,16 @@ __global__ __launch_bounds__(64) void render_fwd_quad_kernel(
 
   bool inside[4];
 #pragma unroll
-  for (int s = 0; s < 4; ++s) inside[s] = (px < W) && (py0 + 2 * s < H);
+  for (int s = 0; s < 4; ++s) inside[s] = (px < W) && (py0 + s < H);
   FwdPair<DEPTH> P0, P1;
-  P0.fly = f2{inside[0] ? (float)lg.ly0 : kBig, inside[1] ? (float)(lg.ly0 + 2) : kBig};
-  P1.fly = f2{inside[2] ? (float)(lg.ly0 + 4) : kBig, inside[3] ? (float)(lg.ly0 + 6) : kBig};
+  P0.fly = f2{inside[0] ? (float)lg.ly0 : kBig, inside[1] ? (float)(lg.ly0 + 1) : kBig};
+  P1.fly = f2{inside[2] ? (float)(lg.ly0 + 2) : kBig, inside[3] ? (float)(lg.ly0 + 3) : kBig};
   P0.T = P1.T = splat(1.0f);
   P0.Cr = P0.Cg = P0.Cb = P0.Dd = P1.Cr = P1.Cg = P1.Cb = P1.Dd = splat(0.0f);
   P0.last0 = P0.last1 = P1.last0 = P1.last1 = 0;
 
   const uint32_t r0 = ranges[tg.tile * 2 + 0], r1 = ranges[tg.tile * 2 + 1];
-  // quadrants that still have an unfinished pixel (bits 16 q .. 16 q + 15 of the ballot)
+  // cells that still have an unfinished pixel (bits 4 c .. 4 c + 3 of the ballot)
   uint64_t alive = __ballot(inside[0] || inside[1] || inside[2] || inside[3]);
   if (lane == 0) {     // the dummy instance: opacity 0, threshold +inf
     lrec[kB * kLds + 0] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -285,13 +326,13 @@ __global__ __launch_bounds__(64) void render_fwd_quad_kernel(
     lrec[kB * kLds + 2] = make_float4(0.f, 0.f, __builtin_inff(), 0.f);
     if constexpr (LODA) lrec[kB * kLds + 3] = make_float4(1.f, 0.f, 0.f, 0.f);
   }
-  const uint16_t* myq = reinterpret_cast<const uint16_t*>(qlist) + lg.q;
+  const uint16_t* myq = reinterpret_cast<const uint16_t*>(qlist) + lg.c;
 
   for (uint32_t base = r0; base < r1 && alive != 0; base += kB) {
     // wave-uniform by construction; readfirstlane tells the compiler so
     const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)min((uint32_t)kB, r1 - base));
     __syncthreads();
-    QuadHit hit{false, false, false, false};
+    uint32_t hit = 0;
     if ((uint32_t)lane < n) {
       const uint32_t gid = point_list[base + lane];
       const float4* r = records + (size_t)gid * kRecVec;
@@ -300,7 +341,7 @@ __global__ __launch_bounds__(64) void render_fwd_quad_kernel(
       a0.x = (a0.x - tile_x0) + a3.x;       // tile-relative pixel centre, once per (tile, Gaussian)
       a0.y = (a0.y - tile_y0) + a3.y;
       const float4 a1 = r[1];
-      hit = quad_hit(a0.x, a0.y, a2.z, a3.w, a0.z, a0.w, a1.x, a3.z);
+      const float ex = a2.z;
       a2.z = a3.z;                           // skip threshold
       lrec[lane * kLds + 0] = a0;
       lrec[lane * kLds + 1] = a1;
@@ -309,27 +350,26 @@ __global__ __launch_bounds__(64) void render_fwd_quad_kernel(
         const int kids = lod_kids[gid];
         lrec[lane * kLds + 3] = make_float4(lod_w[gid], kids >= 2 ? 1.0f / (float)kids : 0.0f, 0.f, 0.f);
       }
+      hit = cell_hit(a0.x, a0.y, ex, a3.w, a0.z, a0.w, a1.x, a3.z);
     }
-    // a finished quadrant takes no more instances
-    hit.q0 = hit.q0 && (alive & 0xffffull) != 0;
-    hit.q1 = hit.q1 && (alive & 0xffff0000ull) != 0;
-    hit.q2 = hit.q2 && (alive & 0xffff00000000ull) != 0;
-    hit.q3 = hit.q3 && (alive & 0xffff000000000000ull) != 0;
-    // one mask per quadrant in scalar registers
-    const uint64_t m0 = __ballot(hit.q0), m1 = __ballot(hit.q1), m2 = __ballot(hit.q2), m3 = __ballot(hit.q3);
-    // the quadrants' lists, front to back: entry = rank of the instance inside its quadrant's mask.  (DS operations of
-    // one wave execute in order: the fill is complete before the byte stores.)
-    for (int i = lane; i < kB + 3; i += 64) qlist[i] = make_uint2(0x00010001u * (kB * kRecBytes), 0x00010001u * (kB * kRecBytes));
+    // a finished cell takes no more instances: bit c of `live_cells` (lanes 0-15 look at the cells' four lanes)
+    const uint32_t live_cells = (uint32_t)__ballot(lane < 16 && ((alive >> (4 * (lane & 15))) & 0xfull) != 0);
+    hit &= live_cells;
+    // the cells' lists, front to back: entry = rank of the instance inside its cell's mask (one mask per cell in scalar
+    // registers).  (DS operations of one wave execute in order: the fill is complete before the entries' stores.)
+    constexpr uint32_t kNone = 0x00010001u * (kB * kRecBytes);
+    for (int i = lane; i < (kB + 3) * 2; i += 64) qlist[i] = make_uint4(kNone, kNone, kNone, kNone);
     uint16_t* ql16 = reinterpret_cast<uint16_t*>(qlist);
     const uint16_t mine = (uint16_t)((uint32_t)lane * kRecBytes);
-    if (hit.q0) ql16[rank_below(m0) * 4 + 0] = mine;
-    if (hit.q1) ql16[rank_below(m1) * 4 + 1] = mine;
-    if (hit.q2) ql16[rank_below(m2) * 4 + 2] = mine;
-    if (hit.q3) ql16[rank_below(m3) * 4 + 3] = mine;
-    const int nmax = max(max(__builtin_popcountll(m0), __builtin_popcountll(m1)),
-                         max(__builtin_popcountll(m2), __builtin_popcountll(m3)));
+    int nmax = 0;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+      const uint64_t m = __ballot((hit >> c) & 1u);
+      if ((hit >> c) & 1u) ql16[rank_below(m) * 16 + c] = mine;
+      nmax = max(nmax, __builtin_popcountll(m));
+    }
     __syncthreads();
-    // one (instance, quadrant) pair per row of the wave
+    // one (instance, cell) pair per quad of the wave
     auto visit = [&](uint32_t j, const float4& q0, const float4& q1, const float4& q2) {
       float lw = 0.0f, lik = 0.0f;
       if constexpr (LODA) {
@@ -352,15 +392,15 @@ __global__ __launch_bounds__(64) void render_fwd_quad_kernel(
       fwd_pair_live<DEPTH, LODA>(P0, pw0, q1, q2, idx1, lw, lik);
       fwd_pair_live<DEPTH, LODA>(P1, pw1, q1, q2, idx1, lw, lik);
     };
-    uint32_t jA = myq[0], jB = myq[4];
+    uint32_t jA = myq[0], jB = myq[16];
     float4 A0 = record_at(lrec, jA)[0], A1 = record_at(lrec, jA)[1], A2 = record_at(lrec, jA)[2];
     for (int it = 0; it < nmax; it += 2) {
       const float4 B0 = record_at(lrec, jB)[0], B1 = record_at(lrec, jB)[1], B2 = record_at(lrec, jB)[2];
-      const uint32_t jA2 = myq[(it + 2) * 4];
+      const uint32_t jA2 = myq[(it + 2) * 16];
       visit(jA, A0, A1, A2);
       if (it + 1 < nmax) {
         A0 = record_at(lrec, jA2)[0]; A1 = record_at(lrec, jA2)[1]; A2 = record_at(lrec, jA2)[2];
-        const uint32_t jB2 = myq[(it + 3) * 4];
+        const uint32_t jB2 = myq[(it + 3) * 16];
         visit(jB, B0, B1, B2);
         jB = jB2;
       }
@@ -380,7 +420,7 @@ __global__ __launch_bounds__(64) void render_fwd_quad_kernel(
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
     if (inside[s]) {
-      const size_t pix = (size_t)(py0 + 2 * s) * W + px;
+      const size_t pix = (size_t)(py0 + s) * W + px;
       out_color[pix] = cr[s] + Tf[s] * b0;
       out_color[plane + pix] = cg[s] + Tf[s] * b1;
       out_color[2 * plane + pix] = cb[s] + Tf[s] * b2;
