@@ -49,6 +49,7 @@ ALPHA_MIN = 1.0 / 255.0
 ALPHA_MAX = 0.99
 T_EPS = 1e-4
 FRAGILE_FP32_K = 8.0 * 2.0 ** -24     # float32 roundings of the exponent's chain, per unit of its terms' magnitudes
+OUTCOME_CAP = 16                      # admissible outcomes enumerated per knife-edge pixel at most
 F = np.float32
 
 SH_C0 = 0.28209479177387814
@@ -322,6 +323,41 @@ def _cov3d_torch(scales, rotations, scale_modifier):
     return Lm @ Lm.transpose(1, 2)
 
 
+# --------------------------------------------------------------------------
+# knife-edge bands: the ONE statement of how far a float32 evaluation may stray from the float64 one
+# --------------------------------------------------------------------------
+def alpha_band(M, tol):
+    """Relative half-width of the band around ``alpha = 1/255``.  The exponent is a sum of three products that cancel
+    (|A dx^2|, |C dy^2|, |B dx dy| reach thousands for a Gaussian hundreds of pixels wide while their sum stays at -5.5),
+    so a float32 alpha carries a relative error of about 2^-24 per unit of ``M`` = the sum of their magnitudes, times the
+    handful of roundings in the chain (``FRAGILE_FP32_K``); a fixed 1e-5 band missed flips at 1/255 on the trained 1080p
+    scene of round 5 (3 of 49 128 values, profiles/r05_config2_config3_scripts.log)."""
+    return tol + FRAGILE_FP32_K * M
+
+
+def t_noise(alpha, araw, M):
+    """Relative error one blended entry adds to the transmittance behind it: its alpha's error (``alpha_band`` without
+    the floor) through ``1 - alpha``.  An alpha AT the 0.99 cap is a constant and adds none.  Elementwise (torch)."""
+    return torch.where(araw < ALPHA_MAX, alpha / (1.0 - alpha).clamp_min(1e-2) * (FRAGILE_FP32_K * M),
+                       torch.zeros_like(M))
+
+
+def on_alpha_edge(alpha, band):
+    """``alpha >= 1/255`` may go either way (``band`` from ``alpha_band``).  Tensors or floats."""
+    return abs(alpha - ALPHA_MIN) < band * ALPHA_MIN
+
+
+def on_t_edge(T, band_T):
+    """``T (1 - alpha) < 1e-4`` may go either way (``band_T``: the floor plus the ``t_noise`` of every entry blended
+    so far, this one included).  Tensors or floats."""
+    return abs(T - T_EPS) < band_T * T_EPS
+
+
+def on_power_edge(power):
+    """The exponent's sign test (``skip`` rule: a positive exponent is not blended) may go either way."""
+    return abs(power) < 1e-12
+
+
 @dataclass
 class OracleOut:
     color: torch.Tensor        # [3,H,W]
@@ -332,13 +368,128 @@ class OracleOut:
     binning: Binning
     n_contrib: np.ndarray      # [H,W] int32 index (1-based, in the tile list) of the last blended Gaussian
     final_T: np.ndarray        # [H,W] float
+    rows: dict = None          # {flat pixel: PixelRow} of every fragile pixel (and of ``capture`` pixels)
+    keep: dict = None          # {tile: [pixels of the tile, list length] bool} (``return_keep=True``)
+    bg: np.ndarray = None      # [3] background in the blend precision
+    fragile_tol: float = 0.0
+
+
+@dataclass
+class PixelRow:
+    """Per-entry blend inputs of one pixel over its tile list, as ``rasterize`` computed them (detached): what
+    ``admissible_outcomes`` walks."""
+    ids: np.ndarray            # [n] Gaussian row of each entry
+    alpha: np.ndarray          # [n] opacity * G, capped at 0.99
+    power: np.ndarray          # [n] exponent
+    band: np.ndarray           # [n] ``alpha_band`` of each entry
+    noise: np.ndarray          # [n] ``t_noise`` of each entry, were it blended
+    rgb: np.ndarray            # [n,3]
+    invz: np.ndarray           # [n]
+
+
+@dataclass
+class Outcome:
+    color: np.ndarray          # [3]
+    invdepth: float
+    final_T: float
+    n_contrib: int
+    keep: np.ndarray           # [n] bool: the entries blended
+    decisions: tuple           # ((kind, side), ...) taken at every knife edge: kind "alpha" | "T" | "power"
+
+
+def admissible_outcomes(out: OracleOut, pixels=None, cap=OUTCOME_CAP):
+    """Every result a float32 blend may legitimately produce at each pixel of ``pixels`` (flat indices; default: the
+    fragile ones).  Walks the pixel's tile list front to back in float64 as ``naive_per_pixel_blend`` does and branches at
+    every decision that lies inside its band (``alpha_band`` / ``t_noise`` / ``on_*_edge``, the very numbers
+    ``rasterize`` flagged the pixel with); later decisions are re-taken on each branch.  Returns ``(outcomes,
+    unenumerated)``: {flat: [Outcome, ...]} (distinct blended sets, the float64 decisions first) and the pixels with more
+    than ``cap`` outcomes (not enumerated)."""
+    if pixels is None:
+        H, W = out.fragile.shape
+        pixels = np.flatnonzero(out.fragile.reshape(-1)).tolist()
+    res, over = {}, []
+    for f in pixels:
+        got = _walk(out.rows[int(f)], np.asarray(out.bg, dtype=np.float64), out.fragile_tol, cap)
+        if got is None:
+            over.append(int(f))
+        else:
+            res[int(f)] = got
+    return res, over
+
+
+def _walk(row, bg, tol, cap):
+    alpha, power, band, noise = (row.alpha.astype(np.float64).tolist(), row.power.astype(np.float64).tolist(),
+                                 row.band.astype(np.float64).tolist(), row.noise.astype(np.float64).tolist())
+    n = len(alpha)
+    done = {}
+    # state: (next entry, T, band_T so far, blended entries, decisions); depth first, the float64 branch first
+    todo = [(0, 1.0, tol, (), ())]
+    while todo:
+        i, T, bT, kept, dec = todo.pop()
+        while True:
+            if i == n:
+                done.setdefault(kept, dec)
+                break
+            p, a = power[i], alpha[i]
+            branches = []                          # (blend?, decisions) of entry i
+            if on_power_edge(p):                   # skip the entry, or clamp its exponent to 0 and go on
+                alts = [(True, dec + (("power", "blend"),)), (False, dec + (("power", "skip"),))]
+                if p > 0:
+                    alts.reverse()
+            else:
+                alts = [(p <= 0, dec)]
+            for consider, d in alts:
+                if not consider:
+                    branches.append((False, d))
+                elif on_alpha_edge(a, band[i]):
+                    live_first = a >= ALPHA_MIN
+                    pair = [(True, d + (("alpha", "live"),)), (False, d + (("alpha", "skip"),))]
+                    branches += pair if live_first else pair[::-1]
+                else:
+                    branches.append((a >= ALPHA_MIN, d))
+            nxt = []
+            for live, d in branches:
+                if not live:
+                    nxt.append((i + 1, T, bT, kept, d))
+                    continue
+                Tn = T * (1.0 - a)
+                bTn = bT + noise[i]
+                stop = Tn < T_EPS
+                if on_t_edge(Tn, bTn):
+                    sides = [(True, d + (("T", "stop"),)), (False, d + (("T", "continue"),))]
+                    if not stop:
+                        sides.reverse()
+                else:
+                    sides = [(stop, d)]
+                for st, dd in sides:
+                    if st:
+                        nxt.append((n, T, bT, kept, dd))      # ends the pixel without blending entry i
+                    else:
+                        nxt.append((i + 1, Tn, bTn, kept + (i,), dd))
+            if len(done) + len(todo) + len(nxt) > cap:
+                return None
+            i, T, bT, kept, dec = nxt[0]
+            todo.extend(reversed(nxt[1:]))
+    outs = []
+    for kept, dec in done.items():
+        T, c, dsum = 1.0, np.zeros(3), 0.0
+        for i in kept:
+            a = alpha[i]
+            c = c + row.rgb[i].astype(np.float64) * (a * T)
+            dsum += float(row.invz[i]) * a * T
+            T = T * (1.0 - a)
+        keep = np.zeros(n, dtype=bool)
+        keep[list(kept)] = True
+        outs.append(Outcome(color=c + T * bg, invdepth=dsum, final_T=T, n_contrib=(kept[-1] + 1) if kept else 0,
+                            keep=keep, decisions=dec))
+    return outs
 
 
 def rasterize(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
               *, image_height, image_width, tanfovx, tanfovy, bg, scale_modifier, viewmatrix,
               projmatrix, sh_degree, campos, interpolation_weights=None, num_node_kids=None,
               dtype=torch.float64, tiles=None, fragile_tol=1e-5, geom_dtype=None, lod_mode="opacity",
-              positive_power="skip") -> OracleOut:
+              positive_power="skip", keep_override=None, capture=(), return_keep=False) -> OracleOut:
     """Dense per-tile oracle.  All tensor arguments are CPU torch tensors; the
     differentiable ones may require grad.  ``tiles``: optional iterable of tile
     ids to restrict the blend to (bench cpu_baseline sampling); other pixels
@@ -346,7 +497,11 @@ def rasterize(means3D, means2D, shs, colors_precomp, opacities, scales, rotation
     continuous stage (projection, conic, colour); the blend runs in ``dtype`` on tile-relative
     coordinates -- ``dtype=float32, geom_dtype=float64`` mirrors the HIP kernels' precision split.
     ``lod_mode``: "opacity" = ``lod_opacity`` per Gaussian (what the kernels do); "alpha" = ``lod_alpha`` per pixel
-    (oracle-only alternative, see ``lod_opacity``)."""
+    (oracle-only alternative, see ``lod_opacity``).
+    ``keep_override``: {flat pixel index: bool row over the pixel's tile list} -- replaces the (no-grad) set of entries
+    those pixels blend before the differentiable blend, so the outputs and autograd are those of the forced outcome
+    (``Outcome.keep``); the ``fragile`` flags keep describing the float64 decisions.  ``capture``: flat pixels whose
+    ``PixelRow`` is kept besides the fragile ones.  ``return_keep``: keep every tile's blended sets in ``out.keep``."""
     if lod_mode not in ("opacity", "alpha"):
         raise ValueError(f"lod_mode {lod_mode!r}")
     H, W = int(image_height), int(image_width)
@@ -441,6 +596,13 @@ def rasterize(means3D, means2D, shs, colors_precomp, opacities, scales, rotation
     n_contrib = np.zeros((H, W), dtype=np.int32)
     final_T = np.ones((H, W), dtype=np.float64)
     tile_iter = range(gx * gy) if tiles is None else tiles
+    forced = {}
+    for f, row in (keep_override or {}).items():
+        y, x = divmod(int(f), W)
+        forced.setdefault((y // TILE) * gx + x // TILE, []).append(((y % TILE) * min(TILE, W - (x // TILE) * TILE)
+                                                                    + x % TILE, row))
+    capture = set(int(f) for f in capture)
+    rows, keeps = {}, {}
     col_tiles, dep_tiles, coords = [], [], []
     for t in tile_iter:
         s, e = binning.ranges[t]
@@ -473,24 +635,32 @@ def rasterize(means3D, means2D, shs, colors_precomp, opacities, scales, rotation
                 stop = live & (T_incl < T_EPS)
                 dead = torch.cumsum(stop.to(torch.int32), dim=1) > 0
                 keep = live & ~dead
-                # The band around a threshold inside which a float32 evaluation may decide differently GROWS WITH THE
-                # FOOTPRINT: the exponent is a sum of three products that cancel (|A dx^2|, |C dy^2|, |B dx dy| reach
-                # thousands for a Gaussian hundreds of pixels wide while their sum stays at -5.5), so alpha carries a
-                # relative error of about 2^-24 per unit of M = the sum of their magnitudes, times the handful of
-                # roundings in the chain (FRAGILE_FP32_K); a fixed 1e-5 band missed flips at 1/255 on the trained 1080p
-                # scene of round 5 (3 of 49 128 values, profiles/r05_config2_config3_scripts.log).  The transmittance
-                # inherits the error of every alpha blended before it.
+                # the band around each threshold inside which a float32 evaluation may decide differently grows with
+                # the footprint (``alpha_band``); the transmittance inherits the error of every alpha blended before it
                 M = 0.5 * (A[ids][None].abs() * dx * dx + C[ids][None].abs() * dy * dy) + (B[ids][None] * dx * dy).abs()
-                band = fragile_tol + FRAGILE_FP32_K * M
-                frag = ((alpha - ALPHA_MIN).abs() < band * ALPHA_MIN) & (power <= 0) & ~dead
-                frag |= (power.abs() < 1e-12) & ~dead
-                # (an alpha AT the 0.99 cap is a constant: it carries no rounding error into 1 - alpha)
-                noise = torch.where(araw < ALPHA_MAX, a_eff / (1.0 - a_eff).clamp_min(1e-2) * (FRAGILE_FP32_K * M),
-                                    torch.zeros_like(M))
-                band_T = fragile_tol + torch.cumsum(noise, dim=1)
-                frag |= ((T_incl - T_EPS).abs() < band_T * T_EPS) & live & \
-                        (torch.cumsum(stop.to(torch.int32), dim=1) <= 1)
+                band = alpha_band(M, fragile_tol)
+                frag = on_alpha_edge(alpha, band) & (power <= 0) & ~dead
+                frag |= on_power_edge(power) & ~dead
+                noise_row = t_noise(alpha.detach(), araw, M)
+                band_T = fragile_tol + torch.cumsum(torch.where(live, noise_row, torch.zeros_like(M)), dim=1)
+                frag |= on_t_edge(T_incl, band_T) & live & (torch.cumsum(stop.to(torch.int32), dim=1) <= 1)
                 fr = frag.any(dim=1)
+                flat = (yy.reshape(-1) * W + xx.reshape(-1)).numpy()
+                want = fr.numpy() | np.isin(flat, list(capture)) if capture else fr.numpy()
+                if want.any():
+                    pid = binning.point_list[s:e]
+                    rgb_t, invz_t = rgb[ids].detach().numpy(), invz[ids].detach().numpy()
+                    for r in np.flatnonzero(want):
+                        rows[int(flat[r])] = PixelRow(ids=pid, alpha=alpha[r].detach().numpy(),
+                                                      power=power[r].detach().numpy(), band=band[r].numpy(),
+                                                      noise=noise_row[r].numpy(), rgb=rgb_t, invz=invz_t)
+                for r, row in forced.get(t, ()):
+                    row = torch.as_tensor(np.asarray(row, dtype=bool))
+                    if row.shape != (e - s,):
+                        raise ValueError(f"keep_override: tile {t} lists {e - s} entries, the row has {row.shape}")
+                    keep[r] = row
+                if return_keep:
+                    keeps[t] = keep.numpy().copy()
                 idx = torch.arange(1, e - s + 1)[None, :].expand_as(keep)
                 nc = torch.where(keep, idx, torch.zeros_like(idx)).max(dim=1).values
             a_fin = torch.where(keep, alpha, torch.zeros_like(alpha))
@@ -514,7 +684,8 @@ def rasterize(means3D, means2D, shs, colors_precomp, opacities, scales, rotation
         color = color.reshape(3, H * W).index_copy(1, flat, torch.cat(col_tiles, 1)).reshape(3, H, W)
         invd = invd.reshape(1, H * W).index_copy(1, flat, torch.cat(dep_tiles)[None, :]).reshape(1, H, W)
     return OracleOut(color=color, radii=torch.from_numpy(geom.radii.copy()), invdepth=invd,
-                     fragile=fragile, geom=geom, binning=binning, n_contrib=n_contrib, final_T=final_T)
+                     fragile=fragile, geom=geom, binning=binning, n_contrib=n_contrib, final_T=final_T, rows=rows,
+                     keep=keeps if return_keep else None, bg=bgc.detach().numpy(), fragile_tol=fragile_tol)
 
 
 def naive_per_pixel_blend(gxp, gyp, conic, opac, rgb, invz, point_list, ranges, W, H, bg):

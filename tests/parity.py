@@ -13,7 +13,16 @@ pixels and gradients'):
     ``T (1 - alpha) < 1e-4`` legitimately disagree on a knife edge -- e.g. two stacked Gaussians capped at alpha = 0.99
     give T = 9.99998e-5 in float32 (stop, as the float32 reference lineage does) and 1.0000000000000002e-4 in float64
     (continue) -- and one such pixel changes a covering Gaussian's gradient by percents (found by fuzz seed 1002).
+    ``run_oracle`` / ``run_hip`` / ``compare`` keep that masking for the callers that want it (``smoke()``).
+
+``verify`` / ``verify_pair`` mask nothing: a fragile pixel is correct when the kernel reproduces ONE of the admissible
+outcomes the oracle enumerates for it (``ro.admissible_outcomes``: every branch of every decision inside its band), and
+the kernel's gradients are compared with the float64 gradients of the FULL loss in which every fragile pixel takes the
+outcome the kernel took (``ro.rasterize(keep_override=...)``).  Pixels, ``n_contrib`` and every gradient are compared
+on every pixel.
 """
+import time
+
 import numpy as np
 import torch
 
@@ -43,23 +52,56 @@ def settings_kwargs(cam, bg, sh_degree, do_depth=True, debug=False, scale_modifi
                 num_node_kids=e_i if num_node_kids is None else num_node_kids.to(device))
 
 
+class OracleRun:
+    """Leaf tensors plus a ``ro.rasterize`` call on them that can be repeated -- with forced decisions
+    (``keep_override``) or on other tiles -- with the gradients of every call accumulating on the same leaves.
+    ``call(leaves, **extra)`` returns an ``OracleOut``; ``grads()`` returns {name: leaf.grad}."""
+
+    def __init__(self, leaves, call):
+        self.leaves, self.call = leaves, call
+
+    def __call__(self, **extra):
+        return self.call(self.leaves, **extra)
+
+    def grads(self):
+        return {k: v.grad for k, v in self.leaves.items() if v is not None}
+
+
+def oracle_run(scene, cam, bg, *, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0,
+               interpolation_weights=None, num_node_kids=None, dtype=torch.float64, geom_dtype=None, lod_mode="opacity",
+               positive_power="skip"):
+    """The ``OracleRun`` of the op's standard entrance on ``scene`` (gradient names as ``run_hip`` returns them)."""
+    req = lambda t: None if t is None else t.clone().requires_grad_(True)
+    lv = dict(means3D=req(scene.means3D), means2D=torch.zeros(scene.P, 3, requires_grad=True),
+              opacities=req(scene.opacities))
+    if colors_precomp is None:
+        lv["shs"] = req(scene.shs)
+    else:
+        lv["colors_precomp"] = req(colors_precomp)
+    if cov3D_precomp is None:
+        lv["scales"], lv["rotations"] = req(scene.scales), req(scene.rotations)
+    else:
+        lv["cov3D_precomp"] = req(cov3D_precomp)
+
+    def call(lv, **extra):
+        return ro.rasterize(lv["means3D"], lv["means2D"], lv.get("shs"), lv.get("colors_precomp"), lv["opacities"],
+                            lv.get("scales"), lv.get("rotations"), lv.get("cov3D_precomp"),
+                            image_height=cam.image_height, image_width=cam.image_width, tanfovx=cam.tanfovx,
+                            tanfovy=cam.tanfovy, bg=bg, scale_modifier=scale_modifier,
+                            viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform,
+                            sh_degree=scene.sh_degree, campos=cam.camera_center,
+                            interpolation_weights=interpolation_weights, num_node_kids=num_node_kids, dtype=dtype,
+                            geom_dtype=geom_dtype, lod_mode=lod_mode, positive_power=positive_power, **extra)
+    return OracleRun(lv, call)
+
+
 def run_oracle(scene, cam, bg, gc, gd, *, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0,
                interpolation_weights=None, num_node_kids=None, do_depth=True, dtype=torch.float64, mask_fragile=True,
                lod_mode="opacity", positive_power="skip"):
-    req = lambda t: None if t is None else t.clone().requires_grad_(True)
-    m3, sc, rot, op = req(scene.means3D), req(scene.scales), req(scene.rotations), req(scene.opacities)
-    sh = req(scene.shs) if colors_precomp is None else None
-    col = req(colors_precomp)
-    cov = req(cov3D_precomp)
-    if cov is not None:
-        sc = rot = None
-    m2 = torch.zeros(scene.P, 3, requires_grad=True)
-    out = ro.rasterize(m3, m2, sh, col, op, sc, rot, cov, image_height=cam.image_height,
-                       image_width=cam.image_width, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, bg=bg,
-                       scale_modifier=scale_modifier, viewmatrix=cam.world_view_transform,
-                       projmatrix=cam.full_proj_transform, sh_degree=scene.sh_degree, campos=cam.camera_center,
-                       interpolation_weights=interpolation_weights, num_node_kids=num_node_kids, dtype=dtype,
-                       lod_mode=lod_mode, positive_power=positive_power)
+    orc = oracle_run(scene, cam, bg, colors_precomp=colors_precomp, cov3D_precomp=cov3D_precomp,
+                     scale_modifier=scale_modifier, interpolation_weights=interpolation_weights,
+                     num_node_kids=num_node_kids, dtype=dtype, lod_mode=lod_mode, positive_power=positive_power)
+    out = orc()
     # see the module docstring: undecidable pixels leave the loss
     ok = torch.from_numpy(~out.fragile) if mask_fragile else torch.ones(out.fragile.shape, dtype=torch.bool)
     out.grad_mask = ok
@@ -70,12 +112,7 @@ def run_oracle(scene, cam, bg, gc, gd, *, colors_precomp=None, cov3D_precomp=Non
     if do_depth:
         loss = loss + (out.invdepth * (gd * ok).to(dtype)).sum()
     loss.backward()
-    grads = dict(means3D=m3.grad, means2D=m2.grad, opacities=op.grad)
-    if sh is not None: grads["shs"] = sh.grad
-    if col is not None: grads["colors_precomp"] = col.grad
-    if sc is not None: grads["scales"] = sc.grad; grads["rotations"] = rot.grad
-    if cov is not None: grads["cov3D_precomp"] = cov.grad
-    return out, grads
+    return out, orc.grads()
 
 
 def run_hip(scene, cam, bg, gc, gd, device, *, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0,
@@ -204,6 +241,147 @@ def compare(hip, oracle_out, oracle_grads, do_depth=True):
     for k, g in oracle_grads.items():
         stats["d_" + k] = err_stats(hip["grads"][k], g)
     return stats
+
+
+def _within(h, o, scale, mixed_tol):
+    """The element-wise bound of ``err_stats`` / ``assert_stats`` on one entry (``scale``: max|oracle| of the image)."""
+    return bool(np.all(np.abs(h - o) <= mixed_tol * (MIXED_REL * np.abs(o) + MIXED_ABS * scale)))
+
+
+def match_fragile(hip, oracle_out, *, do_depth=True, mixed_tol=1.0, cap=ro.OUTCOME_CAP):
+    """Which admissible outcome (``ro.admissible_outcomes``) the kernel took at every fragile pixel of ``oracle_out``:
+    the one whose ``n_contrib`` equals the kernel's exactly and whose final T, colour and inverse depth agree with the
+    kernel's within the element-wise bound (maxima over the whole oracle image).  Several that agree: the closest one,
+    counted as ambiguous.  Returns {"override": {flat: keep row} for every matched pixel, "outcome": {flat: Outcome},
+    "stats": {fragile, fragile_matched, fragile_unmatched, fragile_ambiguous, fragile_unenumerated, forced (matched
+    pixels whose outcome is not the float64 decisions), sides: [("alpha_live", pixels), ...]}, "forced": those pixels}."""
+    outs, over = ro.admissible_outcomes(oracle_out, cap=cap)
+    H, W = oracle_out.fragile.shape
+    nc = hip["views"]["n_contrib"].numpy().reshape(-1)
+    fT = hip["views"]["final_T"].numpy().reshape(-1).astype(np.float64)
+    col = hip["color"].double().numpy().reshape(3, -1)
+    dep = hip["invdepth"].double().numpy().reshape(-1)
+    sc_c = float(oracle_out.color.detach().abs().max())
+    sc_d = float(oracle_out.invdepth.detach().abs().max())
+    sc_t = float(np.abs(oracle_out.final_T).max())
+    override, chosen, sides, forced = {}, {}, {}, set()
+    st = dict(fragile=int(oracle_out.fragile.sum()), fragile_matched=0, fragile_unmatched=0, fragile_ambiguous=0,
+              fragile_unenumerated=len(over), forced=0)
+    for f, cands in outs.items():
+        ok = []
+        for o in cands:
+            if o.n_contrib != nc[f] or not _within(fT[f], o.final_T, sc_t, mixed_tol) or \
+                    not _within(col[:, f], o.color, sc_c, mixed_tol) or \
+                    (do_depth and not _within(dep[f], o.invdepth, sc_d, mixed_tol)):
+                continue
+            ok.append((float(np.abs(col[:, f] - o.color).max()) + abs(fT[f] - o.final_T), len(ok), o))
+        if not ok:
+            st["fragile_unmatched"] += 1
+            continue
+        st["fragile_matched"] += 1
+        st["fragile_ambiguous"] += len(ok) > 1
+        o = min(ok)[2]
+        override[f], chosen[f] = o.keep, o
+        if o is not cands[0]:          # (cands[0]: the float64 decisions)
+            forced.add(f)
+        for kind, side in o.decisions:
+            sides[kind + "_" + side] = sides.get(kind + "_" + side, 0) + 1
+    st["forced"] = len(forced)
+    st["sides"] = sorted(sides.items())        # (a list, not a dict: ``assert_stats`` walks the dicts of a stats dict)
+    return dict(override=override, outcome=chosen, forced=forced, stats=st)
+
+
+def tile_pixels(t, W, H):
+    """Flat indices of tile ``t``'s pixels in the order ``ro.rasterize`` lays them out (row-major inside the tile)."""
+    gx = (W + ro.TILE - 1) // ro.TILE
+    y0, x0 = (t // gx) * ro.TILE, (t % gx) * ro.TILE
+    ys, xs = np.arange(y0, min(y0 + ro.TILE, H)), np.arange(x0, min(x0 + ro.TILE, W))
+    return (ys[:, None] * W + xs[None, :]).reshape(-1).tolist()
+
+
+def _tile_of(f, W):
+    y, x = divmod(int(f), W)
+    return (y // ro.TILE) * ((W + ro.TILE - 1) // ro.TILE) + x // ro.TILE
+
+
+def verify(hip, orc, gc, gd, *, do_depth=True, mixed_tol=1.0, tiles=None, pixels=None, return_keep=False):
+    """The whole check of one kernel run against the oracle, nothing masked:
+      1. ``hip``: the kernel run with the UNMASKED upstream gradients ``gc`` / ``gd``;
+      2. the oracle forward (``orc``: an ``OracleRun``; ``tiles``: restrict it to those tiles);
+      3. ``match_fragile``;
+      4. the oracle gradients of the full loss with every fragile pixel forced to the kernel's outcome -- the loss is a
+         sum over pixels, so a second pass restricted to the tiles of the pixels whose outcome is not the float64 one
+         supplies their terms;
+      5. pixels, ``n_contrib`` and every gradient compared on every pixel (``pixels``: [H,W] bool, the compared ones).
+    Returns {"stats": (``compare``'s keys plus the ``match_fragile`` counts and ``n_contrib_mismatch``), "oracle": the
+    first pass, "grads": the oracle gradients, "match": ``match_fragile``'s result, "color" / "invdepth" / "n_contrib":
+    the reference images with the kernel's outcomes in place}."""
+    oo = orc(tiles=tiles, return_keep=return_keep)
+    m = match_fragile(hip, oo, do_depth=do_depth, mixed_tol=mixed_tol)
+    H, W = oo.fragile.shape
+    dt = oo.color.dtype
+    forced = {f: m["override"][f] for f in m["forced"]}
+    fm = torch.zeros(H, W, dtype=torch.bool)
+    fm.view(-1)[torch.tensor(sorted(forced), dtype=torch.long)] = True
+    color, invd, nc = oo.color.detach().clone(), oo.invdepth.detach().clone(), oo.n_contrib.copy()
+    loss = (oo.color * (gc * ~fm).to(dt)).sum()
+    if do_depth:
+        loss = loss + (oo.invdepth * (gd * ~fm).to(dt)).sum()
+    t_forced = 0.0
+    if forced:
+        t0 = time.time()
+        o2 = orc(tiles=sorted({_tile_of(f, W) for f in forced}), keep_override=forced)
+        t_forced = time.time() - t0
+        loss = loss + (o2.color * (gc * fm).to(dt)).sum()
+        if do_depth:
+            loss = loss + (o2.invdepth * (gd * fm).to(dt)).sum()
+        color[:, fm], invd[:, fm] = o2.color.detach()[:, fm], o2.invdepth.detach()[:, fm]
+        nc[fm.numpy()] = o2.n_contrib[fm.numpy()]
+    loss.backward()
+    og = orc.grads()
+    sel = torch.ones(H, W, dtype=torch.bool) if pixels is None else pixels
+    stats = {"fragile_frac": float(oo.fragile[sel.numpy()].mean()), "rows_touching_fragile": rows_touching_fragile(oo),
+             **m["stats"], "oracle_forced_pass_s": t_forced}
+    stats["n_contrib_mismatch"] = int((hip["views"]["n_contrib"].numpy()[sel.numpy()] != nc[sel.numpy()]).sum())
+    stats["color"] = err_stats(hip["color"][:, sel], color[:, sel])
+    if do_depth:
+        stats["invdepth"] = err_stats(hip["invdepth"][:, sel], invd[:, sel])
+    for k, g in og.items():
+        if k in hip["grads"]:
+            stats["d_" + k] = err_stats(hip["grads"][k], g)
+    return dict(stats=stats, oracle=oo, grads=og, match=m, color=color, invdepth=invd, n_contrib=nc)
+
+
+def verify_pair(scene, cam, bg, gc, gd, device, *, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0,
+                interpolation_weights=None, num_node_kids=None, do_depth=True, debug=True, lod_mode="opacity",
+                mixed_tol=1.0):
+    """``verify`` of the op's standard entrance: ``run_hip`` (unmasked) against ``oracle_run`` on the same inputs.
+    Returns ``verify``'s result plus "hip" and "indices" (``check_indices``)."""
+    kw = dict(colors_precomp=colors_precomp, cov3D_precomp=cov3D_precomp, scale_modifier=scale_modifier)
+    hip = run_hip(scene, cam, bg, gc, gd, device, interpolation_weights=interpolation_weights,
+                  num_node_kids=num_node_kids, do_depth=do_depth, debug=debug, grad_mask=None, **kw)
+    orc = oracle_run(scene, cam, bg, interpolation_weights=None if interpolation_weights is None else
+                     interpolation_weights.cpu(), num_node_kids=None if num_node_kids is None else num_node_kids.cpu(),
+                     lod_mode=lod_mode, **kw)
+    res = verify(hip, orc, gc, gd, do_depth=do_depth, mixed_tol=mixed_tol)
+    res["hip"] = hip
+    res["indices"] = check_indices(hip, res["oracle"])
+    return res
+
+
+def assert_verified(name, res, mixed_tol=1.0, fragile_frac=FRAGILE_FRAC):
+    """Everything ``verify`` found within its bounds: integers bit-exact (when checked), every fragile pixel matched,
+    ``n_contrib`` exact on every pixel, pixels and gradients under ``assert_stats``; the share of fragile pixels (a
+    statistic) under ``fragile_frac``."""
+    st = res["stats"]
+    if "indices" in res:
+        assert all(v == 0 for v in res["indices"].values()), f"{name}: integer mismatch {res['indices']}"
+    assert st["fragile_unenumerated"] == 0, f"{name}: {st['fragile_unenumerated']} pixels over the outcome cap"
+    assert st["fragile_unmatched"] == 0, f"{name}: {st['fragile_unmatched']} of {st['fragile']} knife-edge pixels " \
+        f"match no admissible outcome"
+    assert st["n_contrib_mismatch"] == 0, f"{name}: n_contrib differs on {st['n_contrib_mismatch']} pixels"
+    assert st["fragile_frac"] <= fragile_frac, f"{name}: fragile share {st['fragile_frac']:.2e}"
+    assert_stats(name, st, mixed_tol=mixed_tol)
 
 
 def default_case(P, W, H, seed=0, sh_degree=3, fovy=60.0):

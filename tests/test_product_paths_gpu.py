@@ -92,11 +92,10 @@ def test_capacity_miss_retry_matches_oracle(gpu, monkeypatch):
     bg = torch.tensor([0.1, 0.2, 0.3])
     C._last_L.clear()
     pa.run_hip(scene, cam, bg, gc, gd, gpu, scale_modifier=0.3, debug=False, grad_mask=None)
-    oo, og = pa.run_oracle(scene, cam, bg, gc, gd, scale_modifier=1.5)     # (before its run_hip: fragile-pixel pairing)
     misses0 = C.stats["capacity_misses"]
-    hip = pa.run_hip(scene, cam, bg, gc, gd, gpu, scale_modifier=1.5, debug=False)
+    res = pa.verify_pair(scene, cam, bg, gc, gd, gpu, scale_modifier=1.5, debug=False)
     assert C.stats["capacity_misses"] == misses0 + 1
-    _assert_case("capacity_retry", hip, oo, og)
+    _assert_case("capacity_retry", res)
 
 
 def test_capacity_miss_on_the_lod_shape_key(gpu, monkeypatch):
@@ -159,9 +158,8 @@ def test_short_sh_blocks_with_debug(gpu, deg_stored, deg_active):
     assert scene.shs.shape[1] == (deg_stored + 1) ** 2
     scene.sh_degree = deg_active
     bg = torch.tensor([0.3, 0.0, 0.6])
-    oo, og = pa.run_oracle(scene, cam, bg, gc, gd)
-    hip = pa.run_hip(scene, cam, bg, gc, gd, gpu, debug=True)
-    _assert_case(f"sh_M{scene.shs.shape[1]}_deg{deg_active}_debug", hip, oo, og)
+    res = pa.verify_pair(scene, cam, bg, gc, gd, gpu, debug=True)
+    _assert_case(f"sh_M{scene.shs.shape[1]}_deg{deg_active}_debug", res)
 
 
 def test_render_coarse_call_shape(gpu):
@@ -179,9 +177,9 @@ def test_render_coarse_call_shape(gpu):
                         cat(sky.opacities, body.opacities), cat(sky.shs, body.shs), 1)
     gc, gd = synth.upstream_grads(H, W, seed=52)
     bg = torch.rand(3, generator=torch.Generator().manual_seed(53))
-    oo, og = pa.run_oracle(scene, cam, bg, gc, gd, do_depth=False)
-    hip = pa.run_hip(scene, cam, bg, gc, gd, gpu, do_depth=False, debug=True)
-    _assert_case("render_coarse_shape", hip, oo, og, do_depth=False)
+    res = pa.verify_pair(scene, cam, bg, gc, gd, gpu, do_depth=False, debug=True)
+    hip = res["hip"]
+    _assert_case("render_coarse_shape", res)
     # the reference builds the settings WITHOUT do_depth (:319-337): the field must default to False and the third
     # output must still be a [1,H,W] tensor
     kw = pa.settings_kwargs(cam, bg, 1, debug=True, device=gpu)
@@ -278,14 +276,13 @@ def test_culled_workgroups_and_active_degrees_on_the_half_row_route(gpu):
         scene.means3D[:, :2] *= spread
         gc, gd = synth.upstream_grads(96, 160, seed=3)
         bg = torch.tensor([0.2, 0.1, 0.3])
-        oo, og = pa.run_oracle(scene, cam, bg, gc, gd)
-        hip = pa.run_hip(scene, cam, bg, gc, gd, gpu)
-        idx = pa.check_indices(hip, oo)
+        res = pa.verify_pair(scene, cam, bg, gc, gd, gpu)
+        idx = res["indices"]
         assert all(v == 0 for v in idx.values()), (deg, idx)
-        vis = float((oo.geom.radii > 0).mean())
+        vis = float((res["oracle"].geom.radii > 0).mean())
         if spread > 2:
             assert vis < 0.45, vis                              # the fallback is what ran
-        pa.assert_stats(f"half-row route deg={deg} P={P} visible={vis:.2f}", pa.compare(hip, oo, og))
+        pa.assert_verified(f"half-row route deg={deg} P={P} visible={vis:.2f}", res, fragile_frac=1.0)
 
 
 def test_binning_hand_overs_hold_under_load(gpu):

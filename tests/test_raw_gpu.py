@@ -25,19 +25,19 @@ def _raw_from_scene(scene, seed, logit=True):
     )
 
 
-def _run_oracle_raw(raw, cam, bg, gc, gd, sh_degree, act):
+def _oracle_raw(raw, cam, bg, sh_degree, act):
+    """The oracle of the raw entrance: float64 leaves, the activations of ``ro.activate_raw`` in front of the blend."""
     leaves = {k: v.clone().double().requires_grad_(True) for k, v in raw.items()}
-    s, r, o = ro.activate_raw(leaves["scaling"], leaves["rotation"], leaves["opacity"], act)
-    shs = torch.cat([leaves["f_dc"], leaves["f_rest"]], 1)
-    m2 = torch.zeros(raw["xyz"].shape[0], 3, dtype=torch.float64, requires_grad=True)
-    out = ro.rasterize(leaves["xyz"], m2, shs, None, o, s, r, None, image_height=cam.image_height,
-                       image_width=cam.image_width, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, bg=bg,
-                       scale_modifier=1.0, viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform,
-                       sh_degree=sh_degree, campos=cam.camera_center)
-    ((out.color * gc.double()).sum() + (out.invdepth * gd.double()).sum()).backward()
-    grads = {k: v.grad for k, v in leaves.items()}
-    grads["means2D"] = m2.grad
-    return out, grads
+    leaves["means2D"] = torch.zeros(raw["xyz"].shape[0], 3, dtype=torch.float64, requires_grad=True)
+
+    def call(lv, **extra):
+        s, r, o = ro.activate_raw(lv["scaling"], lv["rotation"], lv["opacity"], act)
+        shs = torch.cat([lv["f_dc"], lv["f_rest"]], 1)
+        return ro.rasterize(lv["xyz"], lv["means2D"], shs, None, o, s, r, None, image_height=cam.image_height,
+                            image_width=cam.image_width, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, bg=bg,
+                            scale_modifier=1.0, viewmatrix=cam.world_view_transform,
+                            projmatrix=cam.full_proj_transform, sh_degree=sh_degree, campos=cam.camera_center, **extra)
+    return pa.OracleRun(leaves, call)
 
 
 def _run_hip_raw(raw, cam, bg, gc, gd, sh_degree, act, device, debug=True):
@@ -59,11 +59,13 @@ def _run_hip_raw(raw, cam, bg, gc, gd, sh_degree, act, device, debug=True):
                 grads=grads)
 
 
-def _compare(hip, oo, og):
-    idx = pa.check_indices(hip, oo)
+def _compare(hip, res):
+    idx = pa.check_indices(hip, res["oracle"])
     assert all(v == 0 for v in idx.values()), idx
-    st = pa.compare(hip, oo, og)
+    st = res["stats"]
     assert st["fragile_frac"] <= pa.FRAGILE_FRAC
+    assert st["fragile_unmatched"] == 0 and st["fragile_unenumerated"] == 0, st
+    assert st["n_contrib_mismatch"] == 0, st["n_contrib_mismatch"]
     for k, v in st.items():
         if isinstance(v, dict):
             assert v["maxrel"] <= pa.REL_TOL and v["l2"] <= pa.REL_TOL, (k, v)
@@ -77,9 +79,8 @@ def test_raw_path_matches_oracle(gpu, P, size, deg, act):
     raw = _raw_from_scene(scene, seed=4, logit=(act == "sigmoid"))
     bg = torch.tensor([0.1, 0.2, 0.3])
     gc, gd = synth.upstream_grads(size, size, seed=1)
-    oo, og = _run_oracle_raw(raw, cam, bg, gc, gd, deg, act)
     hip = _run_hip_raw(raw, cam, bg, gc, gd, deg, act, gpu)
-    _compare(hip, oo, og)
+    _compare(hip, pa.verify(hip, _oracle_raw(raw, cam, bg, deg, act), gc, gd))
 
 
 def test_raw_path_equals_standard_path_on_activated_inputs(gpu):

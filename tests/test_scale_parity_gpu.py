@@ -14,13 +14,15 @@ TILE-SAMPLED, and exact in what it covers:
     backward over the WHOLE frame;
   * the oracle runs on the sub-scene of exactly those Gaussians whose instance lists reach a sampled tile (rows in
     their original order, so every sampled tile's sorted list is the same sequence), restricted to the sampled tiles;
-  * pixels of the sampled tiles (fragile ones excluded and counted) and ALL gradient tensors incl. means2D are compared
-    row by row for the sub-scene; every other row of the HIP gradients must be EXACTLY zero.
+  * every pixel of the sampled tiles and ALL gradient tensors incl. means2D are compared row by row for the sub-scene
+    (``pa.verify``: a knife-edge pixel must reproduce one of its admissible outcomes, and the oracle gradients are those
+    of the outcomes the kernels took); every other row of the HIP gradients must be EXACTLY zero.
 The integer side (radii, tile rectangles, depth bits, offsets, sorted (tile | depth) key sequence, point list, tile
 ranges) is compared bit-exactly over the whole frame against the float32 geometry / binning specification.
 """
 import json
 import os
+import time
 
 import numpy as np
 import pytest
@@ -92,31 +94,8 @@ def _run_case(name, gpu, P, W, H, n_tiles, *, lod=False, do_depth=True, seed=0, 
     sub_t = torch.from_numpy(sub.astype(np.int64))
     sub_scene = synth.Scene(scene.means3D[sub_t], scene.scales[sub_t], scene.rotations[sub_t],
                             scene.opacities[sub_t], scene.shs[sub_t], scene.sh_degree)
-    req = lambda t: t.clone().requires_grad_(True)
-    m3, sc, rot, op, sh = map(req, (sub_scene.means3D, sub_scene.scales, sub_scene.rotations, sub_scene.opacities,
-                                    sub_scene.shs))
-    m2 = torch.zeros(sub_scene.P, 3, requires_grad=True)
-    oo = ro.rasterize(m3, m2, sh, None, op, sc, rot, None, image_height=H, image_width=W, tanfovx=cam.tanfovx,
-                      tanfovy=cam.tanfovy, bg=bg, scale_modifier=1.0, viewmatrix=cam.world_view_transform,
-                      projmatrix=cam.full_proj_transform, sh_degree=scene.sh_degree, campos=cam.camera_center,
-                      interpolation_weights=None if w is None else w[sub_t],
-                      num_node_kids=None if kids is None else kids[sub_t], tiles=tiles)
-    # the sub-scene's lists in the sampled tiles are the full frame's lists (same Gaussians, same order)
-    for t in tiles:
-        a = binning.point_list[binning.ranges[t, 0]:binning.ranges[t, 1]]
-        b = sub[oo.binning.point_list[oo.binning.ranges[t, 0]:oo.binning.ranges[t, 1]]]
-        assert np.array_equal(a, b), f"{name}: tile {t}: sub-scene list differs from the frame's"
-    # pixels with a blend decision on a knife edge leave BOTH losses (tests/parity.py does the same for the small scenes;
-    # until round 6 this harness only left them out of the PIXEL comparison: on rows the reference's scripts trained, one
-    # such pixel -- 2e-4 off, flagged -- put 2e-5 on the gradients of the four Gaussians around it)
-    ok_loss = mask & torch.from_numpy(~oo.fragile)
-    gc_m, gd_m = gc * ok_loss, gd * ok_loss
-    loss = (oo.color * gc_m.double()).sum()
-    if do_depth:
-        loss = loss + (oo.invdepth * gd_m.double()).sum()
-    loss.backward(retain_graph=F32_ORACLE)
-    og = {k: (None if v is None else v.clone()) for k, v in
-          dict(means3D=m3.grad, means2D=m2.grad, opacities=op.grad, shs=sh.grad, scales=sc.grad, rotations=rot.grad).items()}
+    lod_kw = dict(interpolation_weights=None if w is None else w[sub_t], num_node_kids=None if kids is None else kids[sub_t])
+    orc = pa.oracle_run(sub_scene, cam, bg, **lod_kw)
 
     # ---- HIP: whole frame, forward + backward ---------------------------------------------------------------------
     hip = pa.run_hip(scene, cam, bg, gc_m, gd_m, gpu, interpolation_weights=w, num_node_kids=kids,
@@ -129,62 +108,54 @@ def _run_case(name, gpu, P, W, H, n_tiles, *, lod=False, do_depth=True, seed=0, 
     idx = pa.check_indices(hip, oo_int)
     assert all(v == 0 for v in idx.values()), f"{name}: integer mismatch over the whole frame {idx}"
 
+    # ---- the oracle on the sampled tiles, every pixel: knife-edge pixels take the outcome the kernels took -----------
+    hip_sub = dict(hip, grads={k: v[sub_t] for k, v in hip["grads"].items()})
+    t0 = time.time()
+    res = pa.verify(hip_sub, orc, gc_m, gd_m, do_depth=do_depth, tiles=tiles, pixels=mask, return_keep=F32_ORACLE)
+    t_oracle = time.time() - t0
+    oo, og, stats = res["oracle"], res["grads"], res["stats"]
+    # the sub-scene's lists in the sampled tiles are the full frame's lists (same Gaussians, same order)
+    for t in tiles:
+        a = binning.point_list[binning.ranges[t, 0]:binning.ranges[t, 1]]
+        b = sub[oo.binning.point_list[oo.binning.ranges[t, 0]:oo.binning.ranges[t, 1]]]
+        assert np.array_equal(a, b), f"{name}: tile {t}: sub-scene list differs from the frame's"
+
     # ---- whose error is it?  The SAME oracle with the kernels' precision split (per-Gaussian stage in float64, blend and
     # its backward in float32) against the float64 oracle: what float32 arithmetic costs on this scene whatever the
-    # implementation.  Fragile pixels leave both losses (their decisions may differ by precision).
+    # implementation.  It is made to take the kernels' decisions on every pixel (the float64 ones,
+    # the kernels' outcome on the knife edges), so that its figures measure arithmetic only.
     f32 = {}
     if F32_ORACLE:
-        okd = torch.from_numpy(~oo.fragile)
-        m3f, scf, rotf, opf, shf = map(req, (sub_scene.means3D, sub_scene.scales, sub_scene.rotations,
-                                             sub_scene.opacities, sub_scene.shs))
-        m2f = torch.zeros(sub_scene.P, 3, requires_grad=True)
-        of = ro.rasterize(m3f, m2f, shf, None, opf, scf, rotf, None, image_height=H, image_width=W, tanfovx=cam.tanfovx,
-                          tanfovy=cam.tanfovy, bg=bg, scale_modifier=1.0, viewmatrix=cam.world_view_transform,
-                          projmatrix=cam.full_proj_transform, sh_degree=scene.sh_degree, campos=cam.camera_center,
-                          interpolation_weights=None if w is None else w[sub_t],
-                          num_node_kids=None if kids is None else kids[sub_t], tiles=tiles, dtype=torch.float32,
-                          geom_dtype=torch.float64)
-        okf = okd & torch.from_numpy(~of.fragile)
-        for nm, a_, b_ in (("color", of.color, oo.color), ("invdepth", of.invdepth, oo.invdepth)):
-            st = pa.err_stats(a_.detach()[:, okf & mask], b_.detach()[:, okf & mask])
+        decide = {}
+        for t, keep in oo.keep.items():
+            for f, row in zip(pa.tile_pixels(t, W, H), keep):
+                decide[f] = row
+        decide.update(res["match"]["override"])
+        orc32 = pa.oracle_run(sub_scene, cam, bg, dtype=torch.float32, geom_dtype=torch.float64, **lod_kw)
+        of = orc32(tiles=tiles, keep_override=decide)
+        for nm, a_, b_ in (("color", of.color, res["color"]), ("invdepth", of.invdepth, res["invdepth"])):
+            st = pa.err_stats(a_.detach()[:, mask], b_.detach()[:, mask])
             f32[nm] = dict(mixed=st["mixed"], p999_rel=st["p999_rel"], maxrel=st["maxrel"], l2=st["l2"])
-        lf = (of.color * (gc_m * okf).to(of.color.dtype)).sum()
+        lf = (of.color * gc_m.to(of.color.dtype)).sum()
         if do_depth:
-            lf = lf + (of.invdepth * (gd_m * okf).to(of.invdepth.dtype)).sum()
+            lf = lf + (of.invdepth * gd_m.to(of.invdepth.dtype)).sum()
         lf.backward()
-        # the float64 gradients of the same (fragile-free) loss
-        for t in (m3, m2, op, sh, sc, rot):
-            t.grad = None
-        l64 = (oo.color * (gc_m * okf).double()).sum()
-        if do_depth:
-            l64 = l64 + (oo.invdepth * (gd_m * okf).double()).sum()
-        l64.backward()
-        ref64 = dict(means3D=m3.grad, means2D=m2.grad, opacities=op.grad, shs=sh.grad, scales=sc.grad, rotations=rot.grad)
-        got32 = dict(means3D=m3f.grad, means2D=m2f.grad, opacities=opf.grad, shs=shf.grad, scales=scf.grad,
-                     rotations=rotf.grad)
-        for k in ref64:
-            st = pa.err_stats(got32[k], ref64[k])
+        got32 = orc32.grads()
+        for k in og:               # against the float64 gradients of the same loss
+            st = pa.err_stats(got32[k], og[k])
             f32["d_" + k] = dict(mixed=st["mixed"], p999_rel=st["p999_rel"], maxrel=st["maxrel"], l2=st["l2"])
 
     # ---- compare ---------------------------------------------------------------------------------------------------
-    ok = mask & torch.from_numpy(~oo.fragile)
-    stats = {"fragile_frac": float(oo.fragile[mask.numpy()].mean()), "rows_touching_fragile": pa.rows_touching_fragile(oo)}
-    stats["color"] = pa.err_stats(hip["color"][:, ok], oo.color.detach()[:, ok])
-    if do_depth:
-        stats["invdepth"] = pa.err_stats(hip["invdepth"][:, ok], oo.invdepth.detach()[:, ok])
-    nc_h = hip["views"]["n_contrib"][ok].numpy()
-    stats["n_contrib_mismatch"] = int((nc_h != oo.n_contrib[ok.numpy()]).sum())
     outside = torch.ones(P, dtype=torch.bool)
     outside[sub_t] = False
     nonzero_outside = {}
-    for k, g in og.items():
+    for k in og:
         hg = hip["grads"][k]
-        stats["d_" + k] = pa.err_stats(hg[sub_t], g)
         nonzero_outside[k] = int((hg[outside] != 0).reshape(int(outside.sum()), -1).any(dim=1).sum())
     payload = dict(case=name, P=P, W=W, H=H, L=int(binning.num_rendered), tiles=len(tiles),
                    tile_instances_sampled=int(per_tile[tiles].sum()), longest_list=int(per_tile.max()),
                    sub_scene=int(sub.shape[0]), indices=idx, stats=stats, nonzero_rows_outside=nonzero_outside,
-                   float32_oracle_vs_float64=f32)
+                   float32_oracle_vs_float64=f32, oracle_s=t_oracle)
     _log(payload)
     print(json.dumps(payload, default=float))
 
@@ -198,7 +169,7 @@ def _run_case(name, gpu, P, W, H, n_tiles, *, lod=False, do_depth=True, seed=0, 
             **{"in_" + k: getattr(sub_scene, k).numpy() for k in ("means3D", "scales", "rotations", "opacities", "shs")},
             **({} if w is None else {"w": w[sub_t].numpy(), "kids": kids[sub_t].numpy()}),
             **{"hip_d_" + k: hip["grads"][k][sub_t].numpy() for k in og}, **{"ora_d_" + k: v.numpy() for k, v in og.items()},
-            hip_color=hip["color"][:, mask].numpy(), ora_color=oo.color.detach()[:, mask].numpy(),
+            hip_color=hip["color"][:, mask].numpy(), ora_color=res["color"][:, mask].numpy(),
             fragile=oo.fragile[mask.numpy()], mask_idx=np.flatnonzero(mask.numpy().reshape(-1)))
     dump = os.environ.get("HGS_PARITY_DUMP")
     if dump and os.environ.get("HGS_PARITY_DUMP_ON_FAIL", "0") != "1":
@@ -209,6 +180,8 @@ def _run_case(name, gpu, P, W, H, n_tiles, *, lod=False, do_depth=True, seed=0, 
         # (measured 1.8e-3 on the 64 sampled tiles of the synthetic trained-scale frame, 2.6e-3 .. 4.8e-3 on rows the
         # reference's scripts trained: 1 200 .. 1 700 entries on average, footprints of hundreds of pixels)
         assert stats["fragile_frac"] <= max(pa.FRAGILE_FRAC, 4e-6 * payload["tile_instances_sampled"] / len(tiles))
+        assert stats["fragile_unenumerated"] == 0, stats["fragile_unenumerated"]
+        assert stats["fragile_unmatched"] == 0, f"{name}: {stats['fragile_unmatched']} knife-edge pixels match no outcome"
         assert stats["n_contrib_mismatch"] == 0
         assert all(v == 0 for v in nonzero_outside.values()), nonzero_outside
         # Norm-wise 1e-5 and the element-wise bound on everything -- or, per tensor, as good as the float32 ORACLE is against

@@ -156,7 +156,9 @@ def _views(lib, P, L, geom, binb, img, debug):
     out = dict(tiles_touched=at(geom, v.tiles_touched, torch.int32, P), offsets=at(geom, v.offsets, torch.int32, P),
                depths=at(geom, v.depths, torch.float32, P), rects=at(geom, v.rects, torch.int32, 2 * P).view(P, 2),
                point_list=at(binb, v.point_list, torch.int32, L),
-               ranges=at(binb, v.ranges, torch.int32, 2 * T).view(T, 2))
+               ranges=at(binb, v.ranges, torch.int32, 2 * T).view(T, 2),
+               final_T=at(img, v.final_T, torch.float32, H * W).view(H, W),
+               n_contrib=at(img, v.n_contrib, torch.int32, H * W).view(H, W))
     if debug:
         out["tile_ids_sorted"] = at(binb, v.tile_ids_sorted, torch.int32, L)
     else:
@@ -243,23 +245,20 @@ def raster_chain(cam, inp, degree, gc, gd, dev, fill, *, prepare_backward=1, deb
     return res, state
 
 
-def _reference(cam, scene, gc, gd, route, **kw):
+def _reference(cam, scene, route, **kw):
     extra = {}
     if route == "colors":
         extra["colors_precomp"] = _colors(scene)
     elif route == "cov3D":
         extra["cov3D_precomp"] = _cov3d(scene)
-    oo, og = pa.run_oracle(scene, cam, BG, gc, gd, **extra, **kw)
-    pa._PAIRED.clear()
-    return oo, og, oo.grad_mask
+    return pa.oracle_run(scene, cam, BG, **extra, **kw)
 
 
-def _check_against_reference(name, hip, oo, og):
-    idx = pa.check_indices(hip, oo)
-    assert all(v == 0 for v in idx.values()), (name, idx)
-    st = pa.compare(hip, oo, og)
-    assert st["fragile_frac"] <= pa.FRAGILE_FRAC, (name, st["fragile_frac"])
-    pa.assert_stats(name, st)
+def _check_against_reference(name, hip, orc, gc, gd):
+    res = pa.verify(hip, orc, gc, gd)
+    res["indices"] = pa.check_indices(hip, res["oracle"])
+    pa.assert_verified(name, res)
+    return res["oracle"]
 
 
 SIZES = [1, 63, 65, 200, 255, 257, 10_440, 16_769]
@@ -271,28 +270,27 @@ RASTER_CASES = [("h48", P, 1, 0) for P in SIZES] + [("h48", P, 0, 0) for P in (6
 @pytest.mark.parametrize("route,P,pb,debug", RASTER_CASES)
 def test_raster_chain_stays_in_bounds(gpu, route, P, pb, debug):
     cam, scene, gc, gd = _case(P, seed=P % 89)
-    oo, og, mask = _reference(cam, scene, gc, gd, route)
+    orc = _reference(cam, scene, route)
     inp = _inputs(route, scene, gpu)
-    run = lambda fill: raster_chain(cam, inp, scene.sh_degree, gc * mask, gd * mask, gpu, fill, prepare_backward=pb,
+    run = lambda fill: raster_chain(cam, inp, scene.sh_degree, gc, gd, gpu, fill, prepare_backward=pb,
                                     debug=debug)[0]
     hip = _both_fills(run)
-    assert hip["L"] == oo.binning.num_rendered
     if route == "shs_rest":            # the reference differentiates the concatenated [P, 16, 3] coefficients
         hip["grads"]["shs"] = torch.cat([hip["grads"]["shs"], hip["grads"].pop("shs_rest")], 1)
-    _check_against_reference(f"{route} P={P}", hip, oo, og)
+    oo = _check_against_reference(f"{route} P={P}", hip, orc, gc, gd)
+    assert hip["L"] == oo.binning.num_rendered
 
 
 @pytest.mark.parametrize("P", [200, 10_440])
 @pytest.mark.parametrize("mode", ["fused_exact", "fused_miss"])
 def test_single_call_forward_stays_in_bounds(gpu, P, mode):
     cam, scene, gc, gd = _case(P, seed=3)
-    oo, og, mask = _reference(cam, scene, gc, gd, "h48")
+    orc = _reference(cam, scene, "h48")
     inp = _inputs("h48", scene, gpu)
-    L = int(oo.binning.num_rendered)
+    L = int(orc(tiles=[]).binning.num_rendered)              # (geometry and binning only)
     assert L >= 2
-    run = lambda fill: raster_chain(cam, inp, scene.sh_degree, gc * mask, gd * mask, gpu, fill, mode=mode,
-                                    L_hint=L)[0]
-    _check_against_reference(f"{mode} P={P}", _both_fills(run), oo, og)
+    run = lambda fill: raster_chain(cam, inp, scene.sh_degree, gc, gd, gpu, fill, mode=mode, L_hint=L)[0]
+    _check_against_reference(f"{mode} P={P}", _both_fills(run), orc, gc, gd)
 
 
 def _lod_cut(P, seed):
@@ -326,16 +324,13 @@ def test_in_op_lod_chain_stays_in_bounds(gpu):
     assert 64 < n and n % 64 != 0 and bool(((w > 0) & (w < 1)).any()), (n, "the cut must blend and sit off the grid")
     gc, gd = synth.upstream_grads(H, W, seed=11)
     wt, kt = torch.from_numpy(w), torch.from_numpy(ns.astype(np.int32))
-    oo, og = pa.run_oracle(gathered, cam, BG, gc, gd, interpolation_weights=wt, num_node_kids=kt)
-    mask = oo.grad_mask
-    pa._PAIRED.clear()
+    orc = pa.oracle_run(gathered, cam, BG, interpolation_weights=wt, num_node_kids=kt)
     d = lambda t: t.contiguous().to(gpu)
     inp = dict(means3D=d(rows["means3D"]), opacity=d(rows["opacities"]), sh=d(rows["shs"]), colors=None, sh_rest=None,
                scales=d(rows["scales"]), rotations=d(rows["rotations"]), cov3D_precomp=None)
     lod = (d(torch.from_numpy(ri.astype(np.int32))), d(torch.from_numpy(pi.astype(np.int32))), 0)
-    run = lambda fill: raster_chain(cam, inp, 3, gc * mask, gd * mask, gpu, fill, lod=lod, weights=d(wt),
-                                    kids=d(kt))[0]
-    _check_against_reference(f"in-op LOD n={n}", _both_fills(run), oo, og)
+    run = lambda fill: raster_chain(cam, inp, 3, gc, gd, gpu, fill, lod=lod, weights=d(wt), kids=d(kt))[0]
+    _check_against_reference(f"in-op LOD n={n}", _both_fills(run), orc, gc, gd)
 
 
 def _view_cams(n):
@@ -350,12 +345,14 @@ def test_deferred_sh_backward_stays_in_bounds(gpu, P, n_views):
     cams = _view_cams(n_views)
     scene = synth.make_scene(P, cams[0], seed=P % 31)
     gc, gd = synth.upstream_grads(H, W, seed=7)
-    refs = [_reference(c, scene, gc, gd, "h48") for c in cams]
     inp = _inputs("h48", scene, gpu)
     lib = _lib.lib()
+    views = []                       # the views' forward results (for the reference: the outcomes they took)
 
     def run(fill):
-        states = [raster_chain(c, inp, 3, gc * m, gd * m, gpu, fill, defer_sh=True)[1] for c, (_, _, m) in zip(cams, refs)]
+        chains = [raster_chain(c, inp, 3, gc, gd, gpu, fill, defer_sh=True) for c in cams]
+        views[:] = [r for r, _ in chains]
+        states = [st for _, st in chains]
         bufs = Bufs(gpu, fill)
         d_sh = bufs.filled("dL_dshs", torch.float32, (P, 16, 3))                 # written (accumulate = 0)
         d_m3 = bufs.filled("dL_dmeans3D", torch.float32, (P, 3), fill=0x00)      # += target: the views' sum goes in
@@ -372,8 +369,11 @@ def test_deferred_sh_backward_stays_in_bounds(gpu, P, n_views):
         return dict(shs=d_sh.cpu().clone(), means3D=d_m3.cpu().clone())
 
     hip = _both_fills(run)
+    refs = [pa.verify(v, _reference(c, scene, "h48"), gc, gd) for v, c in zip(views, cams)]
+    for r in refs:
+        assert r["stats"]["fragile_unmatched"] == 0 and r["stats"]["fragile_unenumerated"] == 0, r["stats"]
     for k in ("shs", "means3D"):
-        ref = sum(og[k] for _, og, _ in refs)
+        ref = sum(r["grads"][k] for r in refs)
         st = pa.err_stats(hip[k], ref)
         assert st["maxrel"] <= pa.REL_TOL and st["l2"] <= pa.REL_TOL, (k, st)
 
