@@ -608,4 +608,50 @@ int hgs_hier_build(const float* xyz, const float* scales, const float* rots, con
                            out_nodes, out_boxes, tmp, static_cast<hipStream_t>(stream));
 }
 
+constexpr int64_t kHierMergeMaxN = 0x7fffffff;
+
+static int check_merged_view(const hgs_hier_view* merged, int32_t k) {
+  if (k < 1) { set_error("bad sizes: k=%d chunks < 1", k); return HGS_ERR_INVALID; }
+  if (merged->N < 1 + (int64_t)k || merged->N > kHierMergeMaxN) {
+    set_error("bad sizes: merged N=%lld not in [1 + k, 2^31 - 1] (k=%d)", (long long)merged->N, k);
+    return HGS_ERR_INVALID;
+  }
+  if (merged->G != merged->N) { set_error("bad sizes: merged G=%lld != N=%lld", (long long)merged->G, (long long)merged->N); return HGS_ERR_INVALID; }
+  if (merged->M < 1 || merged->M > 64) { set_error("bad sizes: merged M=%d not in [1, 64]", merged->M); return HGS_ERR_INVALID; }
+  return HGS_OK;
+}
+
+static bool null_view(const hgs_hier_view* v) {
+  return !v->xyz || !v->shs || !v->alpha || !v->log_scales || !v->rots || !v->nodes || !v->boxes;
+}
+
+int hgs_hier_merge_place(const hgs_hier_view* chunk, int32_t index, int32_t k, int64_t base, const hgs_hier_view* merged,
+                         void* tmp, hgs_hier_merge_report* report, hgs_stream_t stream, int device) {
+  if (!chunk || !merged || !report) { set_error("null argument"); return HGS_ERR_INVALID; }
+  if (chunk->N < 1 || chunk->N > kHierMergeMaxN) { set_error("bad sizes: chunk N=%lld not in [1, 2^31 - 1]", (long long)chunk->N); return HGS_ERR_INVALID; }
+  if (chunk->G < chunk->N) { set_error("bad sizes: chunk G=%lld < N=%lld", (long long)chunk->G, (long long)chunk->N); return HGS_ERR_INVALID; }
+  int rc = check_merged_view(merged, k);
+  if (rc) return rc;
+  if (chunk->M != merged->M) { set_error("bad sizes: chunk M=%d != merged M=%d", chunk->M, merged->M); return HGS_ERR_INVALID; }
+  if (index < 0 || index >= k) { set_error("bad sizes: chunk index=%d not in [0, k=%d)", index, k); return HGS_ERR_INVALID; }
+  if (base < 1 + (int64_t)k || base > merged->N - chunk->N + 1) {
+    set_error("bad sizes: base=%lld not in [1 + k, merged N - chunk N + 1] = [%lld, %lld]", (long long)base,
+              (long long)(1 + (int64_t)k), (long long)(merged->N - chunk->N + 1));
+    return HGS_ERR_INVALID;
+  }
+  if (null_view(chunk) || null_view(merged) || !tmp) { set_error("null argument"); return HGS_ERR_INVALID; }
+  HGS_HIP(hipSetDevice(device));
+  return launch_hier_merge_place(*chunk, index, base, *merged, tmp, report, static_cast<hipStream_t>(stream));
+}
+
+int hgs_hier_merge_root(const hgs_hier_view* merged, int32_t k, hgs_stream_t stream, int device) {
+  if (!merged) { set_error("null argument"); return HGS_ERR_INVALID; }
+  int rc = check_merged_view(merged, k);
+  if (rc) return rc;
+  if (null_view(merged)) { set_error("null argument"); return HGS_ERR_INVALID; }
+  if (((uintptr_t)merged->rots | (uintptr_t)merged->boxes) & 15u) { set_error("merged rots / boxes must be 16-byte aligned"); return HGS_ERR_INVALID; }
+  HGS_HIP(hipSetDevice(device));
+  return launch_hier_merge_root(*merged, k, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

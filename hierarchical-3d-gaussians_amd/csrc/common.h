@@ -304,5 +304,9 @@ size_t hier_build_tmp_bytes(int32_t P);
 int launch_hier_build(const float* xyz, const float* scales, const float* rots, const float* opacity, const float* shs,
                       int32_t P, int32_t M, float* out_xyz, float* out_shs, float* out_alpha, float* out_log_scales,
                       float* out_rots, int32_t* out_nodes, float* out_boxes, void* tmp, hipStream_t s);
+// consolidation of chunk hierarchies (hier_merge.hip): sizes and offsets checked by the caller
+int launch_hier_merge_place(const hgs_hier_view& chunk, int32_t index, int64_t base, const hgs_hier_view& merged,
+                            void* tmp, hgs_hier_merge_report* report, hipStream_t s);
+int launch_hier_merge_root(const hgs_hier_view& merged, int32_t k, hipStream_t s);
 
 }  // namespace hgs

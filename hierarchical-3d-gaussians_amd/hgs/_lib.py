@@ -56,6 +56,20 @@ class HierHost(C.Structure):
                 ("boxes", C.c_void_p)]
 
 
+class HierView(C.Structure):
+    _fields_ = [("G", C.c_int64), ("N", C.c_int64), ("M", C.c_int32), ("reserved", C.c_int32),
+                ("xyz", C.c_void_p), ("shs", C.c_void_p), ("alpha", C.c_void_p),
+                ("log_scales", C.c_void_p), ("rots", C.c_void_p), ("nodes", C.c_void_p),
+                ("boxes", C.c_void_p)]
+
+
+class HierMergeReport(C.Structure):
+    _fields_ = [("first_bad", C.c_int32 * 3), ("reserved", C.c_int32), ("children_sum", C.c_int64)]
+
+
+HIER_MERGE_TMP_BYTES = 256
+
+
 class ResidRows(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("means3D", "shs", "opacities", "scales", "rotations")]
 
@@ -105,6 +119,9 @@ SIGNATURES = {
     "hgs_hier_build_tmp_bytes": (C.c_size_t, [C.c_int32]),
     "hgs_hier_build": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                  C.c_int]),
+    "hgs_hier_merge_place": (C.c_int, [C.POINTER(HierView), C.c_int32, C.c_int32, C.c_int64, C.POINTER(HierView), _P,
+                                       C.POINTER(HierMergeReport), _P, C.c_int]),
+    "hgs_hier_merge_root": (C.c_int, [C.POINTER(HierView), C.c_int32, _P, C.c_int]),
     "hgs_timing_enable": (C.c_int, [C.c_int]),
     "hgs_timing_stage_count": (C.c_int, []),
     "hgs_timing_stage_name": (C.c_char_p, [C.c_int]),

@@ -4,7 +4,9 @@ The reference builds hierarchies offline with its GaussianHierarchyCreator / Mer
 (scripts/full_train.py:138-139,188-196,242-250 -- C++ sources absent).  This module defines this
 project's own construction rule (``build_hierarchy``, the float64 numpy spec; ``build_hierarchy_gpu``,
 the same rule on the device, behind ``python -m hgs.create_hierarchy``): a balanced binary BVH over
-Morton-sorted leaves, interior nodes holding a moment-matched merge of their children.
+Morton-sorted leaves, interior nodes holding a moment-matched merge of their children.  Chunk hierarchies are joined
+under one root by ``merge_hierarchies`` (the torch spec) and ``merge_hierarchies_gpu`` (the same rule on the device, one
+chunk at a time, behind ``python -m hgs.merge_hierarchies``).
 Layout = DESIGN.md '.hier layout':
 
   one Gaussian per node, Gaussian index == node index (``start`` = node id)
@@ -14,6 +16,9 @@ Children of a node are contiguous (BFS numbering).
 """
 from __future__ import annotations
 
+import os
+import struct
+import time
 from dataclasses import dataclass
 
 import numpy as np
@@ -379,3 +384,174 @@ def merge_hierarchies(chunks) -> Hierarchy:
     boxes[0, 0, 3] = (boxes[0, 1, :3] - boxes[0, 0, :3]).max()
     boxes[0, 1, 3] = 0.0
     return Hierarchy(xyz=xyz, shs=shs, alpha=alpha, log_scales=log_scales, rots=rots, nodes=nodes, boxes=boxes)
+
+
+HIER_MAGIC = b"HGSHIER1"
+HIER_UPSTREAM, HIER_PRIVATE, HIER_UPSTREAM_HALF = 0, 1, 2      # the layouts of include/hgs.h (_lib repeats them)
+
+
+def read_hier_header(path):
+    """-> (G, N, M, layout) of a .hier file from its header and declared sizes, without reading the rows: the three
+    layouts ``hgs_hier_load`` accepts (csrc/hier_io.cpp): HGSHIER1 (private, any M), upstream float and upstream half
+    (int32 P < 0), the upstream ones only if the file size matches the declared sizes exactly, as the loader requires."""
+    size = os.path.getsize(path)
+    with open(path, "rb") as f:
+        head = f.read(24)
+        if head[:8] == HIER_MAGIC:
+            if len(head) < 24:
+                raise ValueError(f"{path}: truncated header")
+            G, N, M, _ = struct.unpack("<4i", head[8:24])
+            if G < 0 or N < 0 or M < 0 or M > 64:
+                raise ValueError(f"{path}: corrupt header")
+            if size < 24 + G * (12 * M + 44) + N * 60:
+                raise ValueError(f"{path}: truncated file (declares G = {G}, N = {N}, M = {M})")
+            return G, N, M, HIER_PRIVATE
+        bad = ValueError(f"{path} is neither an upstream .hier file (declared sizes do not match the file size) "
+                         f"nor an HGSHIER1 file")
+        if len(head) < 4:
+            raise bad
+        P_raw, = struct.unpack("<i", head[:4])
+        half = P_raw < 0
+        G = -P_raw if half else P_raw
+        n_at = 4 + G * (12 + 2 * 56 if half else 236)
+        if n_at + 4 > size:
+            raise bad
+        f.seek(n_at)
+        N, = struct.unpack("<i", f.read(4))
+        if N < 0 or n_at + 4 + N * 60 != size:
+            raise bad
+        return G, N, 16, (HIER_UPSTREAM_HALF if half else HIER_UPSTREAM)
+
+
+class ChunkValidationError(ValueError):
+    """A chunk ``merge_hierarchies_gpu`` rejected: ``chunk`` (its path, or ``chunk <index>``), ``check`` (what failed)
+    and ``node`` (the first offending node of the chunk, None for the children-count sum)."""
+
+    def __init__(self, chunk, check, node, detail=""):
+        at = f"first offending node {node}" if node is not None else detail
+        super().__init__(f"{chunk}: not a valid hierarchy: {check} ({at})")
+        self.chunk, self.check, self.node = chunk, check, node
+
+
+# hgs_hier_merge_report.first_bad, in the order they are reported (a bad children range orphans the children it
+# should claim: the range is named, not the orphans)
+MERGE_CHECKS = ("start != node index or count_leafs + count_merged != 1",
+                "children range outside [1, N)",
+                "parent outside [0, N) or not claiming the node (node 0: parent != -1)")
+MERGE_MAX_NODES = (1 << 31) - 1
+
+
+def merge_layout(node_counts):
+    """-> (bases, N): where chunk c's nodes 1..N_c - 1 start in the merged numbering of ``merge_hierarchies`` (node 0
+    the new root, 1..k the chunk roots, then every chunk's other nodes in order), and the merged node count."""
+    k = len(node_counts)
+    bases, b = [], 1 + k
+    for n in node_counts:
+        bases.append(b)
+        b += int(n) - 1
+    return bases, b
+
+
+def _tensor_sizes(h):
+    G, N = int(h.xyz.shape[0]), int(h.nodes.shape[0])
+    M = int(h.shs.shape[1]) if h.shs.dim() == 3 else int(h.shs.shape[1]) // 3
+    want = {"shs": G * M * 3, "alpha": G, "log_scales": G * 3, "rots": G * 4, "nodes": N * 7, "boxes": N * 8}
+    for name, n in want.items():
+        if getattr(h, name).numel() != n:
+            raise ValueError(f"{name} has {getattr(h, name).numel()} values; {n} expected for G = {G}, N = {N}, M = {M}")
+    return G, N, M
+
+
+def merge_hierarchies_gpu(sources, device=None, stats=None) -> Hierarchy:
+    """``merge_hierarchies`` on the GPU (csrc/hier_merge.hip, hgs_hier_merge_place / hgs_hier_merge_root), applied to
+    chunks trimmed to their first N rows: rows at index >= N (a skybox tail, G > N) are dropped.  ``sources``: chunk
+    ``Hierarchy``s (host or device tensors) or ``.hier`` paths, in merge order.  The merged tensors are allocated once on
+    ``device`` (default: the current GPU); the chunks are placed one at a time, a path loaded, placed and released
+    before the next one (host memory holds one chunk, device memory the merged hierarchy and one chunk's nodes).
+    nodes, boxes and every non-root row equal ``merge_hierarchies`` on the trimmed chunks bit for bit; the root row
+    agrees to float32 rounding.  Each chunk is validated as it is placed: one that fails raises
+    ``ChunkValidationError`` naming it, the check and the first offending node.  ``stats`` (a dict, optional) receives
+    ``read_s`` (host seconds loading paths) and ``merge_ms`` (device events around the placements and the root).  No
+    CPU fallback: raises without libhgs.so or a GPU."""
+    import ctypes as C
+    from . import _lib
+    lib = _lib.lib()
+    if not torch.cuda.is_available():
+        raise RuntimeError("merge_hierarchies_gpu needs a GPU (there is no CPU fallback; merge_hierarchies is the spec)")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    sources = list(sources)
+    k = len(sources)
+    if k < 1:
+        raise ValueError("merge_hierarchies_gpu needs at least one chunk")
+    is_path = [isinstance(s, (str, os.PathLike)) for s in sources]
+    names = [os.fspath(s) if p else f"chunk {c}" for c, (s, p) in enumerate(zip(sources, is_path))]
+    sizes = []
+    for s, p, name in zip(sources, is_path, names):
+        G, N, M = read_hier_header(s)[:3] if p else _tensor_sizes(s)
+        if N < 1 or G < N:
+            raise ValueError(f"{name}: G = {G} rows, N = {N} nodes; 1 <= N <= G expected")
+        sizes.append((G, N, M))
+    Ms = {m for _, _, m in sizes}
+    if len(Ms) != 1:
+        raise ValueError(f"the chunks disagree on the SH coefficients per row: {sorted(Ms)}")
+    M = Ms.pop()
+    bases, N = merge_layout([n for _, n, _ in sizes])
+    if N > MERGE_MAX_NODES:
+        raise ValueError(f"the merged hierarchy would have {N} nodes; at most 2^31 - 1")
+    e = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
+    out = Hierarchy(xyz=e(N, 3), shs=e(N, M, 3), alpha=e(N, 1), log_scales=e(N, 3), rots=e(N, 4),
+                    nodes=e(N, 7, dtype=torch.int32), boxes=e(N, 2, 4))
+    tmp = e(_lib.HIER_MERGE_TMP_BYTES, dtype=torch.uint8)
+    p = lambda t: t.data_ptr()
+
+    def view(G, n, h):
+        return _lib.HierView(G, n, M, 0, p(h.xyz), p(h.shs), p(h.alpha), p(h.log_scales), p(h.rots), p(h.nodes),
+                             p(h.boxes))
+
+    merged = view(N, N, out)
+    events, read_s = [], 0.0
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        for c, (src, path, name) in enumerate(zip(sources, is_path, names)):
+            G, n, _ = sizes[c]
+            if path:
+                from gaussian_hierarchy._C import load_hierarchy
+                t0 = time.perf_counter()
+                h = Hierarchy(*load_hierarchy(name))
+                read_s += time.perf_counter() - t0
+                if _tensor_sizes(h) != sizes[c]:
+                    raise ValueError(f"{name}: the loaded sizes {_tensor_sizes(h)} differ from the header's {sizes[c]}")
+            else:
+                h = src
+
+            def arr(t, dtype=torch.float32):      # host tensors stay put (copied H2D in place); another GPU's move here
+                t = t.detach()
+                if t.is_cuda and t.device != dev:
+                    t = t.to(dev)
+                return t.to(dtype).contiguous()
+            h = Hierarchy(xyz=arr(h.xyz), shs=arr(h.shs), alpha=arr(h.alpha), log_scales=arr(h.log_scales),
+                          rots=arr(h.rots), nodes=h.nodes.detach().to(dev, torch.int32).contiguous(), boxes=arr(h.boxes))
+            rep = _lib.HierMergeReport()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            _lib.check(lib.hgs_hier_merge_place(C.byref(view(G, n, h)), c, k, bases[c], C.byref(merged), p(tmp),
+                                                C.byref(rep), stream, dev.index or 0), f"hgs_hier_merge_place ({name})")
+            ev[1].record()
+            events.append(ev)
+            del h
+            for check, node in zip(MERGE_CHECKS, rep.first_bad):
+                if node >= 0:
+                    raise ChunkValidationError(name, check, int(node))
+            if rep.children_sum != n - 1:
+                raise ChunkValidationError(name, "children counts do not sum to N - 1", None,
+                                           f"they sum to {rep.children_sum}, N = {n}")
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        _lib.check(lib.hgs_hier_merge_root(C.byref(merged), k, stream, dev.index or 0), "hgs_hier_merge_root")
+        ev[1].record()
+        events.append(ev)
+    if stats is not None:
+        events[-1][1].synchronize()
+        stats["read_s"] = read_s
+        stats["merge_ms"] = sum(a.elapsed_time(b) for a, b in events)
+    return out

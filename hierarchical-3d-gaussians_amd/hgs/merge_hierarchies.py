@@ -1,0 +1,116 @@
+"""Hierarchy consolidation: every trained chunk's hierarchy -> one ``merged.hier``.
+
+    python -m hgs.merge_hierarchies <trained chunks dir> <root type> <chunks dir> <output .hier> <chunk name> [...]
+
+The positional form of the reference's consolidation call (scripts/full_train.py:240-250), so only the executable
+changes; the output is what ``render_hierarchy.py`` and the viewer load.  Steps:
+
+  1. per chunk name, read ``<trained chunks dir>/<name>/hierarchy.hier_opt`` (what train_post.py writes), else
+     ``hierarchy.hier`` (said so in the output);
+  2. merge with ``hgs.hierarchy.merge_hierarchies_gpu``: a new root over the chunk roots, every chunk's nodes behind
+     them, rows and boxes unchanged.  Rows behind a chunk's N node rows (the scaffold's skybox, appended by save_hier)
+     are dropped; render_hierarchy.py / train_post.py append the scaffold's skybox again when they load the result;
+  3. write the merged hierarchy (write_hierarchy).
+
+Root type 0 (what full_train.py passes) is the only one.  ``<chunks dir>/<name>/center.txt`` / ``extent.txt`` serve a
+report only: the leaves whose means lie outside their chunk's square (create_hierarchy.select_rows' float32 test),
+having drifted there during post-optimisation.  No pruning or rebalancing.
+
+This project's merge rule, not a restatement of the reference's merger."""
+from __future__ import annotations
+
+import os
+import sys
+import time
+
+import torch
+
+from .create_hierarchy import read_chunk_bounds, select_rows
+
+USAGE = ("usage: python -m hgs.merge_hierarchies <trained chunks dir> <root type> <chunks dir> <output .hier> "
+         "<chunk name> [<chunk name> ...]")
+
+
+def chunk_file(trained_dir, name):
+    """-> (path, fallback): ``hierarchy.hier_opt`` of the chunk, else ``hierarchy.hier`` (fallback True), else None."""
+    d = os.path.join(trained_dir, name)
+    for fname, fallback in (("hierarchy.hier_opt", False), ("hierarchy.hier", True)):
+        if os.path.exists(os.path.join(d, fname)):
+            return os.path.join(d, fname), fallback
+    return None, False
+
+
+def count_drifted(h, node_counts, bounds):
+    """Leaves (count_children == 0) of each chunk whose means lie outside the chunk's square, in the merged hierarchy
+    ``h``; ``bounds[c]`` = (center, extent) or None (not counted)."""
+    from .hierarchy import merge_layout
+    bases, _ = merge_layout(node_counts)
+    total = 0
+    for c, (n, b) in enumerate(zip(node_counts, bounds)):
+        if b is None:
+            continue
+        for lo, hi in ((1 + c, 2 + c), (bases[c], bases[c] + n - 1)):
+            leaf = h.nodes[lo:hi, 6] == 0
+            xyz = h.xyz[lo:hi][leaf].cpu()
+            total += int(xyz.shape[0]) - int(select_rows(xyz, 0, b).numel())
+    return total
+
+
+def run(trained_dir, chunks_dir, out_path, names) -> dict:
+    """Read, merge, write; -> figures of the run."""
+    from gaussian_hierarchy._C import write_hierarchy
+    from .hierarchy import merge_hierarchies_gpu, read_hier_header
+    if not torch.cuda.is_available():
+        raise RuntimeError("hgs.merge_hierarchies merges on the GPU; no GPU is visible")
+    paths = [chunk_file(trained_dir, n)[0] for n in names]
+    headers = [read_hier_header(p) for p in paths]
+    bounds = [read_chunk_bounds(os.path.join(chunks_dir, n)) for n in names]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stats = {}
+    t0 = time.perf_counter()
+    h = merge_hierarchies_gpu(paths, dev, stats)
+    t_merge = time.perf_counter() - t0
+    node_counts = [hd[1] for hd in headers]
+    drifted = count_drifted(h, node_counts, bounds)
+    t1 = time.perf_counter()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    write_hierarchy(out_path, h.xyz, h.shs, h.alpha, h.log_scales, h.rots, h.nodes, h.boxes)
+    return dict(chunks=len(names), nodes=node_counts, merged=h.num_nodes,
+                skybox_dropped=sum(hd[0] - hd[1] for hd in headers), drifted=drifted,
+                bounded=sum(b is not None for b in bounds), merge_ms=stats["merge_ms"], read_s=stats["read_s"],
+                merge_s=t_merge, write_s=time.perf_counter() - t1, path=out_path)
+
+
+def main(argv=None) -> int:
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if len(argv) < 5:
+        print(USAGE, file=sys.stderr)
+        return 2
+    trained_dir, root_type, chunks_dir, out_path, names = argv[0], argv[1], argv[2], argv[3], argv[4:]
+    if root_type != "0":
+        print(f"merge_hierarchies: root type {root_type!r} is not supported (0 only, what full_train.py passes)\n{USAGE}",
+              file=sys.stderr)
+        return 2
+    missing = [n for n in names if chunk_file(trained_dir, n)[0] is None]
+    if missing:
+        print(f"merge_hierarchies: no hierarchy.hier_opt or hierarchy.hier under {trained_dir} for chunk(s) "
+              f"{', '.join(missing)}", file=sys.stderr)
+        return 2
+    for n in names:
+        if chunk_file(trained_dir, n)[1]:
+            print(f"merge_hierarchies: {n}: no hierarchy.hier_opt, merging its hierarchy.hier", flush=True)
+    from .hierarchy import ChunkValidationError
+    try:
+        r = run(trained_dir, chunks_dir, out_path, names)
+    except ChunkValidationError as e:
+        print(f"merge_hierarchies: {e}; nothing written", file=sys.stderr)
+        return 1
+    print(f"merge_hierarchies: {r['chunks']} chunks of {'/'.join(str(n) for n in r['nodes'])} nodes, merged N = "
+          f"{r['merged']} nodes, dropped {r['skybox_dropped']} skybox rows, {r['drifted']} leaves outside their chunk "
+          f"({r['bounded']} chunks with bounds), merge {r['merge_ms']:.2f} ms on the device (read {r['read_s']:.2f} s, "
+          f"write {r['write_s']:.2f} s) -> {r['path']}", flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -415,6 +415,49 @@ int hgs_hier_build(const float* xyz, const float* scales, const float* rots, con
                    float* out_rots, int32_t* out_nodes, float* out_boxes, void* tmp, hgs_stream_t stream, int device);
 
 /* ---------------------------------------------------------------------------
+ * Consolidation of chunk hierarchies on the device: the rule of hgs.hierarchy.merge_hierarchies applied to chunks
+ * trimmed to their first N rows (replaces the upstream GaussianHierarchyMerger call of
+ * scripts/full_train.py:240-250).  For k chunks the merged hierarchy has 1 + k + sum(N_c - 1) nodes, one row per node:
+ * node 0 is a new root whose children are the chunk roots 1..k; chunk c's node 0 lands at 1 + c and its nodes 1..N_c-1
+ * at base_c .. base_c + N_c - 2, with base_0 = 1 + k and base_{c+1} = base_c + N_c - 1.  Depths grow by 1; parent,
+ * start and start_children are remapped; rows and boxes are copied unchanged.  Rows at index >= N of a chunk (G > N:
+ * the skybox tail train_post.py's save_hier appends) are dropped.
+ * hgs_hier_merge_place: copies chunk `index`'s rows and boxes into place (hipMemcpyAsync: the chunk's attribute and box
+ * arrays may be host or device memory), remaps its nodes (chunk->nodes: device memory) into merged->nodes and validates
+ * them in the same pass; then reads the report back (one stream synchronisation per chunk).  A chunk that fails a check
+ * still returns HGS_OK: the caller reads `report`.  tmp: HGS_HIER_MERGE_TMP_BYTES of device memory.
+ * hgs_hier_merge_root: node 0's row (after every chunk is placed): the w = alpha * s0 * s1 * s2 weighted moment match
+ * of rows 1..k in double, axis-aligned covariance, rotation (1,0,0,0), alpha clipped to [0,1], box = union of the chunk
+ * roots' boxes.  Asynchronous on `stream`.
+ * Both check sizes and offsets before any HIP call: chunk 1 <= N <= G, merged N in [1 + k, 2^31 - 1] with merged G == N,
+ * the chunk's M == the merged M in [1, 64], 0 <= index < k, base_c in [1 + k, merged N - N_c + 1]. */
+#define HGS_HIER_MERGE_TMP_BYTES 256
+typedef struct hgs_hier_view {
+  int64_t G;          /* Gaussian rows */
+  int64_t N;          /* nodes */
+  int32_t M;          /* SH coefficients per row */
+  int32_t reserved;
+  float* xyz;         /* [G,3] */
+  float* shs;         /* [G,M,3] */
+  float* alpha;       /* [G] */
+  float* log_scales;  /* [G,3] */
+  float* rots;        /* [G,4] */
+  int32_t* nodes;     /* [N,7] */
+  float* boxes;       /* [N,2,4] */
+} hgs_hier_view;
+typedef struct hgs_hier_merge_report {
+  int32_t first_bad[3]; /* first offending chunk node per check, -1 if none: [0] start != i or count_leafs +
+                         * count_merged != 1; [1] a children range outside [1, N) or a negative children count;
+                         * [2] node 0's parent != -1, or another node's parent outside [0, N) or not claiming it
+                         * (i outside the parent's children range) */
+  int32_t reserved;
+  int64_t children_sum; /* sum of count_children over the chunk: N - 1 for a valid chunk */
+} hgs_hier_merge_report;
+int hgs_hier_merge_place(const hgs_hier_view* chunk, int32_t index, int32_t k, int64_t base, const hgs_hier_view* merged,
+                         void* tmp, hgs_hier_merge_report* report, hgs_stream_t stream, int device);
+int hgs_hier_merge_root(const hgs_hier_view* merged, int32_t k, hgs_stream_t stream, int device);
+
+/* ---------------------------------------------------------------------------
  * Direct (two-shot) SUM all-reduce over peer pointers: the exchange step of per-view data parallelism (SURVEY.md
  * section 8(e); the reference itself is single-GPU: train_single.py:57-59 renders one camera per step, nothing to
  * replace).  One process per GPU; every rank allocates its gradient bucket and a small flag block with hgs_p2p_alloc,
