@@ -654,4 +654,27 @@ int hgs_hier_merge_root(const hgs_hier_view* merged, int32_t k, hgs_stream_t str
   return launch_hier_merge_root(*merged, k, static_cast<hipStream_t>(stream));
 }
 
+size_t hgs_ssim_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W) {
+  if (!ssim_sizes_ok(N, C, H, W)) return 0;
+  return ssim_tmp_bytes(N, C, H, W);
+}
+
+int hgs_ssim_fwd(const float* img1, const float* img2, int32_t N, int32_t C, int32_t H, int32_t W, float* out_image,
+                 float* out_mean, float* maps, void* tmp, hgs_stream_t stream, int device) {
+  if (!ssim_sizes_ok(N, C, H, W)) return HGS_ERR_INVALID;
+  if (!img1 || !img2 || !out_image || !out_mean || !tmp) { set_error("null argument"); return HGS_ERR_INVALID; }
+  if ((uintptr_t)tmp & 7u) { set_error("tmp must be 8-byte aligned"); return HGS_ERR_INVALID; }
+  HGS_HIP(hipSetDevice(device));
+  return launch_ssim_fwd(img1, img2, N, C, H, W, out_image, out_mean, maps, tmp, static_cast<hipStream_t>(stream));
+}
+
+int hgs_ssim_bwd(const float* img1, const float* img2, const float* maps, const float* grad_out, int32_t per_image,
+                 int32_t N, int32_t C, int32_t H, int32_t W, float* grad_img1, hgs_stream_t stream, int device) {
+  if (!ssim_sizes_ok(N, C, H, W)) return HGS_ERR_INVALID;
+  if (!img1 || !img2 || !maps || !grad_out || !grad_img1) { set_error("null argument"); return HGS_ERR_INVALID; }
+  HGS_HIP(hipSetDevice(device));
+  return launch_ssim_bwd(img1, img2, maps, grad_out, per_image, N, C, H, W, grad_img1,
+                         static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -308,5 +308,12 @@ int launch_hier_build(const float* xyz, const float* scales, const float* rots, 
 int launch_hier_merge_place(const hgs_hier_view& chunk, int32_t index, int64_t base, const hgs_hier_view& merged,
                             void* tmp, hgs_hier_merge_report* report, hipStream_t s);
 int launch_hier_merge_root(const hgs_hier_view& merged, int32_t k, hipStream_t s);
+// fused SSIM loss (ssim.hip): ssim_sizes_ok sets the error message; the launches expect sizes it accepted
+bool ssim_sizes_ok(int32_t N, int32_t C, int32_t H, int32_t W);
+size_t ssim_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
+int launch_ssim_fwd(const float* img1, const float* img2, int32_t N, int32_t C, int32_t H, int32_t W,
+                    float* out_image, float* out_mean, float* maps, void* tmp, hipStream_t s);
+int launch_ssim_bwd(const float* img1, const float* img2, const float* maps, const float* grad_out, int32_t per_image,
+                    int32_t N, int32_t C, int32_t H, int32_t W, float* grad_img1, hipStream_t s);
 
 }  // namespace hgs

@@ -122,6 +122,10 @@ SIGNATURES = {
     "hgs_hier_merge_place": (C.c_int, [C.POINTER(HierView), C.c_int32, C.c_int32, C.c_int64, C.POINTER(HierView), _P,
                                        C.POINTER(HierMergeReport), _P, C.c_int]),
     "hgs_hier_merge_root": (C.c_int, [C.POINTER(HierView), C.c_int32, _P, C.c_int]),
+    "hgs_ssim_tmp_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "hgs_ssim_fwd": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int]),
+    "hgs_ssim_bwd": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
+                               C.c_int]),
     "hgs_timing_enable": (C.c_int, [C.c_int]),
     "hgs_timing_stage_count": (C.c_int, []),
     "hgs_timing_stage_name": (C.c_char_p, [C.c_int]),

@@ -458,6 +458,24 @@ int hgs_hier_merge_place(const hgs_hier_view* chunk, int32_t index, int32_t k, i
 int hgs_hier_merge_root(const hgs_hier_view* merged, int32_t k, hgs_stream_t stream, int device);
 
 /* ---------------------------------------------------------------------------
+ * Fused SSIM loss (hgs.loss.ssim): the standard SSIM of the reference's loss -- an 11-tap
+ * Gaussian window (sigma 1.5, normalised to sum 1) applied separably, zero padding, C1 = 0.01^2, C2 = 0.03^2 -- of
+ * img1 against img2, both float32 [N,C,H,W] contiguous on the device, and its gradient with respect to img1.
+ * hgs_ssim_tmp_bytes: host only (no GPU needed); 0 for bad sizes (the reason in hgs_last_error).
+ * hgs_ssim_fwd: out_image [N] = mean SSIM per image, out_mean [1] = mean over every channel and pixel.  maps:
+ * NULL, or [3,N,C,H,W] floats that receive the per-pixel partials the backward needs.  tmp: hgs_ssim_tmp_bytes,
+ * 8-byte aligned.  The sums are added in a fixed order (no atomics): two calls give bit-identical results.
+ * hgs_ssim_bwd: grad_img1 [N,C,H,W] from the forward's maps; grad_out is the upstream gradient on the device, one
+ * value (per_image = 0: of out_mean) or N values (per_image = 1: of out_image).
+ * All three check sizes before any HIP call: N, C, H, W >= 1, N*C*H*W (x 12 bytes of maps) within int64, at most
+ * 2^31 - 1 tiles of 32x16 pixels.  Forward and backward are asynchronous on `stream` (no host synchronisation). */
+size_t hgs_ssim_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
+int hgs_ssim_fwd(const float* img1, const float* img2, int32_t N, int32_t C, int32_t H, int32_t W, float* out_image,
+                 float* out_mean, float* maps, void* tmp, hgs_stream_t stream, int device);
+int hgs_ssim_bwd(const float* img1, const float* img2, const float* maps, const float* grad_out, int32_t per_image,
+                 int32_t N, int32_t C, int32_t H, int32_t W, float* grad_img1, hgs_stream_t stream, int device);
+
+/* ---------------------------------------------------------------------------
  * Direct (two-shot) SUM all-reduce over peer pointers: the exchange step of per-view data parallelism (SURVEY.md
  * section 8(e); the reference itself is single-GPU: train_single.py:57-59 renders one camera per step, nothing to
  * replace).  One process per GPU; every rank allocates its gradient bucket and a small flag block with hgs_p2p_alloc,
