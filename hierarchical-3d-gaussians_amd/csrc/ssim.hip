@@ -30,6 +30,7 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kRowsPerPass = kThreads / kTW;   // 8 output rows per vertical step
 constexpr int kReduceThreads = 1024;
+constexpr int64_t kMaxTiles = (int64_t)UINT32_MAX / kThreads;   // 16 777 215 workgroups of a 1-D grid
 constexpr float kC1 = 0.01f * 0.01f;
 constexpr float kC2 = 0.03f * 0.03f;
 
@@ -130,7 +131,10 @@ __global__ __launch_bounds__(kThreads) void ssim_fwd_kernel(const float* __restr
       e12 += w * hm[4][rr + k][c];
     }
     if (y < H && x < W) {
-      const float sg1 = e11 - mu1 * mu1, sg2 = e22 - mu2 * mu2, sg12 = e12 - mu1 * mu2;
+      // One fused multiply-add each, so that the three (co)variances round alike: with x1 == x2 they are equal and
+      // N2 == D2 exactly.  Written as e - mu * mu, the compiler may round one product (mu1 * mu1 is shared with D1)
+      // and fuse another; in a flat region that difference, relative to C2, put S of identical images 6e-6 from 1.
+      const float sg1 = fmaf(-mu1, mu1, e11), sg2 = fmaf(-mu2, mu2, e22), sg12 = fmaf(-mu1, mu2, e12);
       const float n1 = 2.f * mu1 * mu2 + kC1, n2 = 2.f * sg12 + kC2;
       const float d1 = mu1 * mu1 + mu2 * mu2 + kC1, d2 = sg1 + sg2 + kC2;
       const float inv = 1.f / (d1 * d2);
@@ -271,9 +275,12 @@ bool ssim_sizes_ok(int32_t N, int32_t C, int32_t H, int32_t W) {
     set_error("bad sizes: N=%d C=%d H=%d W=%d: N*C*H*W (x 12 bytes of maps) overflows int64", N, C, H, W);
     return false;
   }
+  // One kThreads-thread workgroup per tile in a 1-D grid: the dispatch packet's grid_size_x counts work-items in 32 bits
+  // (hsa_kernel_dispatch_packet_t), so at most (2^32 - 1) / kThreads = 16 777 215 tiles can be launched.
   const int64_t tiles = (int64_t)((W + (int64_t)kTW - 1) / kTW) * ((H + (int64_t)kTH - 1) / kTH);
-  if (tiles > INT32_MAX || (int64_t)N * C > INT32_MAX / tiles) {
-    set_error("bad sizes: N=%d C=%d H=%d W=%d: more than 2^31 - 1 tiles of %dx%d", N, C, H, W, kTW, kTH);
+  if (tiles > kMaxTiles || (int64_t)N * C > kMaxTiles / tiles) {
+    set_error("bad sizes: N=%d C=%d H=%d W=%d: more than %lld tiles of %dx%d (one %d-thread workgroup per tile; a 1-D "
+              "grid holds at most 2^32 - 1 work-items)", N, C, H, W, (long long)kMaxTiles, kTW, kTH, kThreads);
     return false;
   }
   return true;

@@ -468,7 +468,8 @@ int hgs_hier_merge_root(const hgs_hier_view* merged, int32_t k, hgs_stream_t str
  * hgs_ssim_bwd: grad_img1 [N,C,H,W] from the forward's maps; grad_out is the upstream gradient on the device, one
  * value (per_image = 0: of out_mean) or N values (per_image = 1: of out_image).
  * All three check sizes before any HIP call: N, C, H, W >= 1, N*C*H*W (x 12 bytes of maps) within int64, at most
- * 2^31 - 1 tiles of 32x16 pixels.  Forward and backward are asynchronous on `stream` (no host synchronisation). */
+ * 16 777 215 tiles of 32x16 pixels over all N*C planes (one 256-thread workgroup per tile in a 1-D grid, whose size in
+ * work-items is a 32-bit count).  Forward and backward are asynchronous on `stream` (no host synchronisation). */
 size_t hgs_ssim_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
 int hgs_ssim_fwd(const float* img1, const float* img2, int32_t N, int32_t C, int32_t H, int32_t W, float* out_image,
                  float* out_mean, float* maps, void* tmp, hgs_stream_t stream, int device);

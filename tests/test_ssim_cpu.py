@@ -90,6 +90,28 @@ def test_bad_sizes_are_refused_before_any_hip_call(lib, dims):
     assert b"bad sizes" in lib.hgs_last_error()
 
 
+def test_tile_count_limit_of_a_one_dimensional_grid(lib):
+    """One 256-thread workgroup per 32x16 tile in a 1-D grid whose work-item count is 32 bits: at most
+    (2^32 - 1) // 256 = 16 777 215 tiles.  65536x131072 is 4096 x 4096 = 2^24 tiles, one too many; 65536x131040 is
+    4096 x 4095 tiles, inside the limit."""
+    limit = (2 ** 32 - 1) // 256
+    over, under = (1, 1, 65536, 131072), (1, 1, 65536, 131040)
+    tiles = lambda d: d[0] * d[1] * -(-d[2] // 16) * -(-d[3] // 32)
+    assert tiles(over) == limit + 1 and tiles(under) <= limit
+    assert lib.hgs_ssim_tmp_bytes(*over) == 0
+    assert b"16777215 tiles" in lib.hgs_last_error() and b"2^32 - 1 work-items" in lib.hgs_last_error()
+    p = C.c_void_p(16)      # never dereferenced: the size check comes first
+    assert lib.hgs_ssim_fwd(p, p, *over, p, p, p, p, None, 0) != 0
+    assert b"16777215 tiles" in lib.hgs_last_error()
+    assert lib.hgs_ssim_bwd(p, p, p, p, 1, *over, p, None, 0) != 0
+    assert b"16777215 tiles" in lib.hgs_last_error()
+    n = lib.hgs_ssim_tmp_bytes(*under)
+    assert n >= tiles(under) * 8 and n % 256 == 0
+    # the limit counts the tiles of every (image, channel) plane
+    assert lib.hgs_ssim_tmp_bytes(3, 1, 65536, 131040) == 0 and lib.hgs_ssim_tmp_bytes(1, 3, 65536, 131040) == 0
+    assert lib.hgs_ssim_tmp_bytes(limit, 1, 16, 32) > 0 and lib.hgs_ssim_tmp_bytes(limit + 1, 1, 16, 32) == 0
+
+
 def test_null_pointers_are_refused(lib):
     p = C.c_void_p(256)
     assert lib.hgs_ssim_fwd(None, p, 1, 3, 8, 8, p, p, None, p, None, 0) != 0

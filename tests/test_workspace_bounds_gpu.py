@@ -630,3 +630,109 @@ def test_dist2_knn3_stays_in_bounds(gpu, P):
     k = min(3, P - 1)
     ref = d2.topk(k, dim=1, largest=False).values.sum(1) / 3 if k > 0 else torch.zeros(P, dtype=torch.float64)
     assert torch.allclose(got.double(), ref, rtol=1e-4, atol=1e-6), (P, got[:4], ref[:4])
+
+
+# ================================================================================================================
+# 5. fused SSIM loss
+# ================================================================================================================
+SSIM_SIZES = [(1, 3, 45, 67), (3, 1, 17, 33), (2, 4, 5, 1)]
+
+
+@pytest.mark.parametrize("dims", SSIM_SIZES)
+@pytest.mark.parametrize("per_image", [0, 1])
+def test_ssim_stays_in_bounds(gpu, dims, per_image):
+    """hgs_ssim_fwd with maps, hgs_ssim_fwd with maps = NULL (the same value bits), hgs_ssim_bwd with a non-unit
+    upstream gradient; against the float64 spec within test_ssim_gpu's float32 yardstick rule."""
+    from test_ssim_gpu import errors, pair, yardstick
+    import ssim_spec
+    lib = _lib.lib()
+    N, Ch, Hs, Ws = dims
+    x1, x2 = pair(dims, seed=N * 1000 + Hs)
+    go = torch.tensor([0.7, -1.3, 2.5][:N]) if per_image else torch.tensor([-0.2])
+
+    def run(fill):
+        bufs = Bufs(gpu, fill)
+        i1, i2 = bufs.copy_of("img1", x1), bufs.copy_of("img2", x2)
+        out_image = bufs.filled("out_image", torch.float32, (N,))
+        out_mean = bufs.filled("out_mean", torch.float32, (1,))
+        maps = bufs.filled("maps", torch.float32, (3, N, Ch, Hs, Ws))
+        tmp = bufs.new("tmp", lib.hgs_ssim_tmp_bytes(N, Ch, Hs, Ws))
+        _ok(lib.hgs_ssim_fwd(i1.data_ptr(), i2.data_ptr(), N, Ch, Hs, Ws, out_image.data_ptr(), out_mean.data_ptr(),
+                             maps.data_ptr(), tmp.addr, _stream(), gpu.index or 0), "hgs_ssim_fwd")
+        g = bufs.copy_of("grad_out", go)
+        grad = bufs.filled("grad_img1", torch.float32, (N, Ch, Hs, Ws))
+        _ok(lib.hgs_ssim_bwd(i1.data_ptr(), i2.data_ptr(), maps.data_ptr(), g.data_ptr(), per_image, N, Ch, Hs, Ws,
+                             grad.data_ptr(), _stream(), gpu.index or 0), "hgs_ssim_bwd")
+        out_image0 = bufs.filled("out_image(no maps)", torch.float32, (N,))
+        out_mean0 = bufs.filled("out_mean(no maps)", torch.float32, (1,))
+        tmp0 = bufs.new("tmp(no maps)", lib.hgs_ssim_tmp_bytes(N, Ch, Hs, Ws))
+        _ok(lib.hgs_ssim_fwd(i1.data_ptr(), i2.data_ptr(), N, Ch, Hs, Ws, out_image0.data_ptr(), out_mean0.data_ptr(),
+                             None, tmp0.addr, _stream(), gpu.index or 0), "hgs_ssim_fwd (maps = NULL)")
+        bufs.check()
+        assert torch.equal(x1, i1.cpu()) and torch.equal(x2, i2.cpu()), "an input was modified"
+        return dict(out_image=out_image.cpu().clone(), out_mean=out_mean.cpu().clone(), maps=maps.cpu().clone(),
+                    grad=grad.cpu().clone(), out_image0=out_image0.cpu().clone(), out_mean0=out_mean0.cpu().clone())
+
+    r = _both_fills(run)
+    _assert_same(r["out_image0"], r["out_image"], "out_image with maps = NULL")
+    _assert_same(r["out_mean0"], r["out_mean"], "out_mean with maps = NULL")
+    size_average = not per_image
+    grad_out = go if per_image else go[0]
+    vs, gs = ssim_spec.ssim_and_grad(x1.double(), x2.double(), size_average=size_average, grad_out=grad_out.double())
+    ye = errors(*yardstick(x1, x2, size_average, grad_out), vs, gs)
+    he = errors(r["out_image"] if per_image else r["out_mean"][0], r["grad"], vs, gs)
+    assert he[0] <= max(2e-6, 3 * ye[0]) and he[1] <= 1.5 * ye[1] and he[2] <= 3 * ye[2], (he, ye)
+    other = r["out_mean"][0] if per_image else r["out_image"]          # the output the upstream gradient is not of
+    vo = ssim_spec.ssim(x1.double(), x2.double(), size_average=not size_average)
+    yo = (yardstick(x1, x2, not size_average)[0].double() - vo).abs().max().item()
+    assert (other.double() - vo).abs().max().item() <= max(2e-6, 3 * yo)
+
+
+# ================================================================================================================
+# 6. hierarchy merge
+# ================================================================================================================
+@pytest.mark.parametrize("Ps,tails", [([1], [0]), ([63, 65], [0, 0]), ([1, 257, 4_099], [0, 9, 0])])
+def test_hier_merge_stays_in_bounds(gpu, Ps, tails):
+    """hgs_hier_merge_place per chunk (its rows in guarded copies, a skybox tail G > N on one), then
+    hgs_hier_merge_root: every merged array in its own guarded, 0x00- or 0xFF-filled allocation, so a byte the merger
+    does not write shows as a difference between the fills; against the spec on the trimmed chunks."""
+    from test_hier_merge_gpu import _chunk, _cpu, _trim, _with_tail, compare_to_spec
+    lib = _lib.lib()
+    chunks = [_chunk(P, seed=P % 11 + i, dev=gpu, shift=(3.0 * i, -1.0 * i)) for i, P in enumerate(Ps)]
+    sources = [_cpu(_with_tail(c, t, seed=t) if t else c) for c, t in zip(chunks, tails)]
+    assert any(s.xyz.shape[0] > s.num_nodes for s in sources) == any(tails)
+    k = len(Ps)
+    bases, N = hierarchy.merge_layout([s.num_nodes for s in sources])
+    M = 16
+
+    def hv(G, n, h):
+        return _lib.HierView(G, n, M, 0, *(h[f].data_ptr() for f in ("xyz", "shs", "alpha", "log_scales", "rots",
+                                                                     "nodes", "boxes")))
+
+    def run(fill):
+        bufs = Bufs(gpu, fill)
+        out = dict(xyz=bufs.filled("merged.xyz", torch.float32, (N, 3)),
+                   shs=bufs.filled("merged.shs", torch.float32, (N, M, 3)),
+                   alpha=bufs.filled("merged.alpha", torch.float32, (N, 1)),
+                   log_scales=bufs.filled("merged.log_scales", torch.float32, (N, 3)),
+                   rots=bufs.filled("merged.rots", torch.float32, (N, 4)),
+                   nodes=bufs.filled("merged.nodes", torch.int32, (N, 7)),
+                   boxes=bufs.filled("merged.boxes", torch.float32, (N, 2, 4)))
+        tmp = bufs.new("tmp", _lib.HIER_MERGE_TMP_BYTES)
+        merged = hv(N, N, out)
+        for c, s in enumerate(sources):
+            h = {f: bufs.copy_of(f"chunk{c}.{f}", getattr(s, f)) for f in ("xyz", "shs", "alpha", "log_scales",
+                                                                           "rots", "nodes", "boxes")}
+            rep = _lib.HierMergeReport()
+            _ok(lib.hgs_hier_merge_place(C.byref(hv(s.xyz.shape[0], s.num_nodes, h)), c, k, bases[c],
+                                         C.byref(merged), tmp.addr, C.byref(rep), _stream(), gpu.index or 0),
+                f"hgs_hier_merge_place({c})")
+            assert list(rep.first_bad) == [-1, -1, -1] and rep.children_sum == s.num_nodes - 1
+            for f, t in h.items():
+                assert torch.equal(t.cpu(), getattr(s, f)), f"chunk {c}'s {f} was modified"
+        _ok(lib.hgs_hier_merge_root(C.byref(merged), k, _stream(), gpu.index or 0), "hgs_hier_merge_root")
+        bufs.check()
+        return {f: t.cpu().clone() for f, t in out.items()}
+
+    r = _both_fills(run)
+    compare_to_spec(hierarchy.Hierarchy(**r), hierarchy.merge_hierarchies([_trim(s) for s in sources]))
