@@ -1132,13 +1132,15 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_bwd_kernel(hgs_raster_ar
     const double gb = (2.0 * b2 * c2 * gA - (a2 * c2 + b2 * b2) * gB + 2.0 * a2 * b2 * gC) * di2;
     const double gc = (-b2 * b2 * gA + a2 * b2 * gB - a2 * a2 * gC) * di2;
     const double hb = 0.5 * gb;
-    // dL/dSigma (full symmetric matrix) = T^T G2 T
+    // dL/dSigma (full symmetric matrix) = T^T G2 T; the lower triangle is the upper one mirrored, so that Gs is
+    // symmetric to the bit: evaluated on its own it rounds differently, and that antisymmetric rounding noise reaches
+    // the rotation gradient even where the exact one is zero (an isotropic Gaussian, whose rotation cannot matter)
     double Gs[3][3];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-      for (int j = 0; j < 3; ++j)
-        Gs[i][j] = pd.T0[i] * (ga * pd.T0[j] + hb * pd.T1[j]) + pd.T1[i] * (hb * pd.T0[j] + gc * pd.T1[j]);
+      for (int j = i; j < 3; ++j)
+        Gs[i][j] = Gs[j][i] = pd.T0[i] * (ga * pd.T0[j] + hb * pd.T1[j]) + pd.T1[i] * (hb * pd.T0[j] + gc * pd.T1[j]);
     d_c3[0] = (float)Gs[0][0];
     d_c3[1] = (float)(2.0 * Gs[0][1]);
     d_c3[2] = (float)(2.0 * Gs[0][2]);

@@ -13,7 +13,8 @@ What this launcher adds around the script, and nothing else:
     gaussian_hierarchy, simple_knn) and the plyfile / cv2 / torchvision shims of tests/shims (SURVEY.md App. E.1);
   * the oracle-backed extension layers of tests/harness/cpu_backends.py (TEST ONLY: no GPU here);
   * a torch-function mode that maps ``device="cuda"`` / ``.cuda()`` / ``.to("cuda")`` to the CPU, and no-op stand-ins for
-    the handful of ``torch.cuda.*`` calls the scripts make (Event, max_memory_allocated, empty_cache, set_device).
+    the handful of ``torch.cuda.*`` calls the scripts make (Event, max_memory_allocated, empty_cache, set_device);
+  * HGS_RECORD=<file.npz>: tests/harness/recorder.py records every call across the boundary into that file.
 The reference's files are executed as they are from the checkout HGS_REFERENCE names."""
 import os
 import runpy
@@ -154,6 +155,13 @@ def main():
         return
     from harness import cpu_backends
     cpu_backends.install()
+    if os.environ.get("HGS_RECORD"):
+        # every call across the boundary, written as <HGS_RECORD> (.npz, tests/harness/recorder.py) at exit
+        import atexit
+        import numpy as np
+        from harness import recorder
+        rec = recorder.Recorder().install()
+        atexit.register(lambda: np.savez_compressed(os.environ["HGS_RECORD"], **rec.arrays()))
     torch.cuda.Event = _Event
     torch.cuda.max_memory_allocated = lambda *a, **k: 0
     torch.cuda.empty_cache = lambda: None

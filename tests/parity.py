@@ -369,6 +369,46 @@ def verify_pair(scene, cam, bg, gc, gd, device, *, colors_precomp=None, cov3D_pr
     return res
 
 
+def run_call(settings, args, gc, gd, context=None):
+    """The op on one recorded call (tests/boundary_fixtures.py): ``settings`` = GaussianRasterizationSettings keywords,
+    ``args`` = the eight call arguments, both already on their devices (the non-empty float tensors become fresh
+    leaves); the upstream gradients ``gc`` / ``gd`` (``gd`` None: no depth term) are backpropagated, nothing masked.
+    Returns ``run_hip``'s dict."""
+    import diff_gaussian_rasterization as dgr
+    leaf = lambda t: t.detach().clone().requires_grad_(True) if torch.is_tensor(t) and t.numel() and \
+        t.is_floating_point() else t
+    lv = {k: leaf(v) for k, v in args.items()}
+    color, radii, invd = dgr.GaussianRasterizer(dgr.GaussianRasterizationSettings(**settings), context=context)(**lv)
+    call = color.grad_fn.call
+    views = {k: v.cpu().clone() for k, v in dgr._C.raster_views(call).items()}
+    L = call.L
+    loss = (color * gc.to(color.device)).sum()
+    if gd is not None:
+        loss = loss + (invd * gd.to(color.device)).sum()
+    loss.backward()
+    torch.cuda.synchronize()
+    grads = {k: v.grad.detach().cpu() for k, v in lv.items() if torch.is_tensor(v) and v.grad is not None}
+    return dict(color=color.detach().cpu(), radii=radii.cpu(), invdepth=invd.detach().cpu(), views=views, L=L,
+                grads=grads)
+
+
+def oracle_call(settings, args, dtype=torch.float64):
+    """The ``OracleRun`` of the same recorded call on the CPU (empty tensors count as absent)."""
+    cpu = lambda t: None if t is None or t.numel() == 0 else t.detach().cpu()
+    lv = {k: (None if cpu(v) is None else cpu(v).clone().requires_grad_(True)) for k, v in args.items()}
+    s = settings
+
+    def call(lv, **extra):
+        return ro.rasterize(lv["means3D"], lv["means2D"], lv["shs"], lv["colors_precomp"], lv["opacities"],
+                            lv["scales"], lv["rotations"], lv["cov3D_precomp"], image_height=s["image_height"],
+                            image_width=s["image_width"], tanfovx=s["tanfovx"], tanfovy=s["tanfovy"], bg=cpu(s["bg"]),
+                            scale_modifier=s["scale_modifier"], viewmatrix=cpu(s["viewmatrix"]),
+                            projmatrix=cpu(s["projmatrix"]), sh_degree=s["sh_degree"], campos=cpu(s["campos"]),
+                            interpolation_weights=cpu(s["interpolation_weights"]),
+                            num_node_kids=cpu(s["num_node_kids"]), dtype=dtype, **extra)
+    return OracleRun(lv, call)
+
+
 def assert_verified(name, res, mixed_tol=1.0, fragile_frac=FRAGILE_FRAC):
     """Everything ``verify`` found within its bounds: integers bit-exact (when checked), every fragile pixel matched,
     ``n_contrib`` exact on every pixel, pixels and gradients under ``assert_stats``; the share of fragile pixels (a

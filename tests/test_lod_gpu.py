@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from boundary_fixtures import lod_lerp
 from hgs import hierarchy, synth
 from oracle import lod_oracle as lo
 
@@ -144,15 +145,11 @@ def test_render_post_flow(gpu):
     n = expand_to_size(nodes, boxes, tau, cam.camera_center.to(dev), torch.zeros(3), ri, pi, ni)
     assert 0 < n < G
     get_interpolation_weights(ni[:n], tau, nodes, boxes, cam.camera_center.cpu(), torch.zeros(3), w, ns)
-    xyz, shs, op = h.xyz.to(dev), h.shs.to(dev), h.alpha.to(dev).abs()
-    sc, rot = torch.exp(h.log_scales.to(dev)), torch.nn.functional.normalize(h.rots.to(dev))
-    r, p = ri[:n].long(), pi[:n].long()
-    t = w[:n, None]
-    lerp = lambda a: t.view(-1, *([1] * (a.dim() - 1))) * a[r] + (1 - t).view(-1, *([1] * (a.dim() - 1))) * a[p]
-    pr, rr = rot[p], rot[r]
-    pr = torch.where(((rr * pr).sum(1, keepdim=True) < 0), -pr, pr)
-    rot_i = t * rr + (1 - t) * pr
-    scene = synth.Scene(lerp(xyz).cpu(), lerp(sc).cpu(), rot_i.cpu(), lerp(op).cpu(), lerp(shs).cpu(), 3)
+    full = dict(xyz=h.xyz.to(dev), scaling=torch.exp(h.log_scales.to(dev)),
+                rotation=torch.nn.functional.normalize(h.rots.to(dev)), opacity=h.alpha.to(dev).abs(),
+                features=h.shs.to(dev))
+    L = lod_lerp(full, ri[:n].long(), pi[:n].long(), w[:n])
+    scene = synth.Scene(*(L[k].cpu() for k in ("xyz", "scaling", "rotation", "opacity", "features")), 3)
     gc, gd = synth.upstream_grads(cam.image_height, cam.image_width)
     bg = torch.zeros(3)
     res = pa.verify_pair(scene, cam, bg, gc, gd, dev, interpolation_weights=w, num_node_kids=ns, do_depth=False)
@@ -180,8 +177,9 @@ def test_million_leaf_hierarchy_cut_and_render(gpu):
     G = h.xyz.shape[0]
     ri = torch.zeros(G, dtype=torch.int32, device=gpu); pi = torch.zeros_like(ri); ni = torch.zeros_like(ri)
     w = torch.zeros(G, device=gpu); ns = torch.zeros(G, dtype=torch.int32, device=gpu)
-    xyz, shs, op = h.xyz.to(gpu), h.shs.to(gpu), h.alpha.to(gpu).abs()
-    sc, rot = torch.exp(h.log_scales.to(gpu)), torch.nn.functional.normalize(h.rots.to(gpu))
+    full = dict(xyz=h.xyz.to(gpu), scaling=torch.exp(h.log_scales.to(gpu)),
+                rotation=torch.nn.functional.normalize(h.rots.to(gpu)), opacity=h.alpha.to(gpu).abs(),
+                features=h.shs.to(gpu))
     prev_n = None
     for tau_px in (0.0, 3.0, 15.0):
         tau = (2 * (tau_px + 0.5)) * cam.tanfovx / (0.5 * W)
@@ -196,17 +194,13 @@ def test_million_leaf_hierarchy_cut_and_render(gpu):
             assert n <= prev_n
         prev_n = n
         with torch.no_grad():
-            r, p = ri[:n].long(), pi[:n].long()
-            t = w[:n, None]
-            lerp = lambda a: t.view(-1, *([1] * (a.dim() - 1))) * a[r] + (1 - t).view(-1, *([1] * (a.dim() - 1))) * a[p]
-            pr, rr = rot[p], rot[r]
-            pr = torch.where(((rr * pr).sum(1, keepdim=True) < 0), -pr, pr)
+            L = lod_lerp(full, ri[:n].long(), pi[:n].long(), w[:n])
             rs = dgr.GaussianRasterizationSettings(**pa.settings_kwargs(
                 cam, torch.zeros(3), 3, do_depth=False, device=gpu, interpolation_weights=w, num_node_kids=ns))
             color, radii, _ = dgr.GaussianRasterizer(rs)(
-                means3D=lerp(xyz).contiguous(), means2D=torch.zeros(n, 3, device=gpu), shs=lerp(shs).contiguous(),
-                opacities=lerp(op).contiguous(), scales=lerp(sc).contiguous(),
-                rotations=(t * rr + (1 - t) * pr).contiguous())
+                means3D=L["xyz"].contiguous(), means2D=torch.zeros(n, 3, device=gpu),
+                shs=L["features"].contiguous(), opacities=L["opacity"].contiguous(),
+                scales=L["scaling"].contiguous(), rotations=L["rotation"].contiguous())
         assert torch.isfinite(color).all() and float(color.max()) > 0.05
         assert int((radii > 0).sum()) > 0.5 * n
         print(f"tau={tau_px}px: cut {n} of {G} nodes, mean colour {float(color.mean()):.4f}")
@@ -250,10 +244,7 @@ def test_in_op_lod_interpolation_matches_python_glue(gpu, skybox):
     # (a) python-side lerp exactly as the reference glue, rows handed to the op
     A = leaves()
     r, p = ri[:n].long(), pi[:n].long()
-    t = w[:n].unsqueeze(1); ti = 1 - t
-    parents, rots = A["rot"][p], A["rot"][r]
-    dots = torch.bmm(rots.unsqueeze(1), parents.unsqueeze(2)).flatten()
-    parents = torch.where((dots < 0)[:, None], -parents, parents)
+    L = lod_lerp(dict(xyz=A["xyz"], scaling=A["sc"], rotation=A["rot"], opacity=A["op"], features=A["shs"]), r, p, w[:n])
     sk = torch.arange(G - skybox, G, device=gpu)
     cat = lambda base, full: torch.cat((base, full[sk])).contiguous()
     wa, ka = w.clone(), ns.clone()                       # gaussian_renderer/__init__.py:232-234
@@ -262,10 +253,8 @@ def test_in_op_lod_interpolation_matches_python_glue(gpu, skybox):
     m2a = torch.zeros(n + skybox, 3, device=gpu, requires_grad=True)
     e = torch.empty(0, dtype=torch.int32, device=gpu)
     ca, ra, _ = dgr.GaussianRasterizer(settings(e, e, wa, ka))(
-        means3D=cat(t * A["xyz"][r] + ti * A["xyz"][p], A["xyz"]), means2D=m2a,
-        shs=cat(t.unsqueeze(2) * A["shs"][r] + ti.unsqueeze(2) * A["shs"][p], A["shs"]),
-        opacities=cat(t * A["op"][r] + ti * A["op"][p], A["op"]),
-        scales=cat(t * A["sc"][r] + ti * A["sc"][p], A["sc"]), rotations=cat(t * rots + ti * parents, A["rot"]))
+        means3D=cat(L["xyz"], A["xyz"]), means2D=m2a, shs=cat(L["features"], A["shs"]),
+        opacities=cat(L["opacity"], A["op"]), scales=cat(L["scaling"], A["sc"]), rotations=cat(L["rotation"], A["rot"]))
     (ca * gc).sum().backward()
     # (b) in-op: full arrays + index tensors (+ the skybox count on the context)
     B = leaves()
