@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libhgs.so")
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 INST_GRAD_STRIDE = 10          # floats per (tile, Gaussian) record of the backward scratch (HGS_INST_GRAD_STRIDE)
 ERR_CAPACITY = 5
 
@@ -96,6 +96,14 @@ class AdamTensor(C.Structure):
 
 ADAM_MAX_TENSORS = 8
 
+
+class DensifyTensor(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("dst", C.c_void_p),
+                ("dst_exp_avg", C.c_void_p), ("dst_exp_avg_sq", C.c_void_p), ("row_len", C.c_int32), ("kind", C.c_int32)]
+
+
+DENSIFY_COPY, DENSIFY_XYZ, DENSIFY_SCALING = 0, 1, 2
+
 # symbol -> (restype, argtypes); also the list the export test checks against include/hgs.h
 _P = C.c_void_p
 SIGNATURES = {
@@ -148,6 +156,11 @@ SIGNATURES = {
     "hgs_sh_colors_batched_bwd": (C.c_int, [C.POINTER(ShColorView), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
                                             _P, _P, C.c_int32, _P, C.c_int]),
     "hgs_adam_step": (C.c_int, [C.POINTER(AdamTensor), C.c_int32, C.c_int64, _P, C.c_int64, _P, _P, C.c_int]),
+    "hgs_densify_tmp_bytes": (C.c_size_t, [C.c_int64]),
+    "hgs_densify_plan": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_float, _P, _P,
+                                   C.c_int32, _P, C.c_int]),
+    "hgs_densify_apply": (C.c_int, [C.POINTER(DensifyTensor), C.c_int32, C.c_int64, C.POINTER(C.c_int64), _P, _P, _P, _P,
+                                    _P, C.c_int]),
     "hgs_knn_tmp_bytes": (C.c_size_t, [C.c_int32]),
     "hgs_dist2_knn3": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int]),
     "hgs_hier_load": (C.c_int, [C.c_char_p, C.POINTER(HierHost)]),

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define HGS_ABI_VERSION 7
+#define HGS_ABI_VERSION 8
 #define HGS_TILE 16
 #define HGS_INST_GRAD_STRIDE 10 /* floats per (tile, Gaussian) instance in the backward scratch (40 bytes: the ten sums) */
 
@@ -475,6 +475,52 @@ int hgs_ssim_fwd(const float* img1, const float* img2, int32_t N, int32_t C, int
                  float* out_mean, float* maps, void* tmp, hgs_stream_t stream, int device);
 int hgs_ssim_bwd(const float* img1, const float* img2, const float* maps, const float* grad_out, int32_t per_image,
                  int32_t N, int32_t C, int32_t H, int32_t W, float* grad_img1, hgs_stream_t stream, int device);
+
+/* ---------------------------------------------------------------------------
+ * Adaptive density control as one stream compaction (hgs.densify): replaces the torch chain of
+ * the reference's GaussianModel.densify_and_prune (scene/gaussian_model.py:528-685, called from
+ * train_single.py:150-151).  Per row r of P, with F protected leading rows (scaffold_points) and d = percent_dense *
+ * extent:  g = accum (NaN -> 0), o = sigmoid(opacity), m = max_k exp(scaling_k), w = max_radii2D * o^(1/5);
+ *   clone = |g| w >= max_grad and o > 0.15 and m <= d and r >= F;   split = g w >= max_grad and o > 0.15 and m > d and
+ *   r >= F (no absolute value, gaussian_model.py:625);   low = o < min_opacity.
+ * Output rows, each block in ascending r: originals with not split and not (low and r >= F); one copy of every clone
+ * row with not low; child 0 of every split row with not low; child 1 of the same rows.  The k-th split row (ascending
+ * r, pruned ones included) owns the noise rows z[k] and z[S + k] of noise [2S,3];  child j: xyz' = xyz + R(q / |q|)
+ * (exp(scaling) * z_j) with R of utils/general_utils.py:82-103, scaling' = log(exp(scaling) / 1.6), the rest copied;
+ * moments of new rows are zero.
+ * hgs_densify_tmp_bytes: host only (no GPU needed); 0 for a P outside [0, 2^31 - 1] (the reason in hgs_last_error).
+ * hgs_densify_plan: accum [P], radii [P], opacity [P], scaling [P,3] (device, raw as the optimizer holds them); tmp:
+ *   hgs_densify_tmp_bytes(P) bytes of device memory, 256-byte aligned; totals: four int64 that the device can write
+ *   (device memory, or pinned device-mapped memory from hgs_host_alloc): kept originals, kept clones, split rows S,
+ *   kept split rows.  wait != 0: the call returns after the stream has drained (polled; HGS_BLOCKING_WAIT honoured), so
+ *   that host-mapped totals can be read; otherwise it is asynchronous on `stream`.
+ * hgs_densify_apply: up to HGS_ADAM_MAX_TENSORS tensors of P rows with the plan left in tmp; totals: the plan's four
+ *   values ON THE HOST; every tensor's dst (and moments, if it has any: both or neither) holds totals[0] + totals[1] +
+ *   2 totals[3] rows.  kind: HGS_DENSIFY_XYZ / HGS_DENSIFY_SCALING get the child arithmetic (row_len 3), everything
+ *   else is copied.  scaling [P,3], rotation [P,4] and noise [2S,3] are read for the children of an XYZ tensor.
+ *   Asynchronous on `stream`.  No atomics: two calls give bit-identical results.
+ * All check sizes, null pointers, 0 <= F <= P, max_grad > 0 and rows x row_len overflow before any HIP call; no state is
+ * kept between calls. */
+#define HGS_DENSIFY_COPY 0
+#define HGS_DENSIFY_XYZ 1
+#define HGS_DENSIFY_SCALING 2
+typedef struct hgs_densify_tensor {
+  const float* src;          /* [P, row_len] */
+  const float* exp_avg;      /* [P, row_len] or NULL (then exp_avg_sq is NULL too and no moments are written) */
+  const float* exp_avg_sq;
+  float* dst;                /* [P', row_len] */
+  float* dst_exp_avg;
+  float* dst_exp_avg_sq;
+  int32_t row_len;
+  int32_t kind;              /* HGS_DENSIFY_* */
+} hgs_densify_tensor;
+size_t hgs_densify_tmp_bytes(int64_t P);
+int hgs_densify_plan(const float* accum, const float* radii, const float* opacity, const float* scaling, int64_t P,
+                     int64_t F, float max_grad, float min_opacity, float d, void* tmp, int64_t* totals, int32_t wait,
+                     hgs_stream_t stream, int device);
+int hgs_densify_apply(const hgs_densify_tensor* tensors, int32_t n_tensors, int64_t P, const int64_t* totals,
+                      const float* scaling, const float* rotation, const float* noise, const void* tmp,
+                      hgs_stream_t stream, int device);
 
 /* ---------------------------------------------------------------------------
  * Direct (two-shot) SUM all-reduce over peer pointers: the exchange step of per-view data parallelism (SURVEY.md
