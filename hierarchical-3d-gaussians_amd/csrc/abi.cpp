@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <cmath>
 #include <mutex>
 #include <vector>
 
@@ -675,6 +676,45 @@ int hgs_ssim_bwd(const float* img1, const float* img2, const float* maps, const 
   HGS_HIP(hipSetDevice(device));
   return launch_ssim_bwd(img1, img2, maps, grad_out, per_image, N, C, H, W, grad_img1,
                          static_cast<hipStream_t>(stream));
+}
+
+// Everything hgs_photo_fwd / hgs_photo_bwd can refuse without touching the device.
+static bool photo_args_ok(const hgs_photo_args* a, const void* tmp) {
+  if (!a) { set_error("null argument"); return false; }
+  if (!ssim_sizes_ok(a->N, a->C, a->H, a->W)) return false;
+  if (a->exposure && a->C != 3) { set_error("bad sizes: C=%d with an exposure (a 3x4 exposure needs C = 3)", a->C); return false; }
+  if (!a->rendered || !a->gt || !tmp) { set_error("null argument"); return false; }
+  if (((a->invdepth != nullptr) != (a->mono_invdepth != nullptr)) || ((a->invdepth != nullptr) != (a->depth_mask != nullptr))) {
+    set_error("incomplete depth triple: invdepth, mono_invdepth and depth_mask are given all three or none");
+    return false;
+  }
+  if (!(a->lambda_dssim >= 0.0 && a->lambda_dssim <= 1.0)) { set_error("lambda_dssim=%g not in [0, 1]", a->lambda_dssim); return false; }
+  if (!std::isfinite(a->depth_weight)) { set_error("depth_weight=%g is not finite", a->depth_weight); return false; }
+  if ((uintptr_t)tmp & 7u) { set_error("tmp must be 8-byte aligned"); return false; }
+  return true;
+}
+
+size_t hgs_photo_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W) {
+  if (!ssim_sizes_ok(N, C, H, W)) return 0;
+  return photo_tmp_bytes(N, C, H, W);
+}
+
+int hgs_photo_fwd(const hgs_photo_args* args, float* out, float* maps, void* tmp, hgs_stream_t stream, int device) {
+  if (!photo_args_ok(args, tmp)) return HGS_ERR_INVALID;
+  if (!out) { set_error("null argument"); return HGS_ERR_INVALID; }
+  HGS_HIP(hipSetDevice(device));
+  return launch_photo_fwd(*args, out, maps, tmp, static_cast<hipStream_t>(stream));
+}
+
+int hgs_photo_bwd(const hgs_photo_args* args, const float* maps, const float* grad_out, float* grad_rendered,
+                  float* grad_exposure, float* grad_invdepth, void* tmp, hgs_stream_t stream, int device) {
+  if (!photo_args_ok(args, tmp)) return HGS_ERR_INVALID;
+  if (!maps || !grad_out || !grad_rendered) { set_error("null argument"); return HGS_ERR_INVALID; }
+  if (grad_exposure && !args->exposure) { set_error("grad_exposure without an exposure"); return HGS_ERR_INVALID; }
+  if (grad_invdepth && !args->invdepth) { set_error("grad_invdepth without an invdepth"); return HGS_ERR_INVALID; }
+  HGS_HIP(hipSetDevice(device));
+  return launch_photo_bwd(*args, maps, grad_out, grad_rendered, grad_exposure, grad_invdepth, tmp,
+                          static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

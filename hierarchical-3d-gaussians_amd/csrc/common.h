@@ -315,5 +315,11 @@ int launch_ssim_fwd(const float* img1, const float* img2, int32_t N, int32_t C, 
                     float* out_image, float* out_mean, float* maps, void* tmp, hipStream_t s);
 int launch_ssim_bwd(const float* img1, const float* img2, const float* maps, const float* grad_out, int32_t per_image,
                     int32_t N, int32_t C, int32_t H, int32_t W, float* grad_img1, hipStream_t s);
+// fused training loss (photometric.hip): the caller has checked the sizes with ssim_sizes_ok (the tiling is the same,
+// one workgroup per tile of an image instead of a plane) and the argument combinations
+size_t photo_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
+int launch_photo_fwd(const hgs_photo_args& a, float* out, float* maps, void* tmp, hipStream_t s);
+int launch_photo_bwd(const hgs_photo_args& a, const float* maps, const float* grad_out, float* grad_rendered,
+                     float* grad_exposure, float* grad_invdepth, void* tmp, hipStream_t s);
 
 }  // namespace hgs

@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libhgs.so")
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 INST_GRAD_STRIDE = 10          # floats per (tile, Gaussian) record of the backward scratch (HGS_INST_GRAD_STRIDE)
 ERR_CAPACITY = 5
 
@@ -104,6 +104,14 @@ class DensifyTensor(C.Structure):
 
 DENSIFY_COPY, DENSIFY_XYZ, DENSIFY_SCALING = 0, 1, 2
 
+
+class PhotoArgs(C.Structure):
+    _fields_ = [("rendered", C.c_void_p), ("gt", C.c_void_p), ("exposure", C.c_void_p), ("alpha_mask", C.c_void_p),
+                ("invdepth", C.c_void_p), ("mono_invdepth", C.c_void_p), ("depth_mask", C.c_void_p),
+                ("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("clamp", C.c_int32),
+                ("reserved", C.c_int32), ("lambda_dssim", C.c_double), ("depth_weight", C.c_double)]
+
+
 # symbol -> (restype, argtypes); also the list the export test checks against include/hgs.h
 _P = C.c_void_p
 SIGNATURES = {
@@ -134,6 +142,9 @@ SIGNATURES = {
     "hgs_ssim_fwd": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int]),
     "hgs_ssim_bwd": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
                                C.c_int]),
+    "hgs_photo_tmp_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "hgs_photo_fwd": (C.c_int, [C.POINTER(PhotoArgs), _P, _P, _P, _P, C.c_int]),
+    "hgs_photo_bwd": (C.c_int, [C.POINTER(PhotoArgs), _P, _P, _P, _P, _P, _P, _P, C.c_int]),
     "hgs_timing_enable": (C.c_int, [C.c_int]),
     "hgs_timing_stage_count": (C.c_int, []),
     "hgs_timing_stage_name": (C.c_char_p, [C.c_int]),

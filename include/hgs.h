@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define HGS_ABI_VERSION 8
+#define HGS_ABI_VERSION 9
 #define HGS_TILE 16
 #define HGS_INST_GRAD_STRIDE 10 /* floats per (tile, Gaussian) instance in the backward scratch (40 bytes: the ten sums) */
 
@@ -475,6 +475,48 @@ int hgs_ssim_fwd(const float* img1, const float* img2, int32_t N, int32_t C, int
                  float* out_mean, float* maps, void* tmp, hgs_stream_t stream, int device);
 int hgs_ssim_bwd(const float* img1, const float* img2, const float* maps, const float* grad_out, int32_t per_image,
                  int32_t N, int32_t C, int32_t H, int32_t W, float* grad_img1, hgs_stream_t stream, int device);
+
+/* ---------------------------------------------------------------------------
+ * Fused training loss (hgs.loss.photometric_loss): the whole loss of the reference's three
+ * training scripts and its gradients.  Per pixel and output channel j, in the reference's order of operations:
+ *   u_j = sum_i r_i E[i][j] + E[j][3]   (gaussian_renderer/__init__.py:115-117; u = r when exposure is NULL)
+ *   v_j = min(max(u_j, 0), 1)           (gaussian_renderer/__init__.py:118; only with clamp != 0; the gradient passes
+ *                                        where 0 <= u_j <= 1, both ends included)
+ *   x_j = v_j m                         (train_single.py:102-104, train_post.py:134-137; m = 1 when alpha_mask is NULL)
+ *   L1 = mean |x - gt| (d|t|/dt = sign t, sign 0 = 0), S = SSIM(x, gt) as hgs_ssim_fwd, D = mean |(d - d_mono) m_d|
+ *   loss = (1 - lambda_dssim) L1 + lambda_dssim (1 - S) + depth_weight D
+ *                                       (train_single.py:106-117, train_post.py:139-140, train_coarse.py:99-105)
+ * All means run over every element of the batch.  Every tensor is float32, contiguous, on the device.
+ * hgs_photo_tmp_bytes: host only (no GPU needed); 0 for bad sizes (the reason in hgs_last_error).
+ * hgs_photo_fwd: out [4] = loss, L1, S, D (D = 0 without a depth term).  maps: NULL, or [3,N,C,H,W] floats that receive
+ *   the per-pixel SSIM partials the backward needs.  tmp: hgs_photo_tmp_bytes, 8-byte aligned.  Two launches (the tiles,
+ *   then a fixed-order reduction of the per-workgroup partials, which are kept in double).
+ * hgs_photo_bwd: from the forward's maps and the upstream gradient of `loss` on the device (grad_out [1]):
+ *   grad_rendered [N,C,H,W]; grad_exposure [N,3,4] or NULL (12 sums per image over all pixels, accumulated in double and
+ *   reduced in a fixed order); grad_invdepth [N,H,W] or NULL = depth_weight grad_out / (N H W) sign((d - d_mono) m_d)
+ *   m_d.  tmp as for the forward.  One launch, plus the reduction when grad_exposure is given.
+ * No atomics: two calls give bit-identical results.  All three check, before any HIP call: the sizes as hgs_ssim_*
+ * does (the tiling is the same), C == 3 with an exposure, the depth triple given whole or not at all, lambda_dssim in
+ * [0, 1], a finite depth_weight, grad_exposure / grad_invdepth only with exposure / invdepth.  Asynchronous on
+ * `stream` (no host synchronisation). */
+typedef struct hgs_photo_args {
+  const float* rendered;       /* [N,C,H,W] r */
+  const float* gt;             /* [N,C,H,W] */
+  const float* exposure;       /* [N,3,4] row-major, or NULL */
+  const float* alpha_mask;     /* [N,H,W], or NULL */
+  const float* invdepth;       /* [N,H,W] d, or NULL (then the next two are NULL too) */
+  const float* mono_invdepth;  /* [N,H,W] */
+  const float* depth_mask;     /* [N,H,W] */
+  int32_t N, C, H, W;
+  int32_t clamp;               /* 0 / 1 */
+  int32_t reserved;
+  double lambda_dssim;
+  double depth_weight;
+} hgs_photo_args;
+size_t hgs_photo_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
+int hgs_photo_fwd(const hgs_photo_args* args, float* out, float* maps, void* tmp, hgs_stream_t stream, int device);
+int hgs_photo_bwd(const hgs_photo_args* args, const float* maps, const float* grad_out, float* grad_rendered,
+                  float* grad_exposure, float* grad_invdepth, void* tmp, hgs_stream_t stream, int device);
 
 /* ---------------------------------------------------------------------------
  * Adaptive density control as one stream compaction (hgs.densify): replaces the torch chain of
