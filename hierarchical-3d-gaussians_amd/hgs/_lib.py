@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libhgs.so")
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 INST_GRAD_STRIDE = 10          # floats per (tile, Gaussian) record of the backward scratch (HGS_INST_GRAD_STRIDE)
 ERR_CAPACITY = 5
 
@@ -105,6 +105,22 @@ class DensifyTensor(C.Structure):
 DENSIFY_COPY, DENSIFY_XYZ, DENSIFY_SCALING = 0, 1, 2
 
 
+class StepArgs(C.Structure):
+    _fields_ = [("P", C.c_int64), ("n", C.c_int64), ("radii", C.c_void_p), ("indices", C.c_void_p),
+                ("visible", C.c_void_p), ("means2D_grad", C.c_void_p), ("max_radii2D", C.c_void_p),
+                ("accum", C.c_void_p), ("denom", C.c_void_p), ("opacity_grad", C.c_void_p), ("lock_mask", C.c_void_p),
+                ("lock_head", C.c_int64), ("lock_tail", C.c_int64), ("protect_head", C.c_int64),
+                ("select_all", C.c_int32), ("lock_opacity", C.c_int32), ("clamp", C.c_int32),
+                ("clamp_threshold", C.c_float)]
+
+
+class StepTensor(C.Structure):
+    _fields_ = [("adam", AdamTensor), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+STEP_LOCKABLE, STEP_SCALING = 1, 2
+
+
 class PhotoArgs(C.Structure):
     _fields_ = [("rendered", C.c_void_p), ("gt", C.c_void_p), ("exposure", C.c_void_p), ("alpha_mask", C.c_void_p),
                 ("invdepth", C.c_void_p), ("mono_invdepth", C.c_void_p), ("depth_mask", C.c_void_p),
@@ -172,6 +188,9 @@ SIGNATURES = {
                                    C.c_int32, _P, C.c_int]),
     "hgs_densify_apply": (C.c_int, [C.POINTER(DensifyTensor), C.c_int32, C.c_int64, C.POINTER(C.c_int64), _P, _P, _P, _P,
                                     _P, C.c_int]),
+    "hgs_step_tmp_bytes": (C.c_size_t, [C.c_int64]),
+    "hgs_step_select": (C.c_int, [C.POINTER(StepArgs), _P, _P, C.c_int]),
+    "hgs_step_apply": (C.c_int, [C.POINTER(StepArgs), C.POINTER(StepTensor), C.c_int32, _P, _P, C.c_int]),
     "hgs_knn_tmp_bytes": (C.c_size_t, [C.c_int32]),
     "hgs_dist2_knn3": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int]),
     "hgs_hier_load": (C.c_int, [C.c_char_p, C.POINTER(HierHost)]),

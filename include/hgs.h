@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define HGS_ABI_VERSION 9
+#define HGS_ABI_VERSION 10
 #define HGS_TILE 16
 #define HGS_INST_GRAD_STRIDE 10 /* floats per (tile, Gaussian) instance in the backward scratch (40 bytes: the ten sums) */
 
@@ -563,6 +563,76 @@ int hgs_densify_plan(const float* accum, const float* radii, const float* opacit
 int hgs_densify_apply(const hgs_densify_tensor* tensors, int32_t n_tensors, int64_t P, const int64_t* totals,
                       const float* scaling, const float* rotation, const float* noise, const void* tmp,
                       hgs_stream_t stream, int device);
+
+/* ---------------------------------------------------------------------------
+ * The bookkeeping between loss.backward() and the next render as two launches (hgs.step):
+ * replaces the ~twenty torch launches and four device-to-host waits of train_single.py:144-186, train_post.py:164-192
+ * and train_coarse.py:110-145.  P model rows, six (or any <= HGS_ADAM_MAX_TENSORS per call) parameter tensors [P, row_len]
+ * float32 with gradient and Adam moments.  Three parts, each optional, in this order:
+ *  1. Statistics (train_single.py:147-148, train_coarse.py:110; scene/gaussian_model.py:687-689).  Either (a) raw radii
+ *     [n] int32 as the rasterizer returns them, rendered row i being model row r = indices[i] (or r = i without
+ *     indices, n <= P) and visible iff radii[i] > 0; or (b) visible [n] int64 model rows with their compacted radii [n],
+ *     the pair render() returns, every listed row visible.  For every visible row r:
+ *       max_radii2D[r] = max(max_radii2D[r], float(radius));
+ *       if accum: accum[r] = max(sqrt(g[r,0]^2 + g[r,1]^2), accum[r]) with g = means2D_grad [P,3];  denom[r] += 1.
+ *     max is torch.maximum's: a NaN operand gives NaN.  A row may be listed at most once (not checked; the reference's
+ *     indexed assignment is undefined there too); a row outside [0, P) is skipped.
+ *  2. Optimizer step (train_single.py:162-178, train_post.py:167-192).  Row r is LOCKED if r < lock_head or r >= P -
+ *     lock_tail or lock_mask[r] != 0.  The effective gradient of a tensor flagged HGS_STEP_LOCKABLE is 0 at a locked row,
+ *     the gradient everywhere else.  select_all == 0: the selected rows are those whose effective opacity gradient
+ *     (opacity_grad [P]; lock_opacity: opacity is lockable) is != 0 -- and if no row is selected, every row is
+ *     (train_single.py:173-177 with scene/OurAdam.py:214: an empty `relevant` takes the dense path).  select_all != 0:
+ *     every row (train_post.py:191).  Selected rows of every tensor take exactly hgs_adam_step's update with the
+ *     effective gradient; unselected rows are not read (but for the scaling rows part 3 looks at).  A tensor with
+ *     grad == NULL is not updated (a densification iteration left no gradients).
+ *  3. Size clamp (train_single.py:180-186, train_coarse.py:141-145), on the tensor flagged HGS_STEP_SCALING (row_len 3),
+ *     on its value after part 2, for every row r >= protect_head: if max_k exp(s[r,k]) > clamp_threshold then
+ *     s[r,k] = log(exp(s[r,k]) * 0.8) for all k.  Moments are not touched.  A row whose maximum is within a relative
+ *     1e-5 of the threshold may go either way (f-8's knife-edge band).
+ * Not reproduced, on purpose: the [k,2] `relevant` of train_coarse.py:133 (the coarse configuration is expressed as a
+ * lock of `scaling` alone with lock_head = skybox_points, clamp (0.1 extent, skybox_points) and selection by opacity
+ * gradient); the exposure optimizer (12 floats per camera, stays torch); reset_opacity; the zeroed slices of the .grad
+ * tensors themselves (unobservable after zero_grad(set_to_none=True)).
+ * hgs_step_tmp_bytes: host only (no GPU needed); 0 for a P outside [0, 2^31 - 1] (the reason in hgs_last_error).
+ * hgs_step_select: part 1, and one class byte per model row (selected / locked / clamp candidate) plus one "some row
+ *   was selected" word into tmp (hgs_step_tmp_bytes(P) bytes of device memory, 256-byte aligned).  The word is zeroed
+ *   on the stream, set by wave ballot and one vector store per wave.  n == 0: no statistics.
+ * hgs_step_apply: parts 2 and 3 from the class bytes and the word the select call of the SAME args left in tmp; the
+ *   word chooses the dense fallback inside the kernel.  One launch per call.  clamp != 0 needs one HGS_STEP_SCALING
+ *   tensor among `tensors`.
+ * Both are asynchronous on `stream`: nothing comes back to the host, nothing waits.  Both check sizes (P, n >= 0,
+ * row lengths, lock_head + lock_tail <= P, 0 <= protect_head <= P), null combinations and the threshold before any HIP
+ * call; P == 0 or nothing to do returns HGS_OK without a launch.  No atomics: two calls give bit-identical results. */
+#define HGS_STEP_LOCKABLE 1   /* hgs_step_tensor.flags: in lock_names */
+#define HGS_STEP_SCALING 2    /* the tensor the size clamp acts on; handled a row (3 floats) at a time */
+typedef struct hgs_step_args {
+  int64_t P;
+  int64_t n;                  /* rendered rows (a) or listed rows (b); 0: no statistics */
+  const int32_t* radii;       /* [n] */
+  const int32_t* indices;     /* (a) [n] or NULL */
+  const int64_t* visible;     /* (b) [n]; NULL: form (a) */
+  const float* means2D_grad;  /* [P,3]; needed with accum */
+  float* max_radii2D;         /* [P]; needed with n > 0 */
+  float* accum;               /* [P] or NULL (then denom is NULL too) */
+  float* denom;               /* [P] */
+  const float* opacity_grad;  /* [P]; NULL: no row is marked selected (apply then updates nothing unless select_all) */
+  const uint8_t* lock_mask;   /* [P] or NULL */
+  int64_t lock_head, lock_tail;
+  int64_t protect_head;       /* rows below are never clamped */
+  int32_t select_all;
+  int32_t lock_opacity;
+  int32_t clamp;              /* != 0: part 3 with clamp_threshold (positive, finite) */
+  float clamp_threshold;
+} hgs_step_args;
+typedef struct hgs_step_tensor {
+  hgs_adam_tensor adam;       /* as hgs_adam_step takes it; grad == NULL: no update (clamp only) */
+  int32_t flags;              /* HGS_STEP_* */
+  int32_t reserved;
+} hgs_step_tensor;
+size_t hgs_step_tmp_bytes(int64_t P);
+int hgs_step_select(const hgs_step_args* args, void* tmp, hgs_stream_t stream, int device);
+int hgs_step_apply(const hgs_step_args* args, const hgs_step_tensor* tensors, int32_t n_tensors, const void* tmp,
+                   hgs_stream_t stream, int device);
 
 /* ---------------------------------------------------------------------------
  * Direct (two-shot) SUM all-reduce over peer pointers: the exchange step of per-view data parallelism (SURVEY.md
