@@ -89,27 +89,28 @@ def repair(inp, rounds=8):
     raise AssertionError(f"the knife-edge bands are not empty after {rounds} repairs: {band_counts(inp)}")
 
 
-def formula(inp, lambda_dssim, depth_weight, dtype, grads=("rendered", "exposure", "invdepth")):
+def formula(inp, lambda_dssim, depth_weight, dtype, grads=("rendered", "exposure", "invdepth"), weight=None):
     """The reference's torch lines (photometric_spec.torch_formula with tests/train_loop.ssim) on the CPU in `dtype`,
-    autograd for the gradients -> dict like the spec's."""
+    autograd for the gradients (of the loss, or of ``weight * loss``) -> dict like the spec's."""
     t = {k: (v.to(dtype).clone() if isinstance(v, torch.Tensor) else v) for k, v in inp.items()}
     leaves = {k: t[k].requires_grad_(True) for k in grads if t.get(k) is not None}
     loss, l1, s, depth = spec.torch_formula(ssim_fn=spec.planes_ssim(tl.ssim), lambda_dssim=lambda_dssim,
                                             depth_weight=depth_weight, **t)
-    loss.backward()
+    (loss if weight is None else weight * loss).backward()
     out = dict(loss=loss.detach(), l1=l1.detach(), ssim=s.detach(), depth=depth.detach())
     for k in ("rendered", "exposure", "invdepth"):
         out["grad_" + k] = leaves[k].grad if k in leaves else None
     return out
 
 
-def fused(inp, lambda_dssim, depth_weight, dev, grads=("rendered", "exposure", "invdepth")):
-    """hgs.loss.photometric_loss on `dev` + backward -> dict like the spec's (CPU tensors)."""
+def fused(inp, lambda_dssim, depth_weight, dev, grads=("rendered", "exposure", "invdepth"), weight=None):
+    """hgs.loss.photometric_loss on `dev` + backward (of the loss, or of ``weight * loss``) -> dict like the spec's
+    (CPU tensors)."""
     from hgs import loss
     t = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in inp.items()}
     leaves = {k: t[k].requires_grad_(True) for k in grads if t.get(k) is not None}
     res = loss.photometric_loss(t.pop("rendered"), t.pop("gt"), lambda_dssim=lambda_dssim, depth_weight=depth_weight, **t)
-    res.loss.backward()
+    (res.loss if weight is None else weight * res.loss).backward()
     out = {k: getattr(res, k).detach().cpu() for k in ("loss", "l1", "ssim", "depth")}
     for k in ("rendered", "exposure", "invdepth"):
         out["grad_" + k] = leaves[k].grad.cpu() if k in leaves else None
@@ -142,3 +143,145 @@ def assert_parity(got, yard, want, what=""):
         if not mx <= max(FLOOR, 3 * ymx):
             fails.append((k, "max", mx, ymx))
     assert not fails, (what, fails)
+
+
+# -- small and awkward images (tests/test_photometric_edges_gpu.py) -----------------------------------------------------
+# `make` lays its special regions out as strips (W - max(1, W // 6) masked columns, max(1, H // 6) rows with q == 0), so
+# at W = 1 its mask is all zero and at H = 1 its depth term has no gradient.  `small` places single pixels instead.
+
+# (H, W, C, N or None for (C,H,W), content): the sizes of test_ssim_gpu.OFF_GRID -- every W of
+# {1, 2, 5, 6, 11, 31, 32, 33, 64, 65} and every H of {1, 2, 5, 6, 15, 16, 17, 33}; 1x1, 1xW and Hx1; single rows and
+# columns, images smaller than the window and one pixel either side of the 32x16 tile grid.  C = 3 comes with a
+# per-image exposure, C in {1, 2, 4} without one.
+SWEEP = [(1, 1, 1, None, "random"), (1, 65, 3, None, "random"), (33, 1, 4, 2, "smooth"), (2, 2, 3, 2, "random"),
+         (5, 5, 2, None, "smooth"), (6, 6, 4, None, "random"), (15, 11, 3, 2, "smooth"), (16, 31, 2, 2, "random"),
+         (17, 32, 3, None, "random"), (33, 33, 4, 2, "random"), (16, 64, 3, None, "smooth"),
+         (17, 65, 1, 2, "smooth"), (1, 32, 1, 2, "random"), (2, 33, 4, None, "smooth"), (5, 64, 3, 2, "random"),
+         (6, 1, 3, None, "random"), (15, 2, 1, 2, "random"), (16, 5, 4, 2, "smooth"), (17, 6, 3, None, "random"),
+         (33, 11, 2, None, "random"), (2, 31, 3, 2, "smooth"), (15, 65, 4, None, "random"),
+         (33, 64, 3, 2, "smooth"), (6, 32, 2, 2, "random"), (1, 5, 3, 2, "smooth"), (16, 33, 3, None, "random"),
+         (1, 1, 3, None, "random"), (1, 1, 3, 2, "smooth")]
+ROLES = 7                   # pixels `small` needs for one of each kind
+
+
+def sweep_case(H, W, C_, N, content):
+    return small((C_, H, W) if N is None else (N, C_, H, W), seed=H * 100 + W, content=content)
+
+
+def _three_levels(shape, g, p0, p_half):
+    """Values in {0, 0.5, 1} with probabilities p0, p_half and the rest, float64."""
+    u = torch.rand(shape, generator=g)
+    return 0.5 * (u >= p0).double() + 0.5 * (u >= p0 + p_half).double()
+
+
+def _small_one(C_, H, W, seed, content, kind, exposure, mask, depth):
+    g = torch.Generator().manual_seed(2000 + seed)
+    if content == "smooth":
+        a = natural(C_, H, W, seed)
+        r = 2.0 * a - 0.55
+        gt = (0.8 * a + 0.2 * natural(C_, H, W, seed + 1)).clamp(0, 1)
+    else:
+        assert content == "random", content
+        a = torch.rand(C_, H, W, generator=g, dtype=torch.float64)
+        r = 1.6 * a - 0.3
+        gt = (0.6 * a + 0.4 * torch.rand(C_, H, W, generator=g, dtype=torch.float64)).clamp(0, 1)
+    # One pixel of each kind at distinct random places.  `live` carries a gradient whatever else the image holds: every
+    # u_j inside (0.3, 0.7), a non-zero mask, x away from gt, a non-zero depth mask and q != 0.  The others (images of at
+    # least ROLES pixels): mask 0, mask 0.5, q == 0 exactly, depth mask 0.5, every channel below 0, every channel above 1.
+    perm = torch.randperm(H * W, generator=g)
+    at = lambda p: (int(perm[p]) // W, int(perm[p]) % W)
+    live = at(0)
+    roles = [at(p) for p in range(1, ROLES)] if H * W >= ROLES else None
+    out = dict(rendered=r, gt=gt)
+    E = None
+    if exposure:
+        E = torch.eye(3, 4, dtype=torch.float64) + 0.06 * torch.randn(3, 4, generator=g, dtype=torch.float64)
+        if kind == 0:
+            E[:, :3] *= 2.0                                   # a gain of about 2
+        elif kind == 1:
+            E[:, 3] -= 0.3                                    # an offset of about -0.3
+        out["exposure"] = E
+    if roles:
+        r[(slice(None),) + roles[4]] = -0.5
+        r[(slice(None),) + roles[5]] = 1.8
+    u_live = 0.3 + 0.4 * torch.rand(C_, generator=g, dtype=torch.float64)
+    r[(slice(None),) + live] = u_live if E is None else torch.linalg.solve(E[:, :3].T, u_live - E[:, 3])
+    m_live = 1.0
+    if mask:
+        m = _three_levels((1, H, W), g, 0.15, 0.2)
+        if roles:
+            m[(0,) + roles[0]] = 0.0
+            m[(0,) + roles[1]] = 0.5
+        if m[(0,) + live] == 0:
+            m[(0,) + live] = 1.0
+        m_live = float(m[(0,) + live])
+        out["alpha_mask"] = m
+    x_live = u_live * m_live
+    gt[(slice(None),) + live] = torch.where(x_live < 0.4, x_live + 0.2, x_live - 0.2)
+    if depth:
+        d = 0.2 + 0.3 * torch.rand(1, H, W, generator=g, dtype=torch.float64)
+        mono = d + 0.05 * torch.randn(1, H, W, generator=g, dtype=torch.float64)
+        md = _three_levels((1, H, W), g, 0.15, 0.2)
+        if roles:
+            mono[(0,) + roles[2]] = d[(0,) + roles[2]]
+            md[(0,) + roles[3]] = 0.5
+        if md[(0,) + live] == 0:
+            md[(0,) + live] = 1.0
+        mono[(0,) + live] = d[(0,) + live] + 0.05
+        out.update(invdepth=d, mono_invdepth=mono, depth_mask=md)
+    return out
+
+
+def small(shape, seed=1, content="random", exposure=None, mask=True, depth=True, clamp=True):
+    """Like `make`, for any size down to 1x1: `rendered` leaves [0, 1] on both sides, the alpha and depth masks take
+    values in {0, 0.5, 1}, the exposure (C = 3 unless switched off) is per image -- the noise of `make`, with a gain of
+    about 2 on every third image and an offset of about -0.3 on the next (a single image takes its kind from the seed)
+    -- and single pixels are forced so that no gradient vanishes (see _small_one).  Repaired."""
+    C_ = shape[-3]
+    exposure = (C_ == 3) if exposure is None else exposure
+    one = lambda n, kind: _small_one(*shape[-3:], seed + 10 * n, content, kind, exposure, mask, depth)
+    if len(shape) == 3:
+        inp = one(0, seed % 3)
+    else:
+        per = [one(n, n % 3) for n in range(shape[0])]
+        inp = {k: torch.stack([p[k] for p in per]) for k in per[0]}
+    inp = {k: v.float() for k, v in inp.items()}
+    inp["clamp"] = clamp
+    return repair(inp)
+
+
+def impulses():
+    """test_ssim_gpu's 3x60x130 impulse image as a batch of two whose second image and second gt are all zero: each
+    `rendered` impulse in one channel only (the first is exactly 1.0: the upper end of the inclusive gate), gt's in all
+    three, under a mixing exposure without offsets, so that u = 0 wherever rendered = 0.  -> inputs, every impulse's
+    (y, x)."""
+    import test_ssim_gpu as ts
+    r = torch.zeros(2, ts.IMP_C, ts.IMP_H, ts.IMP_W)
+    gt = torch.zeros_like(r)
+    for i, (y, x) in enumerate(ts.IMPULSES_1):
+        r[0, i % 3, y, x] = 1.0 if i == 0 else 0.2 + 0.045 * i
+    for i, (y, x) in enumerate(ts.IMPULSES_2):
+        gt[0, :, y, x] = torch.tensor([0.9 - 0.07 * i, 0.3 + 0.05 * i, 0.6])
+    E = torch.eye(3, 4) + 0.05 * torch.tensor([[0., 1, -1, 0], [1, 0, 1, 0], [-1, 1, 0, 0]])
+    inp = dict(rendered=r, gt=gt, exposure=E.expand(2, 3, 4).contiguous(), clamp=True)
+    return inp, ts.IMPULSES_1 + ts.IMPULSES_2
+
+
+def l1_closed_form(inp, grad_out=1.0, dtype=torch.float32):
+    """lambda_dssim = 0 without an exposure: grad_rendered = ((1 - 0) g / count) sign(x - gt) m [0 <= r <= 1] with
+    x = clamp(r) m, every operation in `dtype`; g arrives in `dtype` and the constant is formed in double and rounded to
+    it, as the kernel does."""
+    r, gt = inp["rendered"].to(dtype), inp["gt"].to(dtype)
+    m = inp["alpha_mask"].to(dtype).reshape(r.shape[:-3] + (1,) + r.shape[-2:])
+    c = torch.tensor((1.0 - 0.0) / r.numel() * float(torch.tensor(grad_out, dtype=dtype)), dtype=torch.float64).to(dtype)
+    x = (r.clamp(0, 1) if inp["clamp"] else r) * m
+    gate = ((r >= 0) & (r <= 1)).to(dtype) if inp["clamp"] else torch.ones_like(r)
+    return c * torch.sign(x - gt) * m * gate
+
+
+def depth_closed_form(inp, depth_weight, grad_out=1.0, dtype=torch.float32):
+    """grad_invdepth = (depth_weight / (N H W) * g) sign((d - mono) md) md, every operation in `dtype` and the constant
+    formed in double in the kernel's order, then rounded to it."""
+    d, mono, md = (inp[k].to(dtype) for k in ("invdepth", "mono_invdepth", "depth_mask"))
+    c = torch.tensor(float(depth_weight) / d.numel() * float(torch.tensor(grad_out, dtype=dtype)), dtype=torch.float64).to(dtype)
+    return c * torch.sign((d - mono) * md) * md

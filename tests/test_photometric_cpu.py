@@ -263,3 +263,113 @@ def test_photometric_kernels_compile_for_gfx950_without_scratch():
         print(f"{r['kernel']}: {min(r['waves_regs'], r['waves_lds'])} waves per SIMD (registers {r['waves_regs']}, "
               f"LDS {r['waves_lds']}), LDS {r['lds']} bytes, VGPRs {r['vgpr']}, scratch {r['scratch']}")
         assert r["scratch"] == 0, r
+
+
+# -- the inputs of tests/test_photometric_edges_gpu.py: their conditions hold, checked without a GPU -------------------
+
+def _u_of(inp):
+    four = inp["rendered"].dim() == 4
+    r = (inp["rendered"] if four else inp["rendered"][None]).double()
+    E = inp.get("exposure")
+    u, _ = spec.transform(r, None if E is None else E.double().reshape(-1, 3, 4), inp["clamp"], None)
+    return u
+
+
+@pytest.mark.parametrize("H,W,C_,N,content", pc.SWEEP)
+def test_small_cases_are_not_degenerate(H, W, C_, N, content):
+    """Every case of the off-grid sweep: empty bands, the three gradients of the spec non-zero (a kernel that writes
+    zeros cannot pass), masks in {0, 0.5, 1}, a per-image exposure at C = 3, and from 16 pixels per image on one pixel
+    of every special kind."""
+    inp = pc.sweep_case(H, W, C_, N, content)
+    assert pc.band_counts(inp) == (0, 0, 0)
+    assert inp["rendered"].shape == ((C_, H, W) if N is None else (N, C_, H, W))
+    assert all(v.dtype == torch.float32 for v in inp.values() if isinstance(v, torch.Tensor))
+    assert ("exposure" in inp) == (C_ == 3)
+    want = spec.loss_and_grads(lambda_dssim=0.2, depth_weight=0.7, **inp)
+    for k in ("grad_rendered", "grad_invdepth") + (("grad_exposure",) if C_ == 3 else ()):
+        assert want[k].norm().item() > 0, k
+    for k in ("alpha_mask", "depth_mask"):
+        assert set(inp[k].unique().tolist()) <= {0.0, 0.5, 1.0}, k
+    if C_ == 3 and N is not None:
+        E = inp["exposure"]
+        assert E.shape == (N, 3, 4) and not torch.equal(E[0], E[1])
+        assert 1.7 < E[0, :, :3].diagonal().mean().item() < 2.3 and -0.4 < E[1, :, 3].mean().item() < -0.2
+        for n in range(N):       # every image of the batch carries gradient of its own
+            assert want["grad_rendered"][n].norm().item() > 0 and want["grad_exposure"][n].norm().item() > 0
+            assert want["grad_invdepth"][n].norm().item() > 0
+    if H * W >= 16:
+        u = _u_of(inp)
+        out, r = (u < 0) | (u > 1), inp["rendered"]
+        assert bool(out.any()) and bool((~out).any())
+        assert bool((r < 0).any()) and bool((r > 1).any())
+        q = (inp["invdepth"].double() - inp["mono_invdepth"].double()) * inp["depth_mask"].double()
+        assert bool((inp["alpha_mask"] == 0).any()) and bool((inp["alpha_mask"] == 0.5).any())
+        assert bool((q == 0).any()) and bool((inp["invdepth"] == inp["mono_invdepth"]).any())
+        assert bool((inp["depth_mask"] == 0.5).any())
+
+
+def test_the_sweep_covers_every_size_batch_and_channel_count():
+    assert {w for _, w, *_ in pc.SWEEP} == {1, 2, 5, 6, 11, 31, 32, 33, 64, 65}
+    assert {h for h, *_ in pc.SWEEP} == {1, 2, 5, 6, 15, 16, 17, 33}
+    hw = {(h, w) for h, w, *_ in pc.SWEEP}
+    assert (1, 1) in hw and any(h == 1 and w > 1 for h, w in hw) and any(w == 1 and h > 1 for h, w in hw)
+    assert {n for *_, n, _ in pc.SWEEP} == {None, 2}
+    assert {c for _, _, c, *_ in pc.SWEEP} == {1, 2, 3, 4}
+    assert {k for *_, k in pc.SWEEP} == {"random", "smooth"}
+    assert len(set(pc.SWEEP)) == len(pc.SWEEP)
+
+
+def test_make_degenerates_where_small_does_not():
+    """Why the sweep has a generator of its own: at W = 1 `make` masks every pixel, at H = 1 its depth term has q == 0
+    everywhere; the spec's gradients are then identically zero."""
+    a = spec.loss_and_grads(lambda_dssim=0.2, depth_weight=0.7, **pc.make((3, 33, 1), seed=1))
+    assert a["grad_rendered"].norm().item() == 0 and a["grad_exposure"].norm().item() == 0
+    b = spec.loss_and_grads(lambda_dssim=0.2, depth_weight=0.7, **pc.make((3, 1, 9), seed=1))
+    assert b["grad_invdepth"].norm().item() == 0
+    for shape in ((3, 33, 1), (3, 1, 9), (3, 1, 1)):
+        c = spec.loss_and_grads(lambda_dssim=0.2, depth_weight=0.7, **pc.small(shape, seed=1))
+        assert all(c[k].norm().item() > 0 for k in ("grad_rendered", "grad_exposure", "grad_invdepth")), shape
+
+
+def test_impulse_image_has_exact_zeros_far_from_every_impulse():
+    """The spec on the impulse batch: more than 10 pixels (Chebyshev) from every impulse grad_rendered is exactly zero
+    in all three channels -- u = 0 passes the inclusive gate, x = gt = 0, every window that reaches the pixel sees
+    zeros, A = 0 and sign(0) = 0 -- and the all-zero second image has zero gradients."""
+    import test_ssim_gpu as ts
+    inp, points = pc.impulses()
+    assert pc.band_counts(inp) == (0, 0, 0)
+    assert {x % 32 for _, x in ts.IMPULSES_1[:12]} == {0, 4, 5, 26, 27, 31}
+    assert {y % 16 for y, _ in ts.IMPULSES_1[:12]} == {0, 4, 5, 10, 11, 15}
+    far = ts._far_from(points, ts.IMP_H, ts.IMP_W, 10)
+    print("pixels far from every impulse:", int(far.sum()))
+    assert int(far.sum()) == 3919
+    want = spec.loss_and_grads(lambda_dssim=0.2, **inp)
+    g = want["grad_rendered"]
+    assert bool((g[0][:, far] == 0).all()) and bool((g[0][:, ~far] != 0).any())
+    assert bool((g[1] == 0).all()) and bool((want["grad_exposure"][1] == 0).all())
+    assert bool((want["grad_exposure"][0] != 0).sum() >= 10)     # r_0 du_2 and r_2 du_0 are clamped away: u = -0.05 r
+    for i, (y, x) in enumerate(ts.IMPULSES_1):      # one channel in, every channel out
+        near = g[0][:, max(0, y - 5): y + 6, max(0, x - 5): x + 6]
+        assert bool((near != 0).flatten(1).any(dim=1).all()), (i, y, x)
+
+
+def test_closed_forms_agree_with_the_spec():
+    """lambda_dssim = 0 without an exposure leaves the L1 gradient alone, and the depth gradient is a sign times one
+    constant whatever lambda is -- with a soft and a negative depth mask too.  In float64 the L1 restatement is the
+    spec's own expression, to the bit.  The depth restatement forms its constant in the kernel's order,
+    (depth_weight / count) * g, and the spec in the order depth_weight * g / count: two roundings of a double apart, so
+    it is held to 1e-15 of its largest value."""
+    inp = pc.make((3, 37, 53), seed=11, exposure=False)
+    inp = {k: (v.double() if isinstance(v, torch.Tensor) else v) for k, v in inp.items()}
+    assert int((inp["rendered"] == 0).sum()) > 50
+    got = spec.loss_and_grads(lambda_dssim=0.0, depth_weight=0.7, grad_out=-1.75, **inp)
+    assert torch.equal(got["grad_rendered"], pc.l1_closed_form(inp, -1.75, torch.float64))
+    assert got["grad_rendered"].norm().item() > 0
+    g = torch.Generator().manual_seed(3)
+    levels = torch.tensor([-0.75, 0.0, 0.3, 0.5, 1.0], dtype=torch.float64)
+    inp["depth_mask"] = levels[torch.randint(0, 5, inp["depth_mask"].shape, generator=g)]
+    for lam in (0.0, 0.2, 1.0):
+        got = spec.loss_and_grads(lambda_dssim=lam, depth_weight=0.7, grad_out=-1.75, **inp)
+        want = pc.depth_closed_form(inp, 0.7, -1.75, torch.float64)
+        assert (got["grad_invdepth"] - want).abs().max().item() <= 1e-15 * want.abs().max().item()
+        assert bool((got["grad_invdepth"][inp["depth_mask"] < 0] != 0).any())

@@ -163,13 +163,27 @@ def test_the_plain_case_agrees_with_l1_and_the_fused_ssim(gpu):
           (got["grad_rendered"] - comp["grad_rendered"]).abs().max().item())
 
 
-@pytest.mark.parametrize("shape", [(2, 3, 37, 53), (3, 8, 9), (3, 16, 32)])
+GUARD_SHAPES = [(2, 3, 37, 53), (3, 8, 9), (3, 16, 32)]
+# one pixel, one row, one column per image and one tile of one channel: pc.small's inputs (pc.make has no gradient at
+# W = 1 and takes C = 3)
+GUARD_SMALL = [(1, 3, 1, 1), (3, 1, 65), (2, 3, 33, 1), (1, 1, 16, 32)]
+
+
+@pytest.mark.parametrize("shape", GUARD_SHAPES + GUARD_SMALL)
 def test_buffers_handed_to_the_c_abi_stay_in_bounds(gpu, shape):
     """Every buffer of hgs_photo_fwd / hgs_photo_bwd between guard bytes, outputs pre-filled with 0x00 and with 0xFF:
-    the guards are intact, the inputs unchanged and the results the same bits (nothing unwritten is read)."""
+    the guards are intact, the inputs unchanged and the results the same bits (nothing unwritten is read).  Once with
+    every optional input the shape admits, and once with every optional pointer, grad_exposure and grad_invdepth NULL."""
+    inp = pc.make(shape, seed=8) if shape in GUARD_SHAPES else pc.small(shape, seed=8)
+    _guarded_calls(gpu, shape, inp)
+    off = dict(exposure=False, mask=False, depth=False)
+    _guarded_calls(gpu, shape, pc.make(shape, seed=8, **off) if shape in GUARD_SHAPES else pc.small(shape, seed=8, **off))
+
+
+def _guarded_calls(gpu, shape, inp):
     from hgs import _lib
     lib = _lib.lib()
-    inp = pc.make(shape, seed=8)
+    assert pc.band_counts(inp) == (0, 0, 0)
     N, Ch, H, W = shape if len(shape) == 4 else (1,) + shape
     up = torch.tensor([-1.75])
     stream = lambda: C.c_void_p(torch.cuda.current_stream(gpu).cuda_stream)
@@ -185,16 +199,19 @@ def test_buffers_handed_to_the_c_abi_stay_in_bounds(gpu, shape):
             return g
 
         for k in ("rendered", "gt") + pc.OPTIONAL:
-            t[k] = buf(k, like=inp[k])
+            if k in inp:
+                t[k] = buf(k, like=inp[k])
         g_up = buf("grad_out", like=up)
         out, maps = buf("out", nbytes=16), buf("maps", nbytes=3 * N * Ch * H * W * 4)
         tmp_f, tmp_b = (buf(n, nbytes=lib.hgs_photo_tmp_bytes(N, Ch, H, W)) for n in ("tmp fwd", "tmp bwd"))
-        grad_r, grad_E, grad_d = buf("grad_rendered", nbytes=N * Ch * H * W * 4), buf("grad_exposure", nbytes=N * 48), \
-            buf("grad_invdepth", nbytes=N * H * W * 4)
+        grad_r = buf("grad_rendered", nbytes=N * Ch * H * W * 4)
+        grad_E = buf("grad_exposure", nbytes=N * 48) if "exposure" in inp else None
+        grad_d = buf("grad_invdepth", nbytes=N * H * W * 4) if "invdepth" in inp else None
+        addr = lambda g: None if g is None else g.addr
         args = _lib.PhotoArgs(**{k: t[k].addr for k in t}, N=N, C=Ch, H=H, W=W, clamp=1, reserved=0, lambda_dssim=LAM,
                               depth_weight=DW)
         _lib.check(lib.hgs_photo_fwd(C.byref(args), out.addr, maps.addr, tmp_f.addr, stream(), gpu.index or 0), "fwd")
-        _lib.check(lib.hgs_photo_bwd(C.byref(args), maps.addr, g_up.addr, grad_r.addr, grad_E.addr, grad_d.addr,
+        _lib.check(lib.hgs_photo_bwd(C.byref(args), maps.addr, g_up.addr, grad_r.addr, addr(grad_E), addr(grad_d),
                                      tmp_b.addr, stream(), gpu.index or 0), "bwd")
         out0 = buf("out (maps = NULL)", nbytes=16)
         tmp0 = buf("tmp (maps = NULL)", nbytes=lib.hgs_photo_tmp_bytes(N, Ch, H, W))
@@ -205,7 +222,7 @@ def test_buffers_handed_to_the_c_abi_stay_in_bounds(gpu, shape):
         assert torch.equal(out.view(torch.float32), out0.view(torch.float32))
         return {n: g.view(torch.float32).cpu().clone() for n, g in
                 (("out", out), ("maps", maps), ("grad_rendered", grad_r), ("grad_exposure", grad_E),
-                 ("grad_invdepth", grad_d))}
+                 ("grad_invdepth", grad_d)) if g is not None}
 
     a, b = run(0x00), run(0xFF)
     for k in a:
@@ -213,8 +230,11 @@ def test_buffers_handed_to_the_c_abi_stay_in_bounds(gpu, shape):
     want = spec.loss_and_grads(lambda_dssim=LAM, depth_weight=DW, grad_out=-1.75, **inp)
     assert abs(a["out"][0].item() - want["loss"].item()) <= 1e-5
     for k in ("grad_rendered", "grad_exposure", "grad_invdepth"):
-        w = want[k].reshape(-1)
-        assert ((a[k].double() - w).norm() / w.norm()).item() <= 1e-4, k
+        assert (k in a) == (want[k] is not None), k
+        if k in a:
+            w = want[k].reshape(-1)
+            assert w.norm().item() > 0, k
+            assert ((a[k].double() - w).norm() / w.norm()).item() <= 1e-4, k
 
 
 def test_peak_memory_is_the_maps_and_the_gradients(gpu):
