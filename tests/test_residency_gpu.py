@@ -21,9 +21,9 @@ def _scene(gpu, leaves=20_000, seed=4):
     return h, attrs, h.nodes.to(gpu), h.boxes.to(gpu)
 
 
-def _render(gpu, cam, arrays, ri, pi, w, ns):
+def _render(gpu, cam, arrays, ri, pi, w, ns, sh_degree=3):
     import diff_gaussian_rasterization as dgr
-    kw = pa.settings_kwargs(cam, torch.zeros(3), 3, do_depth=False, device=gpu, interpolation_weights=w, num_node_kids=ns)
+    kw = pa.settings_kwargs(cam, torch.zeros(3), sh_degree, do_depth=False, device=gpu, interpolation_weights=w, num_node_kids=ns)
     kw.update(render_indices=ri, parent_indices=pi)
     rs = dgr.GaussianRasterizationSettings(**kw)
     G = arrays["means3D"].shape[0]
@@ -34,14 +34,14 @@ def _render(gpu, cam, arrays, ri, pi, w, ns):
     return color, radii
 
 
-def _reference(gpu, cam, full, nodes, boxes, tau):
+def _reference(gpu, cam, full, nodes, boxes, tau, sh_degree=3):
     from gaussian_hierarchy._C import expand_to_size, get_interpolation_weights
     G = full["means3D"].shape[0]
     ri = torch.zeros(G, dtype=torch.int32, device=gpu); pi = torch.zeros_like(ri); ni = torch.zeros_like(ri)
     w = torch.zeros(G, device=gpu); ns = torch.zeros(G, dtype=torch.int32, device=gpu)
     n = expand_to_size(nodes, boxes, tau, cam.camera_center.to(gpu), torch.zeros(3), ri, pi, ni)
     get_interpolation_weights(ni[:n], tau, nodes, boxes, cam.camera_center.cpu(), torch.zeros(3), w, ns)
-    color, radii = _render(gpu, cam, full, ri[:n], pi, w, ns)
+    color, radii = _render(gpu, cam, full, ri[:n], pi, w, ns, sh_degree)
     # rows the view needs: every node row, and the parent row of the entries whose weight is not exactly 1 (the in-op
     # LOD gather does not read the parent of a weight-1 entry, gaussian_math.h: lod_row_gather)
     rows = int(torch.unique(torch.cat([ri[:n], pi[:n][w[:n] != 1.0]])).numel())
@@ -79,6 +79,45 @@ def test_budgeted_rendering_is_bit_identical_and_recycles_slots(gpu):
     assert st["evictions"] > 0 and st["retries"] == 0
     assert st["rows_fetched"] > bh.B                           # more rows went through the slots than there are slots
     # bookkeeping is consistent: every occupied slot is the slot of its row, the free list holds the rest
+    ids = bh.id_of_slot.long()
+    occ = ids >= 0
+    assert int(occ.sum()) == bh.resident_rows
+    assert torch.equal(bh.slot_of[ids[occ]].long(), torch.nonzero(occ).reshape(-1))
+    assert int((bh.slot_of >= 0).sum()) == bh.resident_rows and int((bh.slot_of == -2).sum()) == 0
+    free = bh.free_list[:bh.free_top].long()
+    assert free.unique().numel() == bh.free_top and not bool(occ[free].any())
+
+
+@pytest.mark.parametrize("M,sh_degree", [(1, 0), (4, 1), (9, 2)])
+def test_budgeted_rendering_is_bit_identical_at_small_sh_degrees(gpu, M, sh_degree):
+    """The same property with 3 M = 3, 12 and 27 SH floats per row: M = 1 and 9 go through the scalar SH stores of the
+    fetch kernel, which M = 16 never reaches.  A 2 000-leaf scene; the six views need ~2 000 - 2 300 rows each and
+    ~2 700 together, so a budget of 1.05 x the largest view evicts."""
+    from hgs.residency import BudgetedHierarchy
+    h, attrs, nodes, boxes = _scene(gpu, leaves=2_000, seed=8)
+    attrs = dict(attrs, shs=attrs["shs"][:, :M].contiguous())
+    full = {k: v.to(gpu).contiguous() for k, v in attrs.items()}
+    G = full["means3D"].shape[0]
+    refs = [_reference(gpu, cam, full, nodes, boxes, tau, sh_degree) for cam, tau in _views()]
+    need = max(r[3] for r in refs)
+    assert need < 0.9 * G
+    bh = BudgetedHierarchy(attrs["means3D"], attrs["shs"], attrs["opacities"], attrs["scales"], attrs["rotations"], gpu,
+                           budget_rows=int(need * 1.05))
+    assert bh.B < G and bh.M == M
+    for rnd in range(2):
+        for (cam, tau), (color_ref, radii_ref, n_ref, rows_ref) in zip(_views(), refs):
+            sel = bh.select(nodes, boxes, tau, cam.camera_center.to(gpu), cam.camera_center.cpu())
+            assert sel.attempts == 1 and sel.tau == tau and sel.n == n_ref
+            assert int(sel.render_indices.min()) >= 0 and int(sel.parent_indices.min()) >= 0
+            assert int(sel.render_indices.max()) < bh.B
+            arrays = dict(means3D=bh.means3D, shs=bh.shs, opacities=bh.opacities, scales=bh.scales, rotations=bh.rotations)
+            color, radii = _render(gpu, cam, arrays, sel.render_indices, sel.parent_indices, sel.weights, sel.kids,
+                                   sh_degree)
+            assert torch.equal(color, color_ref) and torch.equal(radii, radii_ref)
+            assert bh.resident_rows <= bh.B
+    st = bh.stats
+    assert st["evictions"] > 0 and st["retries"] == 0
+    assert st["rows_fetched"] > bh.B
     ids = bh.id_of_slot.long()
     occ = ids >= 0
     assert int(occ.sum()) == bh.resident_rows

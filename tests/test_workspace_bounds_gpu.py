@@ -736,3 +736,64 @@ def test_hier_merge_stays_in_bounds(gpu, Ps, tails):
 
     r = _both_fills(run)
     compare_to_spec(hierarchy.Hierarchy(**r), hierarchy.merge_hierarchies([_trim(s) for s in sources]))
+
+
+# ================================================================================================================
+# 7. budgeted residency
+# ================================================================================================================
+def _resid_cut(rows, n, rng):
+    """A cut of n entries whose distinct needed rows are exactly ``rows``."""
+    ri = rng.permutation(np.concatenate([rows, rng.choice(rows, n - len(rows))])).astype(np.int32)
+    return ri, rng.choice(rows, n).astype(np.int32), rng.choice(np.array([1.0, 0.5], np.float32), n)
+
+
+@pytest.mark.parametrize("M", [1, 9, 16])
+@pytest.mark.parametrize("G,B,n", [(1, 1, 1), (65, 63, 64), (257, 255, 300), (1003, 257, 1000)])
+def test_residency_chain_stays_in_bounds(gpu, G, B, n, M):
+    """hgs_resid_mark -> _evict -> _fetch -> _remap, every device buffer of the four calls between guards: a first frame
+    that fills the budget with rows 0 .. B-1, then one that needs rows G-B .. G-1 -- the last host row into the last
+    free slot, after an eviction wherever the two sets differ.  The caller initialises slot_of, id_of_slot and free_list
+    (include/hgs.h); stamp, counters, the slot arrays, miss_ids, ro and po hold the fill.  Which slot a row gets depends
+    on the order of the miss list and of the free stack, which the header leaves open: results are compared by row id
+    (tests/residency_model.py: by_id), between the fills and with the plain slot cache."""
+    import residency_model as rm
+    from test_residency_kernels_gpu import DeviceCache, HostRows
+    rng = np.random.default_rng(G + M)
+    cuts = [_resid_cut(np.arange(B), n, rng), _resid_cut(np.arange(G - B, G), n, rng)]
+    host_np = rm.pattern_rows(G, M)
+    host = HostRows(host_np)
+
+    def run(fill):
+        bufs = Bufs(gpu, fill)
+        dc = DeviceCache(gpu, G, B, M, host, cap=n, alloc=lambda name, dtype, count: bufs.filled(name, dtype, (count,)))
+        res = []
+        for frame, (ri, pi, w) in enumerate(cuts, start=1):
+            dc.set_cut(ri, pi, w, prefill=False)
+            rc, count = dc.mark(frame)
+            _ok(rc, "hgs_resid_mark")
+            _ok(dc.evict(frame, count), "hgs_resid_evict")
+            _ok(dc.fetch(count, frame), "hgs_resid_fetch")
+            _ok(dc.remap(), "hgs_resid_remap")
+            bufs.check()
+            assert dc.free_top == 0                                # the budget is full to its last slot
+            s = dc.state()
+            rm.check_invariants(s["slot_of"], s["id_of_slot"], s["free_list"], s["free_top"], B)
+            for t, a in ((dc.ri, ri), (dc.pi, pi), (dc.w, w)):
+                assert np.array_equal(t.cpu().numpy().view(np.uint32), a.view(np.uint32)), "an input was modified"
+            res.append(dict(count=count, **{k: torch.from_numpy(v) if isinstance(v, np.ndarray) else v
+                                            for k, v in rm.by_id(s, dc.out(dc.ro), dc.out(dc.po)).items()}))
+        return res
+
+    try:
+        got = _both_fills(run)
+    finally:
+        torch.cuda.synchronize()
+        host.free()
+    model = rm.SlotCache(G, B, M, host_np)
+    for frame, ((ri, pi, w), r) in enumerate(zip(cuts, got), start=1):
+        rc, ro, po, m = model.make_resident(ri, pi, w, frame)
+        assert rc == rm.OK and r["count"] == m == (B if frame == 1 else min(B, G - B))
+        want = rm.by_id(rm.state_of(model), ro, po)
+        for k, v in want.items():
+            assert np.array_equal(np.asarray(r[k]), v), (frame, k)
+        assert np.array_equal(want["ro_ids"], ri) and np.array_equal(want["resident"], np.unique(ri))
