@@ -973,6 +973,287 @@ __global__ __launch_bounds__(kPreBlock) void k8_presum_work_kernel(const uint2* 
   }
 }
 
+// ---- K8a, phase 1: sum the instance partials (one contiguous run per Gaussian, emission order) -------------------------
+// The runs of a wave's 64 Gaussians lie BACK TO BACK in the scratch (emission order = Gaussian order), ~170 records of
+// 40 bytes: the wave streams that range through LDS with all lanes loading (coalesced, a dozen loads per lane in
+// flight) and every lane then sums its own run out of LDS -- in the same order as before, so the sums keep their bits.
+// Round 3 had each lane walk its run in global memory: 2.7 dependent round trips per Gaussian on average, the longest
+// run of the wave for everybody, at 3 waves per SIMD (160 registers) to hide them.
+// Two routes per wave:
+//   * (always in frames of short runs, launch_preprocess_bwd) the wave streams its contiguous range of records through
+//     LDS, each lane sums its own run from there;
+//   * `presummed` and a run of more than kK8LongRun records in the wave: k8_presum_work_kernel left every segment's ten
+//     sums at the segment's start; the other lanes walk their short runs in global memory (the wave's range is mostly
+//     the long run).
+// `st` is the calling wave's stage (kK8StageRec records).  Every lane of the wave calls (out-of-range lanes with n = 0).
+constexpr uint32_t kK8StageRec = 256;                                 // records per wave and pass: 10 KB
+__device__ __forceinline__ void k8_sum_runs(const GeomWs& g, const float* __restrict__ inst, int idx, uint32_t n,
+                                            int presummed, float2* st, double (&s)[10]) {
+  const int lane = threadIdx.x & 63;
+  const unsigned long long long_mask = presummed ? __ballot(n > kK8LongRun) : 0ull;
+  if (long_mask == 0ull) {
+    uint32_t incl = n;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const uint32_t t = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += t;
+    }
+    const uint32_t my0 = incl - n, my1 = incl;                         // this lane's run, in records of the wave's range
+    const uint32_t total = __shfl(incl, 63, 64);
+    if (total) {                                                       // (wave-uniform)
+      const unsigned long long nz = __ballot(n != 0u);
+      const int first = __ffsll((long long)nz) - 1;
+      const uint32_t off_mine = n ? g.offsets[idx] : 0u;
+      const size_t base = (size_t)__shfl(off_mine, first, 64);         // (no instances before the first non-empty lane)
+      for (uint32_t c0 = 0; c0 < total; c0 += kK8StageRec) {
+        const uint32_t cn = min(kK8StageRec, total - c0) * 5u;           // float2 words of this pass
+        const float2* src = reinterpret_cast<const float2*>(inst) + (base + c0) * 5;
+        for (uint32_t t0 = 0; t0 < cn; t0 += 64u * 4u) {               // four loads in flight per lane
+          float2 v[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const uint32_t t = t0 + (uint32_t)j * 64u + (uint32_t)lane;
+            v[j] = src[min(t, cn - 1u)];
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const uint32_t t = t0 + (uint32_t)j * 64u + (uint32_t)lane;
+            if (t < cn) st[t] = v[j];
+          }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const uint32_t k0 = max(my0, c0), k1 = min(my1, c0 + kK8StageRec);
+        for (uint32_t k = k0; k < k1; ++k) {
+          const float2* r = st + (k - c0) * 5u;
+          const float2 v0 = r[0], v1 = r[1], v2 = r[2], v3 = r[3], v4 = r[4];
+          s[0] += v0.x; s[1] += v0.y; s[2] += v1.x; s[3] += v1.y;
+          s[4] += v2.x; s[5] += v2.y; s[6] += v3.x; s[7] += v3.y;
+          s[8] += v4.x; s[9] += v4.y;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();                               // (the next pass overwrites the stage)
+      }
+    }
+  } else if (n != 0u) {
+    const size_t off = (size_t)g.offsets[idx];
+    if (n > kK8LongRun) {
+      const uint32_t nseg = k8_nseg(n);
+      for (uint32_t j = 0; j < nseg; ++j) {                              // segment sums, in segment order
+        const double* ps = reinterpret_cast<const double*>(inst + (off + (size_t)j * kK8Seg) * kInstStride);
+#pragma unroll
+        for (int i = 0; i < 10; ++i) s[i] += ps[i];
+      }
+    } else {
+      const float2* ip = reinterpret_cast<const float2*>(inst) + off * 5;
+#pragma unroll 2
+      for (uint32_t k = 0; k < n; ++k) {
+        const float2 v0 = ip[k * 5 + 0], v1 = ip[k * 5 + 1], v2 = ip[k * 5 + 2], v3 = ip[k * 5 + 3], v4 = ip[k * 5 + 4];
+        s[0] += v0.x; s[1] += v0.y; s[2] += v1.x; s[3] += v1.y;
+        s[4] += v2.x; s[5] += v2.y; s[6] += v3.x; s[7] += v3.y;
+        s[8] += v4.x; s[9] += v4.y;
+      }
+    }
+  }
+}
+
+// ---- K8a, phase 2: recompute the forward projection and walk the chain rule back (one visible Gaussian per lane) --------
+// s: the ten sums of the Gaussian's run.  p: its mean, as loaded.  gr: dL/drgb, clamp-masked (K1's flags) for SH colours,
+// the plain sums for precomputed colours.  The gradients arrive zeroed (cov3D_precomp leaves d_scale and d_rot alone).
+// (separate arrays, not a struct: with a struct K8a took 178 registers instead of 158)
+template <bool LOD>
+__device__ __forceinline__ void k8_chain(const hgs_raster_args& a, const GeomWs& g, int idx, const double (&s)[10],
+                                         float (&p)[3], float (&d_mean)[3], float (&d_m2)[3], float& d_op,
+                                         float (&d_scale)[3], float (&d_rot)[4], float (&d_c3)[6], float (&gr)[3]) {
+  CamLds cam;
+  load_camera(a, cam);
+  gr[0] = (float)s[6]; gr[1] = (float)s[7]; gr[2] = (float)s[8];
+  // ---- recompute the forward projection (double chain; clamp decisions from K1's flags) ----
+  const uint32_t flags = g.flags[idx];
+  load_mean<LOD>(a, lod_row_gather<LOD>(a, idx), p);
+  float q[4] = {1.f, 0.f, 0.f, 0.f};
+  float sc[3] = {1.f, 1.f, 1.f};
+  double qnorm = 1.0;
+  ProjD pd;
+  if (a.cov3D_precomp) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) pd.c3[i] = (double)a.cov3D_precomp[(size_t)idx * 6 + i];
+  } else {
+    load_scale_rot<LOD>(a, idx, sc, q, &qnorm);
+    cov3d_from_scale_rot_d(sc, a.scale_modifier, q, pd);
+  }
+  project_gaussian_d(p, cam.vm, cam.pm, a.width, a.height, a.tanfovx, a.tanfovy, (flags & 8u) != 0,
+                     (flags & 16u) != 0, pd);
+
+  const double A = pd.conA, B = pd.conB, C = pd.conC;
+  const double gA = -0.5 * s[2], gB = -s[3], gC = -0.5 * s[4];
+  const double ggx = -(A * s[0] + B * s[1]);
+  const double ggy = -(C * s[1] + B * s[0]);
+  const double dm2x = ggx * 0.5 * (double)a.width, dm2y = ggy * 0.5 * (double)a.height;
+  d_m2[0] = (float)dm2x;
+  d_m2[1] = (float)dm2y;
+  double dmean[3] = {0.0, 0.0, 0.0};
+
+  // screen position -> clip space -> world
+  const double dhx = dm2x * pd.pw, dhy = dm2y * pd.pw;
+  const double dhw = -(dm2x * pd.hx + dm2y * pd.hy) * pd.pw * pd.pw;
+#pragma unroll
+  for (int j = 0; j < 3; ++j)
+    dmean[j] += (double)cam.pm[j * 4 + 0] * dhx + (double)cam.pm[j * 4 + 1] * dhy + (double)cam.pm[j * 4 + 3] * dhw;
+
+  // conic -> 2D covariance
+  const double a2 = pd.a, b2 = pd.b, c2 = pd.c;
+  const double di2 = pd.di * pd.di;
+  const double ga = (-c2 * c2 * gA + b2 * c2 * gB - b2 * b2 * gC) * di2;
+  const double gb = (2.0 * b2 * c2 * gA - (a2 * c2 + b2 * b2) * gB + 2.0 * a2 * b2 * gC) * di2;
+  const double gc = (-b2 * b2 * gA + a2 * b2 * gB - a2 * a2 * gC) * di2;
+  const double hb = 0.5 * gb;
+  // dL/dSigma (full symmetric matrix) = T^T G2 T; the lower triangle is the upper one mirrored, so that Gs is
+  // symmetric to the bit: evaluated on its own it rounds differently, and that antisymmetric rounding noise reaches
+  // the rotation gradient even where the exact one is zero (an isotropic Gaussian, whose rotation cannot matter)
+  double Gs[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = i; j < 3; ++j)
+      Gs[i][j] = Gs[j][i] = pd.T0[i] * (ga * pd.T0[j] + hb * pd.T1[j]) + pd.T1[i] * (hb * pd.T0[j] + gc * pd.T1[j]);
+  d_c3[0] = (float)Gs[0][0];
+  d_c3[1] = (float)(2.0 * Gs[0][1]);
+  d_c3[2] = (float)(2.0 * Gs[0][2]);
+  d_c3[3] = (float)Gs[1][1];
+  d_c3[4] = (float)(2.0 * Gs[1][2]);
+  d_c3[5] = (float)Gs[2][2];
+  // dL/dT = 2 G2 T Sigma = 2 G2 U
+  double dT0[3], dT1[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    dT0[j] = 2.0 * ga * pd.U0[j] + gb * pd.U1[j];
+    dT1[j] = gb * pd.U0[j] + 2.0 * gc * pd.U1[j];
+  }
+  double gJ00 = 0.0, gJ02 = 0.0, gJ11 = 0.0, gJ12 = 0.0;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    gJ00 += dT0[j] * (double)cam.vm[j * 4 + 0];
+    gJ02 += dT0[j] * (double)cam.vm[j * 4 + 2];
+    gJ11 += dT1[j] * (double)cam.vm[j * 4 + 1];
+    gJ12 += dT1[j] * (double)cam.vm[j * 4 + 2];
+  }
+  const double itz = pd.itz, itz2 = itz * itz, itz3 = itz2 * itz;
+  const double g_txc = -pd.fx * itz2 * gJ02;
+  const double g_tyc = -pd.fy * itz2 * gJ12;
+  double g_tz = -pd.fx * itz2 * gJ00 + 2.0 * pd.fx * pd.txc * itz3 * gJ02 - pd.fy * itz2 * gJ11 +
+                2.0 * pd.fy * pd.tyc * itz3 * gJ12;
+  double g_tx = 0.0, g_ty = 0.0;
+  if (flags & 8u) g_tz += g_txc * (pd.txc * itz); else g_tx = g_txc;
+  if (flags & 16u) g_tz += g_tyc * (pd.tyc * itz); else g_ty = g_tyc;
+  // inverse depth
+  g_tz += -s[9] * itz2;
+#pragma unroll
+  for (int j = 0; j < 3; ++j)
+    dmean[j] += (double)cam.vm[j * 4 + 0] * g_tx + (double)cam.vm[j * 4 + 1] * g_ty + (double)cam.vm[j * 4 + 2] * g_tz;
+  d_mean[0] = (float)dmean[0]; d_mean[1] = (float)dmean[1]; d_mean[2] = (float)dmean[2];
+
+  // Sigma -> scale / rotation
+  if (!a.cov3D_precomp) {
+    const double* R = pd.R;
+    const double* sv = pd.s;
+    double dM[3][3];   // dL/dM, M_ik = R_ik s_k ; dL/dM = 2 Gs M
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        double acc = 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) acc += Gs[i][j] * (R[j * 3 + k] * sv[k]);
+        dM[i][k] = 2.0 * acc;
+      }
+    double gR[3][3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      double acc = 0.0;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        acc += R[i * 3 + k] * dM[i][k];
+        gR[i][k] = dM[i][k] * sv[k];
+      }
+      double dsk = (double)a.scale_modifier * acc;
+      if (a.activations & HGS_ACT_SCALE_EXP) dsk *= (double)sc[k];          // d exp(raw) / d raw = exp(raw)
+      d_scale[k] = (float)dsk;
+    }
+    const double r = q[0], x = q[1], y = q[2], z = q[3];
+    double dq[4];
+    dq[0] = 2.0 * (-z * gR[0][1] + y * gR[0][2] + z * gR[1][0] - x * gR[1][2] - y * gR[2][0] + x * gR[2][1]);
+    dq[1] = 2.0 * (y * gR[0][1] + z * gR[0][2] + y * gR[1][0] - 2.0 * x * gR[1][1] - r * gR[1][2] +
+                   z * gR[2][0] + r * gR[2][1] - 2.0 * x * gR[2][2]);
+    dq[2] = 2.0 * (-2.0 * y * gR[0][0] + x * gR[0][1] + r * gR[0][2] + x * gR[1][0] + z * gR[1][2] -
+                   r * gR[2][0] + z * gR[2][1] - 2.0 * y * gR[2][2]);
+    dq[3] = 2.0 * (-2.0 * z * gR[0][0] - r * gR[0][1] + x * gR[0][2] + r * gR[1][0] - 2.0 * z * gR[1][1] +
+                   y * gR[1][2] + x * gR[2][0] + y * gR[2][1]);
+    if (a.activations & HGS_ACT_ROT_NORMALIZE) {     // through q = raw / |raw|: (I - q q^T) / |raw|
+      const double dot = r * dq[0] + x * dq[1] + y * dq[2] + z * dq[3];
+      const double inv = 1.0 / qnorm;
+      dq[0] = (dq[0] - r * dot) * inv; dq[1] = (dq[1] - x * dot) * inv;
+      dq[2] = (dq[2] - y * dot) * inv; dq[3] = (dq[3] - z * dot) * inv;
+    }
+    d_rot[0] = (float)dq[0]; d_rot[1] = (float)dq[1]; d_rot[2] = (float)dq[2]; d_rot[3] = (float)dq[3];
+  }
+
+  // opacity (through the LOD remap)
+  {
+    float dod = 1.0f;
+    double dact = 1.0;
+    const float o_act = load_opacity<LOD>(a, idx, &dact);
+    float o_rec = o_act;      // the opacity K1 put into the record (same functions, same float)
+    if (a.interpolation_weights && a.num_node_kids && !a.lod_per_pixel)
+      o_rec = lod_opacity(o_act, a.interpolation_weights[idx], a.num_node_kids[idx], &dod);
+    // the instance records carry sum X = sum (o G) dL/dalpha; dL/do = sum G dL/dalpha = (sum X) / o.  o <= 0: never
+    // blended, sum X = 0
+    // (exact division, once per Gaussian: rcp_d seeds from v_rcp_f32, which overflows for a denormal opacity -- the
+    // Newton step would then turn 0 x inf into a NaN that poisons the optimizer state)
+    const float sums5 = o_rec > 0.0f ? (float)(s[5] / (double)o_rec) : 0.0f;
+    d_op = a.activations ? (float)((double)sums5 * (double)dod * dact) : sums5 * dod;
+  }
+
+  if (!a.colors_precomp) {
+    if (flags & 1u) gr[0] = 0.f;
+    if (flags & 2u) gr[1] = 0.f;
+    if (flags & 4u) gr[2] = 0.f;
+  }
+}
+
+// One row of every per-Gaussian gradient but dL/dmeans3D (which K8b adds the view-direction term to).
+// accumulate_grads: add to what the buffers hold (gradient accumulation over several views of one optimizer
+// step); dL/dmeans2D (a per-view statistic) and dL/dcolors_precomp (the gradient of a view's colours) are always
+// overwritten
+template <bool ACC>
+__device__ __forceinline__ void k8_store_row(const hgs_raster_grads& out, int idx, const float (&d_m2)[3], float d_op,
+                                             const float (&d_scale)[3], const float (&d_rot)[4], const float (&d_c3)[6],
+                                             const float (&d_col)[3]) {
+  constexpr bool acc = ACC;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) out.dL_dmeans2D[idx * 3 + j] = d_m2[j];
+  out.dL_dopacity[idx] = d_op + (acc ? out.dL_dopacity[idx] : 0.f);
+  if (out.dL_dcolors) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) out.dL_dcolors[idx * 3 + j] = d_col[j];   // per view, like dL/dmeans2D: never accumulated
+  }
+  if (out.dL_dscales) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) out.dL_dscales[idx * 3 + j] = d_scale[j] + (acc ? out.dL_dscales[idx * 3 + j] : 0.f);
+  }
+  if (out.dL_drotations) {
+    float4* dst = reinterpret_cast<float4*>(out.dL_drotations) + idx;
+    float4 v = make_float4(d_rot[0], d_rot[1], d_rot[2], d_rot[3]);
+    if (acc) { const float4 o = *dst; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
+    *dst = v;
+  }
+  if (out.dL_dcov3D) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) out.dL_dcov3D[(size_t)idx * 6 + j] = d_c3[j] + (acc ? out.dL_dcov3D[(size_t)idx * 6 + j] : 0.f);
+  }
+}
+
 template <bool ACC, bool LOD>   // ACC: add into the gradient buffers (accumulation over the views of one optimizer step)
 __global__ __launch_bounds__(kPreBlock) void preprocess_bwd_kernel(hgs_raster_args a, GeomWs g,
                                                                    const float* __restrict__ inst,
@@ -984,94 +1265,12 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_bwd_kernel(hgs_raster_ar
   const bool in_range = idx < a.P;
   const uint32_t n = in_range ? g.tiles_touched[idx] : 0u;   // (out-of-range lanes stay for the wave-wide staging below)
 
-  // ---- sum the instance partials (one contiguous run per Gaussian, emission order) --------------------------------
-  // The runs of a wave's 64 Gaussians lie BACK TO BACK in the scratch (emission order = Gaussian order), ~170 records of
-  // 40 bytes: the wave streams that range through LDS with all lanes loading (coalesced, a dozen loads per lane in
-  // flight) and every lane then sums its own run out of LDS -- in the same order as before, so the sums keep their bits.
-  // Round 3 had each lane walk its run in global memory: 2.7 dependent round trips per Gaussian on average, the longest
-  // run of the wave for everybody, at 3 waves per SIMD (160 registers) to hide them.
   double s[10];
 #pragma unroll
   for (int i = 0; i < 10; ++i) s[i] = 0.0;
   static_assert(kInstStride == 10, "instance record = the ten sums, 40 bytes");
-  // Two routes per wave:
-  //   * (always in frames of short runs, launch_preprocess_bwd) the wave streams its contiguous range of records through
-  //     LDS, each lane sums its own run from there;
-  //   * `presummed` and a run of more than kK8LongRun records in the wave: k8_presum_work_kernel left every segment's ten
-  //     sums at the segment's start; the other lanes walk their short runs in global memory (the wave's range is mostly
-  //     the long run).
-  {
-    constexpr uint32_t kStageRec = 256;                                  // records per wave and pass: 10 KB
-    __shared__ float2 stage[kPreBlock / 64][kStageRec * 5];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long long_mask = presummed ? __ballot(n > kK8LongRun) : 0ull;
-    if (long_mask == 0ull) {
-      uint32_t incl = n;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-      }
-      const uint32_t my0 = incl - n, my1 = incl;                         // this lane's run, in records of the wave's range
-      const uint32_t total = __shfl(incl, 63, 64);
-      if (total) {                                                       // (wave-uniform)
-        const unsigned long long nz = __ballot(n != 0u);
-        const int first = __ffsll((long long)nz) - 1;
-        const uint32_t off_mine = n ? g.offsets[idx] : 0u;
-        const size_t base = (size_t)__shfl(off_mine, first, 64);         // (no instances before the first non-empty lane)
-        float2* st = stage[wave];
-        for (uint32_t c0 = 0; c0 < total; c0 += kStageRec) {
-          const uint32_t cn = min(kStageRec, total - c0) * 5u;           // float2 words of this pass
-          const float2* src = reinterpret_cast<const float2*>(inst) + (base + c0) * 5;
-          for (uint32_t t0 = 0; t0 < cn; t0 += 64u * 4u) {               // four loads in flight per lane
-            float2 v[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              const uint32_t t = t0 + (uint32_t)j * 64u + (uint32_t)lane;
-              v[j] = src[min(t, cn - 1u)];
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              const uint32_t t = t0 + (uint32_t)j * 64u + (uint32_t)lane;
-              if (t < cn) st[t] = v[j];
-            }
-          }
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-          const uint32_t k0 = max(my0, c0), k1 = min(my1, c0 + kStageRec);
-          for (uint32_t k = k0; k < k1; ++k) {
-            const float2* r = st + (k - c0) * 5u;
-            const float2 v0 = r[0], v1 = r[1], v2 = r[2], v3 = r[3], v4 = r[4];
-            s[0] += v0.x; s[1] += v0.y; s[2] += v1.x; s[3] += v1.y;
-            s[4] += v2.x; s[5] += v2.y; s[6] += v3.x; s[7] += v3.y;
-            s[8] += v4.x; s[9] += v4.y;
-          }
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();                               // (the next pass overwrites the stage)
-        }
-      }
-    } else if (n != 0u) {
-      const size_t off = (size_t)g.offsets[idx];
-      if (n > kK8LongRun) {
-        const uint32_t nseg = k8_nseg(n);
-        for (uint32_t j = 0; j < nseg; ++j) {                              // segment sums, in segment order
-          const double* ps = reinterpret_cast<const double*>(inst + (off + (size_t)j * kK8Seg) * kInstStride);
-#pragma unroll
-          for (int i = 0; i < 10; ++i) s[i] += ps[i];
-        }
-      } else {
-        const float2* ip = reinterpret_cast<const float2*>(inst) + off * 5;
-#pragma unroll 2
-        for (uint32_t k = 0; k < n; ++k) {
-          const float2 v0 = ip[k * 5 + 0], v1 = ip[k * 5 + 1], v2 = ip[k * 5 + 2], v3 = ip[k * 5 + 3], v4 = ip[k * 5 + 4];
-          s[0] += v0.x; s[1] += v0.y; s[2] += v1.x; s[3] += v1.y;
-          s[4] += v2.x; s[5] += v2.y; s[6] += v3.x; s[7] += v3.y;
-          s[8] += v4.x; s[9] += v4.y;
-        }
-      }
-    }
-  }
+  __shared__ float2 stage[kPreBlock / 64][kK8StageRec * 5];
+  k8_sum_runs(g, inst, idx, n, presummed, stage[threadIdx.x >> 6], s);
   if constexpr (!LOD) {
     if (!in_range) return;
   }
@@ -1082,170 +1281,15 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_bwd_kernel(hgs_raster_ar
   float d_scale[3] = {0.f, 0.f, 0.f};
   float d_rot[4] = {0.f, 0.f, 0.f, 0.f};
   float d_c3[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float gr[3] = {0.f, 0.f, 0.f};
   float d_col[3] = {0.f, 0.f, 0.f};
-  float sums6 = 0.f, sums7 = 0.f, sums8 = 0.f;
-
-  if (n == 0) {
-    // culled: all-zero gradients (K8b zero-fills dL/dSH)
-  } else {
-    CamLds cam;
-    load_camera(a, cam);
-    sums6 = (float)s[6]; sums7 = (float)s[7]; sums8 = (float)s[8];
-    // ---- recompute the forward projection (double chain; clamp decisions from K1's flags) ----
-    const uint32_t flags = g.flags[idx];
+  if (n != 0) {                              // (culled: all-zero gradients; K8b zero-fills dL/dSH)
     float p[3];
-    load_mean<LOD>(a, lod_row_gather<LOD>(a, idx), p);
-    float q[4] = {1.f, 0.f, 0.f, 0.f};
-    float sc[3] = {1.f, 1.f, 1.f};
-    double qnorm = 1.0;
-    ProjD pd;
-    if (a.cov3D_precomp) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) pd.c3[i] = (double)a.cov3D_precomp[(size_t)idx * 6 + i];
-    } else {
-      load_scale_rot<LOD>(a, idx, sc, q, &qnorm);
-      cov3d_from_scale_rot_d(sc, a.scale_modifier, q, pd);
-    }
-    project_gaussian_d(p, cam.vm, cam.pm, a.width, a.height, a.tanfovx, a.tanfovy, (flags & 8u) != 0,
-                       (flags & 16u) != 0, pd);
-
-    const double A = pd.conA, B = pd.conB, C = pd.conC;
-    const double gA = -0.5 * s[2], gB = -s[3], gC = -0.5 * s[4];
-    const double ggx = -(A * s[0] + B * s[1]);
-    const double ggy = -(C * s[1] + B * s[0]);
-    const double dm2x = ggx * 0.5 * (double)a.width, dm2y = ggy * 0.5 * (double)a.height;
-    d_m2[0] = (float)dm2x;
-    d_m2[1] = (float)dm2y;
-    double dmean[3] = {0.0, 0.0, 0.0};
-
-    // screen position -> clip space -> world
-    const double dhx = dm2x * pd.pw, dhy = dm2y * pd.pw;
-    const double dhw = -(dm2x * pd.hx + dm2y * pd.hy) * pd.pw * pd.pw;
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      dmean[j] += (double)cam.pm[j * 4 + 0] * dhx + (double)cam.pm[j * 4 + 1] * dhy + (double)cam.pm[j * 4 + 3] * dhw;
-
-    // conic -> 2D covariance
-    const double a2 = pd.a, b2 = pd.b, c2 = pd.c;
-    const double di2 = pd.di * pd.di;
-    const double ga = (-c2 * c2 * gA + b2 * c2 * gB - b2 * b2 * gC) * di2;
-    const double gb = (2.0 * b2 * c2 * gA - (a2 * c2 + b2 * b2) * gB + 2.0 * a2 * b2 * gC) * di2;
-    const double gc = (-b2 * b2 * gA + a2 * b2 * gB - a2 * a2 * gC) * di2;
-    const double hb = 0.5 * gb;
-    // dL/dSigma (full symmetric matrix) = T^T G2 T; the lower triangle is the upper one mirrored, so that Gs is
-    // symmetric to the bit: evaluated on its own it rounds differently, and that antisymmetric rounding noise reaches
-    // the rotation gradient even where the exact one is zero (an isotropic Gaussian, whose rotation cannot matter)
-    double Gs[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = i; j < 3; ++j)
-        Gs[i][j] = Gs[j][i] = pd.T0[i] * (ga * pd.T0[j] + hb * pd.T1[j]) + pd.T1[i] * (hb * pd.T0[j] + gc * pd.T1[j]);
-    d_c3[0] = (float)Gs[0][0];
-    d_c3[1] = (float)(2.0 * Gs[0][1]);
-    d_c3[2] = (float)(2.0 * Gs[0][2]);
-    d_c3[3] = (float)Gs[1][1];
-    d_c3[4] = (float)(2.0 * Gs[1][2]);
-    d_c3[5] = (float)Gs[2][2];
-    // dL/dT = 2 G2 T Sigma = 2 G2 U
-    double dT0[3], dT1[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      dT0[j] = 2.0 * ga * pd.U0[j] + gb * pd.U1[j];
-      dT1[j] = gb * pd.U0[j] + 2.0 * gc * pd.U1[j];
-    }
-    double gJ00 = 0.0, gJ02 = 0.0, gJ11 = 0.0, gJ12 = 0.0;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      gJ00 += dT0[j] * (double)cam.vm[j * 4 + 0];
-      gJ02 += dT0[j] * (double)cam.vm[j * 4 + 2];
-      gJ11 += dT1[j] * (double)cam.vm[j * 4 + 1];
-      gJ12 += dT1[j] * (double)cam.vm[j * 4 + 2];
-    }
-    const double itz = pd.itz, itz2 = itz * itz, itz3 = itz2 * itz;
-    const double g_txc = -pd.fx * itz2 * gJ02;
-    const double g_tyc = -pd.fy * itz2 * gJ12;
-    double g_tz = -pd.fx * itz2 * gJ00 + 2.0 * pd.fx * pd.txc * itz3 * gJ02 - pd.fy * itz2 * gJ11 +
-                  2.0 * pd.fy * pd.tyc * itz3 * gJ12;
-    double g_tx = 0.0, g_ty = 0.0;
-    if (flags & 8u) g_tz += g_txc * (pd.txc * itz); else g_tx = g_txc;
-    if (flags & 16u) g_tz += g_tyc * (pd.tyc * itz); else g_ty = g_tyc;
-    // inverse depth
-    g_tz += -s[9] * itz2;
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      dmean[j] += (double)cam.vm[j * 4 + 0] * g_tx + (double)cam.vm[j * 4 + 1] * g_ty + (double)cam.vm[j * 4 + 2] * g_tz;
-    d_mean[0] = (float)dmean[0]; d_mean[1] = (float)dmean[1]; d_mean[2] = (float)dmean[2];
-
-    // Sigma -> scale / rotation
-    if (!a.cov3D_precomp) {
-      const double* R = pd.R;
-      const double* sv = pd.s;
-      double dM[3][3];   // dL/dM, M_ik = R_ik s_k ; dL/dM = 2 Gs M
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          double acc = 0.0;
-#pragma unroll
-          for (int j = 0; j < 3; ++j) acc += Gs[i][j] * (R[j * 3 + k] * sv[k]);
-          dM[i][k] = 2.0 * acc;
-        }
-      double gR[3][3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        double acc = 0.0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          acc += R[i * 3 + k] * dM[i][k];
-          gR[i][k] = dM[i][k] * sv[k];
-        }
-        double dsk = (double)a.scale_modifier * acc;
-        if (a.activations & HGS_ACT_SCALE_EXP) dsk *= (double)sc[k];          // d exp(raw) / d raw = exp(raw)
-        d_scale[k] = (float)dsk;
-      }
-      const double r = q[0], x = q[1], y = q[2], z = q[3];
-      double dq[4];
-      dq[0] = 2.0 * (-z * gR[0][1] + y * gR[0][2] + z * gR[1][0] - x * gR[1][2] - y * gR[2][0] + x * gR[2][1]);
-      dq[1] = 2.0 * (y * gR[0][1] + z * gR[0][2] + y * gR[1][0] - 2.0 * x * gR[1][1] - r * gR[1][2] +
-                     z * gR[2][0] + r * gR[2][1] - 2.0 * x * gR[2][2]);
-      dq[2] = 2.0 * (-2.0 * y * gR[0][0] + x * gR[0][1] + r * gR[0][2] + x * gR[1][0] + z * gR[1][2] -
-                     r * gR[2][0] + z * gR[2][1] - 2.0 * y * gR[2][2]);
-      dq[3] = 2.0 * (-2.0 * z * gR[0][0] - r * gR[0][1] + x * gR[0][2] + r * gR[1][0] - 2.0 * z * gR[1][1] +
-                     y * gR[1][2] + x * gR[2][0] + y * gR[2][1]);
-      if (a.activations & HGS_ACT_ROT_NORMALIZE) {     // through q = raw / |raw|: (I - q q^T) / |raw|
-        const double dot = r * dq[0] + x * dq[1] + y * dq[2] + z * dq[3];
-        const double inv = 1.0 / qnorm;
-        dq[0] = (dq[0] - r * dot) * inv; dq[1] = (dq[1] - x * dot) * inv;
-        dq[2] = (dq[2] - y * dot) * inv; dq[3] = (dq[3] - z * dot) * inv;
-      }
-      d_rot[0] = (float)dq[0]; d_rot[1] = (float)dq[1]; d_rot[2] = (float)dq[2]; d_rot[3] = (float)dq[3];
-    }
-
-    // opacity (through the LOD remap)
-    {
-      float dod = 1.0f;
-      double dact = 1.0;
-      const float o_act = load_opacity<LOD>(a, idx, &dact);
-      float o_rec = o_act;      // the opacity K1 put into the record (same functions, same float)
-      if (a.interpolation_weights && a.num_node_kids && !a.lod_per_pixel)
-        o_rec = lod_opacity(o_act, a.interpolation_weights[idx], a.num_node_kids[idx], &dod);
-      // the instance records carry sum X = sum (o G) dL/dalpha; dL/do = sum G dL/dalpha = (sum X) / o.  o <= 0: never
-      // blended, sum X = 0
-      // (exact division, once per Gaussian: rcp_d seeds from v_rcp_f32, which overflows for a denormal opacity -- the
-      // Newton step would then turn 0 x inf into a NaN that poisons the optimizer state)
-      const float sums5 = o_rec > 0.0f ? (float)(s[5] / (double)o_rec) : 0.0f;
-      d_op = a.activations ? (float)((double)sums5 * (double)dod * dact) : sums5 * dod;
-    }
-
+    k8_chain<LOD>(a, g, idx, s, p, d_mean, d_m2, d_op, d_scale, d_rot, d_c3, gr);
     // colour: precomputed colours get their gradient here; SH colours hand the clamp-masked dL/drgb to K8b
-    float gr[3] = {sums6, sums7, sums8};
     if (a.colors_precomp) {
       d_col[0] = gr[0]; d_col[1] = gr[1]; d_col[2] = gr[2];
     } else {
-      if (flags & 1u) gr[0] = 0.f;
-      if (flags & 2u) gr[1] = 0.f;
-      if (flags & 4u) gr[2] = 0.f;
       drgb[idx * 3 + 0] = gr[0];
       drgb[idx * 3 + 1] = gr[1];
       drgb[idx * 3 + 2] = gr[2];
@@ -1320,34 +1364,9 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_bwd_kernel(hgs_raster_ar
     }
     if (!in_range) return;
   }
-  // accumulate_grads: add to what the buffers hold (gradient accumulation over several views of one optimizer
-  // step); dL/dmeans2D (a per-view statistic) and dL/dcolors_precomp (the gradient of a view's colours) are always
-  // overwritten
-  constexpr bool acc = ACC;
 #pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    out.dL_dmeans3D[idx * 3 + j] = d_mean[j] + (acc ? out.dL_dmeans3D[idx * 3 + j] : 0.f);
-    out.dL_dmeans2D[idx * 3 + j] = d_m2[j];
-  }
-  out.dL_dopacity[idx] = d_op + (acc ? out.dL_dopacity[idx] : 0.f);
-  if (out.dL_dcolors) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) out.dL_dcolors[idx * 3 + j] = d_col[j];   // per view, like dL/dmeans2D: never accumulated
-  }
-  if (out.dL_dscales) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) out.dL_dscales[idx * 3 + j] = d_scale[j] + (acc ? out.dL_dscales[idx * 3 + j] : 0.f);
-  }
-  if (out.dL_drotations) {
-    float4* dst = reinterpret_cast<float4*>(out.dL_drotations) + idx;
-    float4 v = make_float4(d_rot[0], d_rot[1], d_rot[2], d_rot[3]);
-    if (acc) { const float4 o = *dst; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
-    *dst = v;
-  }
-  if (out.dL_dcov3D) {
-#pragma unroll
-    for (int j = 0; j < 6; ++j) out.dL_dcov3D[(size_t)idx * 6 + j] = d_c3[j] + (acc ? out.dL_dcov3D[(size_t)idx * 6 + j] : 0.f);
-  }
+  for (int j = 0; j < 3; ++j) out.dL_dmeans3D[idx * 3 + j] = d_mean[j] + (ACC ? out.dL_dmeans3D[idx * 3 + j] : 0.f);
+  k8_store_row<ACC>(out, idx, d_m2, d_op, d_scale, d_rot, d_c3, d_col);
 }
 
 
@@ -1545,6 +1564,108 @@ __global__ __launch_bounds__(kPreBlock) void sh_bwd_kernel(hgs_raster_args a, Ge
     }
     store_sh(out.dL_dshs, idx, a.M, dsh);
   }
+}
+
+// d_mean += the view-direction term of dL/dmean, rounded as preprocess_bwd_kernel<false, false> followed by
+// sh_bwd_kernel<false, true, false> round it: there the compiler contracts  x0 y0 + x1 y1 + x2 y2  into
+// fma(x2, y2, fma(x0, y0, x1 y1)),  g - u dot  into  fma(-u, dot, g),  and K8b's  dL/dmean += v inv  into  fma(v, inv, .)
+// on what K8a stored,  d_mean + 0.f  (a -0.f becomes +0.f).  Written out, with contraction off, so that the fused
+// kernel does not depend on what the compiler makes of the same expressions in other surroundings.
+__device__ __forceinline__ float k8_dot3(float x0, float y0, float x1, float y1, float x2, float y2) {
+#pragma clang fp contract(off)
+  return __fmaf_rn(x2, y2, __fmaf_rn(x0, y0, x1 * y1));
+}
+__device__ __forceinline__ void k8_add_view_term(const float (&gr)[3], const float (&J)[9], float ux, float uy, float uz,
+                                                 float inv, float (&d_mean)[3]) {
+#pragma clang fp contract(off)
+  const float gdx = k8_dot3(gr[0], J[0], gr[1], J[1], gr[2], J[2]);
+  const float gdy = k8_dot3(gr[0], J[3], gr[1], J[4], gr[2], J[5]);
+  const float gdz = k8_dot3(gr[0], J[6], gr[1], J[7], gr[2], J[8]);
+  const float dot = k8_dot3(ux, gdx, uy, gdy, uz, gdz);       // through the normalisation dir = d/|d|
+  d_mean[0] = __fmaf_rn(__fmaf_rn(-ux, dot, gdx), inv, d_mean[0] + 0.f);
+  d_mean[1] = __fmaf_rn(__fmaf_rn(-uy, dot, gdy), inv, d_mean[1] + 0.f);
+  d_mean[2] = __fmaf_rn(__fmaf_rn(-uz, dot, gdz), inv, d_mean[2] + 0.f);
+}
+
+// K8a and K8b in one kernel, for the drop-in training call (launch_preprocess_bwd says when): what
+// preprocess_bwd_kernel<false, false> and sh_bwd_kernel<false, true, false> compute together, to the bit, without the
+// 64 bytes per Gaussian that only pass between the two (drgb out and in, dL/dmeans3D out, in and out again, the mean and
+// tiles_touched a second time) and without the second launch.
+//   phase 1  the run sums (k8_sum_runs); the waves' stages are the first 40 KB of the dynamic buffer
+//   phase 2  the double chain (k8_chain); every gradient but the SH block is stored from registers
+//   phase 3  K8b's JAC body on the mean and the masked dL/drgb still in registers (k8_add_view_term); dL/dmeans3D is
+//            written once; then the buffer becomes the [256][3M + 4] output stage (every lane fills its row from b[] and
+//            dL/drgb: no dsh[48] next to the chain) and the SH block leaves as whole lines (coop_store_sh)
+// 160 registers like K8a (the double chain): three waves per SIMD, which three 53 KB buffers per compute unit also allow.
+// No waves-per-SIMD hint: with its 168-register cap the compiler spills 32 bytes, without it it needs 160 and none.
+__global__ __launch_bounds__(kPreBlock) void preprocess_bwd_sh_kernel(hgs_raster_args a, GeomWs g,
+                                                                         const float* __restrict__ inst,
+                                                                         hgs_raster_grads out, int presummed) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int block_first = blockIdx.x * kPreBlock;
+  const int idx = block_first + threadIdx.x;
+  const bool in_range = idx < a.P;                           // (out-of-range lanes stay: wave-wide staging, barriers)
+  const uint32_t n = in_range ? g.tiles_touched[idx] : 0u;
+
+  double s[10];
+#pragma unroll
+  for (int i = 0; i < 10; ++i) s[i] = 0.0;
+  k8_sum_runs(g, inst, idx, n, presummed, reinterpret_cast<float2*>(smem_raw) + (threadIdx.x >> 6) * (kK8StageRec * 5), s);
+
+  float d_mean[3] = {0.f, 0.f, 0.f};
+  float d_m2[3] = {0.f, 0.f, 0.f};
+  float d_op = 0.f;
+  float d_scale[3] = {0.f, 0.f, 0.f};
+  float d_rot[4] = {0.f, 0.f, 0.f, 0.f};
+  float d_c3[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float gr[3] = {0.f, 0.f, 0.f};                             // clamp-masked dL/drgb
+  float b[16];
+  const int nb = (a.sh_degree + 1) * (a.sh_degree + 1);
+  float p[3];
+  if (n != 0) k8_chain<false>(a, g, idx, s, p, d_mean, d_m2, d_op, d_scale, d_rot, d_c3, gr);
+  if (in_range) {
+    const float d_col[3] = {0.f, 0.f, 0.f};
+    k8_store_row<false>(out, idx, d_m2, d_op, d_scale, d_rot, d_c3, d_col);
+  }
+  __builtin_amdgcn_sched_barrier(0);                         // (phase 3's loads stay out of the double chain's registers)
+  if (n != 0) {
+    float ux, uy, uz;
+    const float inv = unit_dir(p, a.campos, ux, uy, uz);
+    sh_basis(a.sh_degree, ux, uy, uz, b);
+    const float* jp = g.shjac + (size_t)idx * kJacStride;
+    float J[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) J[k] = jp[k];
+    k8_add_view_term(gr, J, ux, uy, uz, inv, d_mean);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) d_mean[j] = 0.f;             // (culled: K8a stores 0, K8b leaves it)
+  }
+  if (in_range) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) out.dL_dmeans3D[idx * 3 + j] = d_mean[j];
+  }
+
+  float* lds = reinterpret_cast<float*>(smem_raw);
+  const int nc = a.M * 3, stride = sh_row_stride(nc);
+  __syncthreads();                                           // (every wave has summed its runs: the stages are dead)
+  if (in_range) {
+    float* row = lds + threadIdx.x * stride;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+      if (i * 4 < nc) {
+        float v[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int k = (i * 4 + c) / 3, ch = (i * 4 + c) % 3;
+          v[c] = (n != 0 && k < nb) ? b[k] * gr[ch] : 0.f;     // (culled rows and the degrees above sh_degree: zeros)
+        }
+        *reinterpret_cast<float4*>(row + i * 4) = make_float4(v[0], v[1], v[2], v[3]);
+      }
+    }
+  }
+  __syncthreads();
+  coop_store_sh<false>(out.dL_dshs, block_first, a.P, nc, lds);
 }
 
 // K8b for several views of the same Gaussians at once (hgs_raster_sh_bwd_batched): the SH block is read once and
@@ -1872,6 +1993,19 @@ int launch_preprocess_bwd(const hgs_raster_args& a, const GeomWs& g, const float
       hipLaunchKernelGGL(k8_presum_work_kernel, dim3(want < 1 ? 1 : (want < kPresumGrid ? want : kPresumGrid)), dim3(kPreBlock), 0,
                          s, work, work_counter, g.tiles_touched, g.offsets, const_cast<float*>(inst_grads));
       HGS_LAUNCH_CHECK("preprocess_bwd_long_runs", s, a.debug);
+    }
+    // the drop-in training call: K8a and K8b as one kernel (HGS_K8_FUSE=0 keeps them apart; read on every call)
+    const char* fuse_env = getenv("HGS_K8_FUSE");
+    const bool fused = !(fuse_env && fuse_env[0] == '0') && !a.lod_render_indices && !a.accumulate_grads &&
+                       !a.defer_sh_bwd && a.shs && !a.shs_rest && out.dL_dshs && a.prepare_backward && !a.colors_precomp &&
+                       ((a.M * 3) & 3) == 0;
+    if (fused) {                       // one dynamic LDS buffer: the four waves' run stages, then the output stage
+      const size_t stage_bytes = (size_t)(kPreBlock / 64) * kK8StageRec * 5 * sizeof(float2);
+      const size_t rows_bytes = (size_t)kPreBlock * (a.M * 3 + 4) * sizeof(float);
+      hipLaunchKernelGGL(preprocess_bwd_sh_kernel, dim3(nblk), dim3(kPreBlock),
+                         stage_bytes > rows_bytes ? stage_bytes : rows_bytes, s, a, g, inst_grads, out, presum ? 1 : 0);
+      HGS_LAUNCH_CHECK("preprocess_bwd_sh", s, a.debug);
+      return HGS_OK;
     }
     auto k8a = a.lod_render_indices ? preprocess_bwd_kernel<false, true>      // (accumulation is refused with lod, abi.cpp)
                                     : (a.accumulate_grads ? preprocess_bwd_kernel<true, false> : preprocess_bwd_kernel<false, false>);
