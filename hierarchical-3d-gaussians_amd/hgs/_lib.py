@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libhgs.so")
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 INST_GRAD_STRIDE = 10          # floats per (tile, Gaussian) record of the backward scratch (HGS_INST_GRAD_STRIDE)
 ERR_CAPACITY = 5
 
@@ -173,6 +173,11 @@ SIGNATURES = {
     "hgs_hier_boxes_nested": (C.c_int, [_P, _P, C.c_int32, _P, C.POINTER(C.c_int32), _P, C.c_int]),
     "hgs_interp_weights": (C.c_int, [_P, C.c_int32, C.c_float, _P, _P, C.c_int32, C.POINTER(C.c_float),
                                      C.POINTER(C.c_float), _P, _P, _P, C.c_int]),
+    "hgs_hier_cull_bounds": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int]),
+    "hgs_lod_cut_view_tmp_bytes": (C.c_size_t, [C.c_int32]),
+    "hgs_lod_cut_view": (C.c_int, [_P, _P, _P, C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                   C.c_float, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, _P, C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int32), _P, C.c_int]),
     "hgs_lod_gather": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int]),
     "hgs_lod_gather_bwd": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                      _P, _P, C.c_int]),

@@ -1,0 +1,164 @@
+"""Frustum-culled hierarchy cut (opt-in; csrc/lod_frustum.hip, include/hgs.h "Frustum-culled cut").
+
+``gaussian_hierarchy._C.expand_to_size`` selects by granularity only: a camera inside a scene gets the cut of the whole
+sphere around it.  Here every node carries a view-independent ball around its own rows, and an entry is dropped when one
+of five widened frustum planes has both the node's ball and its parent's outside -- a rule under which nothing the
+rasterizer would draw is lost::
+
+    bounds = cull_bounds(nodes, means3D, scales)                        # once per hierarchy (activated scales)
+    planes, rs = frustum_planes(cam.world_view_transform, tanfovx, tanfovy, W, H)
+    cut = cut_view(nodes, boxes, bounds, tau, cam.camera_center, planes, rs)
+    # cut.render_indices / parent_indices / weights / kids go to GaussianRasterizationSettings as the outputs of
+    # expand_to_size + get_interpolation_weights do
+
+The kept entries are exactly those of the unculled cut, in its order, with its parents, weights and sibling counts."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib
+
+NEAR_Z = 0.2        # the rasterizer's near cull (view z)
+_K1_CLAMP = 1.3     # the rasterizer's clamp on t.x / t.z, in units of tanfov
+_PAD_PX = 36.0      # the widened plane leaves (fov_scale - 1) W / 2 >= 18 px for dilation, ceil and tile rounding
+
+
+@dataclass
+class CutView:
+    """One culled cut.  The tensors are views of the output buffers (``out``, or freshly allocated ones)."""
+    n: int                          # kept entries
+    n_unculled: int                 # entries of the cut without the cull (what expand_to_size returns)
+    render_indices: torch.Tensor    # int32 [n]
+    parent_indices: torch.Tensor    # int32 [n]
+    node_indices: torch.Tensor      # int32 [n]
+    weights: torch.Tensor           # f32 [n]
+    kids: torch.Tensor              # int32 [n]
+
+
+class CutBuffers:
+    """Preallocated outputs of ``cut_view`` (``out=``): ri, pi, ni (int32), w (float32), ns (int32), ``cap`` entries each.
+    Any object with these five attributes will do."""
+
+    def __init__(self, cap, device):
+        i32 = dict(dtype=torch.int32, device=device)
+        self.ri = torch.zeros(cap, **i32); self.pi = torch.zeros(cap, **i32); self.ni = torch.zeros(cap, **i32)
+        self.w = torch.zeros(cap, dtype=torch.float32, device=device)
+        self.ns = torch.zeros(cap, **i32)
+
+
+def frustum_planes(world_view_transform, tanfovx, tanfovy, width, height, scale_modifier=1.0, near=NEAR_Z):
+    """-> (planes float32 CPU [5,4], radius_scale).  Row k = (a, d), |a| = 1, a . x + d >= 0 inside: the left, right,
+    -y and +y side planes through the camera centre at tangents ``fov_scale * tanfov`` with
+    ``fov_scale = max(1.3, 1 + 36 / min(width, height))``, then the near plane view z = ``near``.  Built in double from
+    the stored (row-vector) ``world_view_transform`` (view = [x 1] @ M), rounded once.
+    ``radius_scale = max(1, scale_modifier) * sqrt((1 + 1.69 (tx^2 + ty^2)) / (1 + 1.69 min(tx, ty)^2))``."""
+    M = np.asarray(torch.as_tensor(world_view_transform).detach().to("cpu", torch.float64).numpy()).reshape(4, 4)
+    tx, ty = float(tanfovx), float(tanfovy)
+    if not (tx > 0.0 and ty > 0.0 and int(width) > 0 and int(height) > 0):
+        raise ValueError("frustum_planes: tanfovx, tanfovy, width and height must be positive")
+    fov_scale = max(_K1_CLAMP, 1.0 + _PAD_PX / min(int(width), int(height)))
+    wx, wy = fov_scale * tx, fov_scale * ty
+    rows = (((1.0, 0.0, wx), 0.0), ((-1.0, 0.0, wx), 0.0), ((0.0, 1.0, wy), 0.0), ((0.0, -1.0, wy), 0.0),
+            ((0.0, 0.0, 1.0), -float(near)))
+    planes = np.zeros((5, 4), dtype=np.float64)
+    for k, (nv, d0) in enumerate(rows):
+        a = [sum(M[i, j] * nv[j] for j in range(3)) for i in range(3)]
+        d = sum(M[3, j] * nv[j] for j in range(3)) + d0
+        ln = math.sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2])
+        if not ln > 0.0:
+            raise ValueError("frustum_planes: degenerate world_view_transform")
+        planes[k] = (a[0] / ln, a[1] / ln, a[2] / ln, d / ln)
+    k2 = _K1_CLAMP * _K1_CLAMP
+    kappa = math.sqrt((1.0 + k2 * (tx * tx + ty * ty)) / (1.0 + k2 * min(tx, ty) ** 2))
+    return torch.from_numpy(planes.astype(np.float32)), max(1.0, float(scale_modifier)) * kappa
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _need(t, name, dtype, shape_ok, what):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError(f"{name} must be a GPU tensor")
+    if t.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype}, not {t.dtype}")
+    if not shape_ok(t):
+        raise ValueError(f"{name} must be {what}, not {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def cull_bounds(nodes, means3D, scales) -> torch.Tensor:
+    """float32 [N,4] = (centre, radius) of every node's own rows: the mean of the rows' means and
+    max_i(|m_i - c| + 3 max_k s_i,k) on ACTIVATED ``scales``.  View independent; rebuild it when the rows change."""
+    _need(nodes, "nodes", torch.int32, lambda t: t.dim() == 2 and t.shape[1] == 7, "[N,7]")
+    G = int(means3D.shape[0]) if torch.is_tensor(means3D) and means3D.dim() >= 1 else 0
+    _need(means3D, "means3D", torch.float32, lambda t: t.dim() == 2 and t.shape[1] == 3, "[G,3]")
+    _need(scales, "scales", torch.float32, lambda t: t.dim() == 2 and tuple(t.shape) == (G, 3), "[G,3]")
+    dev = nodes.device
+    if means3D.device != dev or scales.device != dev:
+        raise ValueError("nodes, means3D and scales must live on one device")
+    N = int(nodes.shape[0])
+    bounds = torch.empty(N, 4, dtype=torch.float32, device=dev)
+    p = _lib.ptr
+    _lib.check(_lib.lib().hgs_hier_cull_bounds(p(nodes), N, p(means3D), p(scales), G, p(bounds), _stream(dev),
+                                               dev.index or 0), "hgs_hier_cull_bounds")
+    return bounds
+
+
+def _host_floats(t, n, name):
+    v = t.detach().to("cpu", torch.float32).reshape(-1) if torch.is_tensor(t) else torch.tensor(t, dtype=torch.float32).reshape(-1)
+    if v.numel() != n:
+        raise ValueError(f"{name} must hold {n} values, not {v.numel()}")
+    return (C.c_float * n)(*[float(x) for x in v])
+
+
+def cut_view(nodes, boxes, bounds, tau, viewpoint, planes, radius_scale, out=None, nested=None) -> CutView:
+    """The LOD cut at granularity ``tau`` from ``viewpoint`` minus the entries outside ``planes`` (``frustum_planes``),
+    with the kept entries' weights and sibling counts: ``expand_to_size`` + ``get_interpolation_weights`` + the cull in
+    one call.  ``viewpoint`` (3 values) and ``planes`` ([5,4]) are read on the host -- pass CPU tensors in a frame loop.
+    ``out``: preallocated buffers (``CutBuffers``) -- a cut that does not fit them raises ``_lib.HgsError`` naming the
+    count; without it the outputs are allocated to fit.  ``nested``: force the single-pass (True) or level-by-level
+    (False) route; default: single pass when the boxes nest, as ``expand_to_size`` decides."""
+    _need(nodes, "nodes", torch.int32, lambda t: t.dim() == 2 and t.shape[1] == 7, "[N,7]")
+    N = int(nodes.shape[0])
+    _need(boxes, "boxes", torch.float32, lambda t: t.numel() == N * 8, "[N,2,4]")
+    _need(bounds, "bounds", torch.float32, lambda t: t.dim() == 2 and tuple(t.shape) == (N, 4), "[N,4]")
+    dev = nodes.device
+    if boxes.device != dev or bounds.device != dev:
+        raise ValueError("nodes, boxes and bounds must live on one device")
+    if torch.is_tensor(planes) and tuple(planes.shape) != (5, 4):
+        raise ValueError(f"planes must be [5,4], not {tuple(planes.shape)}")
+    pl = _host_floats(planes, 20, "planes")
+    vp = _host_floats(viewpoint, 3, "viewpoint")
+    own = out is None
+    bufs = CutBuffers(max(N, 1), dev) if own else out
+    for name, dtype in (("ri", torch.int32), ("pi", torch.int32), ("ni", torch.int32), ("w", torch.float32),
+                        ("ns", torch.int32)):
+        _need(getattr(bufs, name), f"out.{name}", dtype, lambda t: t.dim() == 1, "one-dimensional")
+        if getattr(bufs, name).device != dev:
+            raise ValueError(f"out.{name} must live on the hierarchy's device")
+    lib = _lib.lib()
+    if nested is None:
+        from gaussian_hierarchy._C import _boxes_nested
+        nested = N > 0 and _boxes_nested(nodes, boxes)
+    tmp = torch.empty(lib.hgs_lod_cut_view_tmp_bytes(N), dtype=torch.uint8, device=dev)
+    p = _lib.ptr
+    for attempt in range(2):
+        cap = min(t.numel() for t in (bufs.ri, bufs.pi, bufs.ni, bufs.w, bufs.ns))
+        n, n_all = C.c_int32(0), C.c_int32(0)
+        rc = lib.hgs_lod_cut_view(p(nodes), p(boxes), p(bounds), N, float(tau), vp, pl, float(radius_scale),
+                                  1 if nested else 0, p(bufs.ri), p(bufs.pi), p(bufs.ni), p(bufs.w), p(bufs.ns), cap,
+                                  p(tmp), C.byref(n), C.byref(n_all), _stream(dev), dev.index or 0)
+        if rc != 0 and own and attempt == 0 and n.value > cap:      # nodes of several rows: allocate what it takes
+            bufs = CutBuffers(int(n.value), dev)
+            continue
+        _lib.check(rc, "hgs_lod_cut_view")
+        break
+    k = int(n.value)
+    return CutView(k, int(n_all.value), bufs.ri[:k], bufs.pi[:k], bufs.ni[:k], bufs.w[:k], bufs.ns[:k])

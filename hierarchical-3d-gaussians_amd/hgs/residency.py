@@ -26,7 +26,11 @@ The rasterizer's in-op LOD path runs on the slot arrays unchanged: rows are rows
 ``prefetch(nodes, boxes, tau, next_viewpoint_gpu, next_viewpoint_cpu)``, called once the CURRENT view's render has been
 enqueued, runs the NEXT view's cut, weights and residency on a second stream while the render occupies the first: the rows
 a camera jump needs (1.4 M rows = 360 MB over PCIe in the 50 M-node fly-through) cross the bus under the previous frame
-instead of in front of the next one, and ``select`` for that viewpoint reuses the prefetched cut."""
+instead of in front of the next one, and ``select`` for that viewpoint reuses the prefetched cut.
+
+``select(..., frustum=(planes, radius_scale))`` / ``prefetch(..., frustum=...)`` (the pair of hgs.frustum.frustum_planes): the
+cut, every retry of the regulator and the prefetch drop the entries the view cannot draw (hgs.frustum.cut_view), so rows
+beside and behind the camera are neither fetched nor held and the budget goes to a finer cut of what is in view."""
 from __future__ import annotations
 
 import ctypes as C
@@ -128,11 +132,12 @@ class BudgetedHierarchy:
         self._side = None               # the prefetch stream (created on first use)
         self._resid_done = None         # event: the residency kernels of the last select are enqueued (before its render)
         self._prefetch_done = None      # event: the last prefetch has finished on the side stream
-        self._prefetched = None         # (viewpoint key, tau, n) of the cut waiting in the other buffer set
+        self._prefetched = None         # (viewpoint + frustum key, tau, t, (n, culled)) of the cut waiting in the other buffer set
         self._regulated = None          # granularity the previous view was coarsened to (None: the request fitted)
         self._skip_batch = 0            # evictions left that skip the batch attempt (it failed recently)
         self._since_probe, self.probe_every = 0, 16
-        self.stats = dict(views=0, rows_fetched=0, bytes_fetched=0, evictions=0, retries=0)
+        self.stats = dict(views=0, rows_fetched=0, bytes_fetched=0, evictions=0, retries=0, entries_culled=0)
+        self._bounds = None             # (key of the node list, float32 [N,4] culling balls): built on first frustum use
         self.profile_fetch = False      # True: (rows, start event, end event) of every fetch launch -> self.fetch_events
         self.fetch_events = []
         self._slot_rows = _lib.ResidRows(*[C.c_void_p(t.data_ptr()) for t in
@@ -277,8 +282,32 @@ class BudgetedHierarchy:
         return ro_buf[:n], po_buf[:n], m
 
     @staticmethod
-    def _vp_key(viewpoint_cpu):
-        return tuple(float(x) for x in viewpoint_cpu.reshape(-1)[:3])
+    def _vp_key(viewpoint_cpu, frustum=None):
+        key = tuple(float(x) for x in viewpoint_cpu.reshape(-1)[:3])
+        if frustum is not None:         # a prefetched cut is only reused under the frustum it was culled with
+            key += tuple(float(x) for x in torch.as_tensor(frustum[0]).reshape(-1)) + (float(frustum[1]),)
+        return key
+
+    def _cull_bounds(self, nodes):
+        """The culling balls of ``nodes`` (hgs.frustum.cull_bounds) from the constructor's arrays: computed once, on the
+        first use of a frustum; the means and scales are uploaded for that one launch and freed."""
+        key = (nodes.data_ptr(), int(nodes.shape[0]), nodes._version)
+        if self._bounds is None or self._bounds[0] != key:
+            from .frustum import cull_bounds
+            means = torch.from_numpy(np.ascontiguousarray(self._rows[:, 52:55])).to(self.dev)
+            scales = torch.from_numpy(np.ascontiguousarray(self._rows[:, 55:58])).to(self.dev)
+            self._bounds = (key, cull_bounds(nodes, means, scales))
+            del means, scales
+        return self._bounds[1]
+
+    def _cut(self, nodes, boxes, t, viewpoint_gpu, viewpoint_cpu, bufs, frustum):
+        """One cut at ``t`` into ``bufs``: (entries, entries the frustum dropped, are the weights already in bufs?)."""
+        if frustum is None:
+            from gaussian_hierarchy._C import expand_to_size
+            return expand_to_size(nodes, boxes, t, viewpoint_gpu, torch.zeros(3), bufs.ri, bufs.pi, bufs.ni), 0, False
+        from .frustum import cut_view
+        cv = cut_view(nodes, boxes, self._cull_bounds(nodes), t, viewpoint_cpu, frustum[0], frustum[1], out=bufs)
+        return cv.n, cv.n_unculled - cv.n, True
 
     def _join_prefetch(self):
         """The current stream waits for a prefetch in flight (it owns slot_of / stamp / the free list until it is done)."""
@@ -303,20 +332,22 @@ class BudgetedHierarchy:
         return t, probing
 
     def _fit(self, nodes, boxes, tau, t, probing, viewpoint_gpu, viewpoint_cpu, bufs, new_frame, max_attempts, growth,
-             fine_growth, reuse_n=None):
+             fine_growth, reuse_n=None, frustum=None):
         """Cut + weights + residency into ``bufs``, coarsening until the rows fit: (n, t, ro, po, rows fetched, attempts).
-        ``reuse_n``: the cut and its weights at ``t`` are already in ``bufs`` (a prefetch left them)."""
-        from gaussian_hierarchy._C import expand_to_size, get_interpolation_weights
+        ``reuse_n``: the cut and its weights at ``t`` are already in ``bufs`` (a prefetch left them): (entries, culled).
+        ``frustum``: the (planes, radius_scale) pair of hgs.frustum.frustum_planes -- every cut is then a ``cut_view``."""
+        from gaussian_hierarchy._C import get_interpolation_weights
         zero3 = torch.zeros(3)
         for attempt in range(1, max_attempts + 1):
             reuse = attempt == 1 and reuse_n is not None
-            n = reuse_n if reuse else expand_to_size(nodes, boxes, t, viewpoint_gpu, zero3, bufs.ri, bufs.pi, bufs.ni)
+            n, culled, weighted = (reuse_n[0], reuse_n[1], True) if reuse else \
+                self._cut(nodes, boxes, t, viewpoint_gpu, viewpoint_cpu, bufs, frustum)
             near = n <= 1.1 * self.B
             try:
                 if n > self.B:          # more node rows than slots: no need to look at them
                     raise _lib.HgsError(f"a cut of {n} entries cannot fit a budget of {self.B} rows", _lib.ERR_CAPACITY)
                 # the weights first: an entry of weight 1 does not need its parent row (make_resident)
-                if not reuse:
+                if not weighted:
                     get_interpolation_weights(bufs.ni[:n], t, nodes, boxes, viewpoint_cpu, zero3, bufs.w, bufs.ns)
                 ro, po, m = self.make_resident(bufs.ri[:n], bufs.pi[:n], bufs.w, _bufs=bufs, _new_frame=new_frame)
             except _lib.HgsError as e:
@@ -330,18 +361,22 @@ class BudgetedHierarchy:
             if probing and attempt == 1:
                 self.probe_every = 16
             self._regulated = t if t > float(tau) else None
+            self.stats["entries_culled"] += culled
             return n, t, ro, po, m, attempt
         raise RuntimeError(f"no granularity up to tau = {t:g} fits a budget of {self.B} rows")
 
-    def prefetch(self, nodes, boxes, tau, viewpoint_gpu, viewpoint_cpu) -> int:
+    def prefetch(self, nodes, boxes, tau, viewpoint_gpu, viewpoint_cpu, frustum=None) -> int:
         """The NEXT view's cut, weights and residency on a second stream, to be called right after the current view's
         render was enqueued (its pose known or predicted: a viewer extrapolates its camera).  BEST EFFORT: rows the
         current view uses are never evicted (they carry the current frame's stamp; so do the rows fetched here), nothing
         the render reads is written -- free slots and slots of older frames are filled, the other set of cut buffers
         receives the indices -- and no granularity is changed.  When everything the next view needs became resident,
         ``select`` for the same viewpoint and request starts from this cut (its mark pass only stamps the rows); otherwise
-        it finds that many fewer rows missing.  Returns the rows fetched."""
-        from gaussian_hierarchy._C import expand_to_size, get_interpolation_weights
+        it finds that many fewer rows missing.  ``frustum``: the NEXT view's (planes, radius_scale) pair; ``select`` reuses
+        the cut only when it is given the same one.  Returns the rows fetched."""
+        from gaussian_hierarchy._C import get_interpolation_weights
+        if frustum is not None:
+            self._cull_bounds(nodes)    # (a first use builds the balls on the current stream, before the side stream waits)
         if self._side is None:
             self._side = torch.cuda.Stream(device=self.dev)
         side, zero3 = self._side, torch.zeros(3)
@@ -356,13 +391,14 @@ class BudgetedHierarchy:
         m = 0
         with torch.cuda.stream(side):
             try:
-                n = expand_to_size(nodes, boxes, t, viewpoint_gpu, zero3, other.ri, other.pi, other.ni)
+                n, culled, weighted = self._cut(nodes, boxes, t, viewpoint_gpu, viewpoint_cpu, other, frustum)
                 if n <= self.B:
-                    get_interpolation_weights(other.ni[:n], t, nodes, boxes, viewpoint_cpu, zero3, other.w, other.ns)
+                    if not weighted:
+                        get_interpolation_weights(other.ni[:n], t, nodes, boxes, viewpoint_cpu, zero3, other.w, other.ns)
                     ro, _, m = self.make_resident(other.ri[:n], other.pi[:n], other.w, _bufs=other, _new_frame=False,
                                                   _best_effort=True)
                     if ro is not None:
-                        self._prefetched = (self._vp_key(viewpoint_cpu), float(tau), t, n)
+                        self._prefetched = (self._vp_key(viewpoint_cpu, frustum), float(tau), t, (n, culled))
                     self.stats["prefetched_rows"] = self.stats.get("prefetched_rows", 0) + m
             finally:
                 self._prefetch_done = torch.cuda.Event()
@@ -370,20 +406,23 @@ class BudgetedHierarchy:
         return m
 
     def select(self, nodes, boxes, tau, viewpoint_gpu, viewpoint_cpu, max_attempts: int = 96, growth: float = 1.2,
-               fine_growth: float = 1.05) -> Selection:
+               fine_growth: float = 1.05, frustum=None) -> Selection:
         """expand_to_size + get_interpolation_weights at ``tau`` (train_post.py:91-113, render_hierarchy.py:58-80), the
         cut's rows made resident; a cut that does not fit the budget is repeated at ``growth`` x tau (from 1e-4 when the
         request was tau = 0: every leaf) -- at ``fine_growth`` x tau once the cut is within a tenth of the budget, so that
-        the regulator settles on the last few per cent of it."""
+        the regulator settles on the last few per cent of it.  ``frustum``: the view's (planes, radius_scale) pair of
+        hgs.frustum.frustum_planes -- the cut and every retry of the regulator then drop the entries outside it
+        (hgs.frustum.cut_view: the kept entries are those of the plain cut, unchanged), ``stats["entries_culled"]`` counts
+        them, and rows no view looks at are neither fetched nor held."""
         self._join_prefetch()
         pre, self._prefetched = self._prefetched, None
         (t, probing), reuse_n = self._start_tau(tau, fine_growth), None
-        if not probing and pre is not None and pre[0] == self._vp_key(viewpoint_cpu) and pre[1] == float(tau) and pre[2] == t:
+        if not probing and pre is not None and pre[0] == self._vp_key(viewpoint_cpu, frustum) and pre[1] == float(tau) and pre[2] == t:
             self._cur = 1 - self._cur   # the cut and its weights are waiting in the other buffer set
             reuse_n = pre[3]
         bufs = self._sets[self._cur]
         n, t, ro, po, m, attempt = self._fit(nodes, boxes, tau, t, probing, viewpoint_gpu, viewpoint_cpu, bufs, True,
-                                             max_attempts, growth, fine_growth, reuse_n)
+                                             max_attempts, growth, fine_growth, reuse_n, frustum)
         self.stats["views"] += 1
         self._resid_done = torch.cuda.Event()
         self._resid_done.record(torch.cuda.current_stream(self.dev))

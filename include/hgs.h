@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define HGS_ABI_VERSION 10
+#define HGS_ABI_VERSION 11
 #define HGS_TILE 16
 #define HGS_INST_GRAD_STRIDE 10 /* floats per (tile, Gaussian) instance in the backward scratch (40 bytes: the ten sums) */
 
@@ -317,6 +317,36 @@ int hgs_interp_weights(const int32_t* node_indices, int32_t n, float size, const
                        const float* boxes, int32_t N, const float viewpoint[3], const float viewdir[3],
                        float* interpolation_weights, int32_t* num_siblings,
                        hgs_stream_t stream, int device);
+
+/* ---------------------------------------------------------------------------
+ * Frustum-culled cut (ABI 11; opt-in: the calls above are unchanged).  The cut above, minus the entries that a view
+ * cannot draw, with the weights and sibling counts of the kept entries, in one call.
+ *   Bound of node n: a ball (c_n, R_n) around its own rows [start, start + count_leafs + count_merged): c_n = the mean
+ *   of the rows' means, R_n = max_i(|m_i - c_n| + 3 max_k s_i,k) on ACTIVATED scales; bounds f32 [N,4] = (c, R); a node
+ *   without rows gets R = +inf.  View independent: rebuilt only when the rows change (one launch).
+ *   Planes: f32 [5,4] HOST values, rows (a, d) with |a| = 1 and a.x + d >= 0 inside: the four side planes through the
+ *   camera centre at tangents fov_scale * tanfov, fov_scale = max(1.3, 1 + 36 / min(W, H)) (1.3: the rasterizer's clamp
+ *   on t.x / t.z), and the near plane view z = 0.2 (the rasterizer's cull).
+ *   radius_scale = max(1, scale_modifier) * sqrt((1 + 1.69 (tx^2 + ty^2)) / (1 + 1.69 min(tx, ty)^2)), tx, ty = tanfov.
+ *   Cull: an entry of node n with parent p (the root: p = n) is dropped iff for some plane k BOTH
+ *   a_k.c_n + d_k + radius_scale R_n < 0 and a_k.c_p + d_k + radius_scale R_p < 0 (float32, left to right, no
+ *   contraction).  The weight plays no part.  The kept entries keep their order, parents, weights, sibling counts.
+ * ------------------------------------------------------------------------- */
+/* bounds[N,4] from the node list and the [G,3] means / activated scales (device).  A node whose rows leave [0, G) is an
+ * error (HGS_ERR_INVALID, the node is named); host sync.  The word that check reports through is allocated and freed
+ * inside the call (4 bytes; a bounds build happens once per hierarchy), so the call takes no workspace. */
+int hgs_hier_cull_bounds(const int32_t* nodes, int32_t N, const float* means, const float* scales, int32_t G,
+                         float* bounds, hgs_stream_t stream, int device);
+size_t hgs_lod_cut_view_tmp_bytes(int32_t N);
+/* nested != 0: the single-pass route (precondition: hgs_hier_boxes_nested), else level by level.  The five outputs hold
+ * `capacity` entries each; *count_out_host = kept entries, *unculled_out_host = what hgs_expand_to_size would have
+ * returned (one host sync).  More kept entries than `capacity`: HGS_ERR_INVALID, the message and *count_out_host give
+ * the count, nothing is written past the capacity.  N <= 0: no entries, no GPU work. */
+int hgs_lod_cut_view(const int32_t* nodes, const float* boxes, const float* bounds, int32_t N, float size,
+                     const float viewpoint[3], const float planes[20], float radius_scale, int32_t nested,
+                     int32_t* render_indices, int32_t* parent_indices, int32_t* nodes_for_render_indices,
+                     float* weights, int32_t* num_siblings, int32_t capacity, void* tmp, int32_t* count_out_host,
+                     int32_t* unculled_out_host, hgs_stream_t stream, int device);
 
 /* In-op LOD attribute interpolation: the gather + lerp that render_post does in Python
  * (gaussian_renderer/__init__.py:199-218), for callers that pass GaussianRasterizationSettings.render_indices /
