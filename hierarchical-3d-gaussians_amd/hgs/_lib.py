@@ -12,9 +12,10 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libhgs.so")
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 INST_GRAD_STRIDE = 10          # floats per (tile, Gaussian) record of the backward scratch (HGS_INST_GRAD_STRIDE)
 ERR_CAPACITY = 5
+CUT_COST_ENTRIES, CUT_COST_ROWS = 0, 1
 
 
 class RasterArgs(C.Structure):
@@ -178,6 +179,11 @@ SIGNATURES = {
     "hgs_lod_cut_view": (C.c_int, [_P, _P, _P, C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                    C.c_float, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, _P, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int32), _P, C.c_int]),
+    "hgs_lod_cut_budget_tmp_bytes": (C.c_size_t, [C.c_int32]),
+    "hgs_lod_cut_budget": (C.c_int, [_P, _P, _P, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_float),
+                                     C.POINTER(C.c_float), C.c_float, _P, _P, _P, _P, _P, C.c_int32, _P,
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                     C.POINTER(C.c_int32), _P, C.c_int]),
     "hgs_lod_gather": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int]),
     "hgs_lod_gather_bwd": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                      _P, _P, C.c_int]),

@@ -11,7 +11,14 @@ rasterizer would draw is lost::
     # cut.render_indices / parent_indices / weights / kids go to GaussianRasterizationSettings as the outputs of
     # expand_to_size + get_interpolation_weights do
 
-The kept entries are exactly those of the unculled cut, in its order, with its parents, weights and sibling counts."""
+The kept entries are exactly those of the unculled cut, in its order, with its parents, weights and sibling counts.
+
+``cut_to_budget`` (csrc/lod_budget.hip, include/hgs.h "Budget-exact cut") is the same cut at the finest granularity
+``tau* >= tau_min`` whose cost -- entries, or the rows a budgeted viewer has to hold -- is at most ``budget``: one call,
+no trial cuts::
+
+    bc = cut_to_budget(nodes, boxes, bounds, budget_rows, cam.camera_center, planes, rs, tau_min=tau)
+    # bc.tau is what was rendered, bc.cost <= budget_rows; the other fields are those of cut_view at bc.tau"""
 from __future__ import annotations
 
 import ctypes as C
@@ -162,3 +169,81 @@ def cut_view(nodes, boxes, bounds, tau, viewpoint, planes, radius_scale, out=Non
         break
     k = int(n.value)
     return CutView(k, int(n_all.value), bufs.ri[:k], bufs.pi[:k], bufs.ni[:k], bufs.w[:k], bufs.ns[:k])
+
+
+@dataclass
+class BudgetCut(CutView):
+    """A ``CutView`` at the granularity ``cut_to_budget`` chose."""
+    tau: float = 0.0                # tau*: exactly a float32 value
+    cost: int = 0                   # the cost of the cut at tau* under the requested cost (<= budget)
+
+
+_COSTS = {"entries": _lib.CUT_COST_ENTRIES, "rows": _lib.CUT_COST_ROWS}
+
+
+def cut_to_budget(nodes, boxes, bounds, budget, viewpoint, planes=None, radius_scale=1.0, tau_min=0.0, cost="rows",
+                  out=None) -> BudgetCut:
+    """The cut at the finest granularity ``tau* >= tau_min`` that costs at most ``budget``, with weights and sibling
+    counts -- what ``cut_view`` returns at ``tau*``, bit for bit -- and ``tau*`` itself, in one call (no trial cuts, one
+    host wait).  ``cost``: "entries" (the length of the cut) or "rows" (the entries plus the distinct parent rows that
+    entries of weight < 1 read: what ``BudgetedHierarchy.make_resident`` has to hold).  ``tau*`` is ``tau_min`` when the
+    request fits; otherwise the result of the radix descent of include/hgs.h: ``cost(tau*) <= budget`` while the next
+    float32 below costs more -- the smallest fitting granularity wherever the cost does not rise with tau (always for
+    "entries" without planes).  ``bounds`` and ``planes`` are both given (the frustum cull of ``cut_view``) or both
+    None.  The boxes must nest (every hierarchy this package builds or merges); a budget below the cost of the coarsest
+    cut raises ``_lib.HgsError`` with code ``ERR_CAPACITY`` naming that cost, and nothing is written.  ``out``:
+    preallocated buffers of at least ``budget`` entries (``CutBuffers``)."""
+    _need(nodes, "nodes", torch.int32, lambda t: t.dim() == 2 and t.shape[1] == 7, "[N,7]")
+    N = int(nodes.shape[0])
+    _need(boxes, "boxes", torch.float32, lambda t: t.numel() == N * 8, "[N,2,4]")
+    dev = nodes.device
+    if boxes.device != dev:
+        raise ValueError("nodes and boxes must live on one device")
+    if (bounds is None) != (planes is None):
+        raise ValueError("bounds and planes go together: give both or neither")
+    pl = None
+    if bounds is not None:
+        _need(bounds, "bounds", torch.float32, lambda t: t.dim() == 2 and tuple(t.shape) == (N, 4), "[N,4]")
+        if bounds.device != dev:
+            raise ValueError("nodes, boxes and bounds must live on one device")
+        if torch.is_tensor(planes) and tuple(planes.shape) != (5, 4):
+            raise ValueError(f"planes must be [5,4], not {tuple(planes.shape)}")
+        pl = _host_floats(planes, 20, "planes")
+    vp = _host_floats(viewpoint, 3, "viewpoint")
+    if cost not in _COSTS:
+        raise ValueError(f"cost must be 'entries' or 'rows', not {cost!r}")
+    if N < 1:
+        raise ValueError("an empty hierarchy has no cut")
+    budget, tau_min = int(budget), float(tau_min)
+    if budget < 0 or budget > 2 ** 31 - 1:
+        raise ValueError(f"budget must be in [0, 2^31), not {budget}")
+    if not tau_min >= 0.0:
+        raise ValueError(f"tau_min must be >= 0, not {tau_min}")
+    from gaussian_hierarchy._C import _boxes_nested
+    if not _boxes_nested(nodes, boxes):
+        raise ValueError("cut_to_budget needs a hierarchy whose boxes nest (every child's box inside its parent's): "
+                         "these do not -- use cut_view / BudgetedHierarchy.select(fit='regulate')")
+    if out is None:
+        # no cut costs more than every row plus every node: a larger budget asks for the same cut
+        rows = int((nodes[:, 3].long() + nodes[:, 4].long()).clamp(min=0).sum()) + N
+        budget = min(budget, rows)
+        bufs = CutBuffers(max(budget, 1), dev)
+    else:
+        bufs = out
+    for name, dtype in (("ri", torch.int32), ("pi", torch.int32), ("ni", torch.int32), ("w", torch.float32),
+                        ("ns", torch.int32)):
+        _need(getattr(bufs, name), f"out.{name}", dtype, lambda t: t.dim() == 1, "one-dimensional")
+        if getattr(bufs, name).device != dev:
+            raise ValueError(f"out.{name} must live on the hierarchy's device")
+    lib = _lib.lib()
+    tmp = torch.empty(lib.hgs_lod_cut_budget_tmp_bytes(N), dtype=torch.uint8, device=dev)
+    p = _lib.ptr
+    cap = min(t.numel() for t in (bufs.ri, bufs.pi, bufs.ni, bufs.w, bufs.ns))
+    n, n_all, tau, cst = C.c_int32(0), C.c_int32(0), C.c_float(0.0), C.c_int32(0)
+    _lib.check(lib.hgs_lod_cut_budget(p(nodes), p(boxes), p(bounds), N, tau_min, budget, _COSTS[cost], vp, pl,
+                                      float(radius_scale), p(bufs.ri), p(bufs.pi), p(bufs.ni), p(bufs.w), p(bufs.ns),
+                                      cap, p(tmp), C.byref(n), C.byref(n_all), C.byref(tau), C.byref(cst), _stream(dev),
+                                      dev.index or 0), "hgs_lod_cut_budget")
+    k = int(n.value)
+    return BudgetCut(k, int(n_all.value), bufs.ri[:k], bufs.pi[:k], bufs.ni[:k], bufs.w[:k], bufs.ns[:k],
+                     float(tau.value), int(cst.value))

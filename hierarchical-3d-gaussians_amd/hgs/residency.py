@@ -30,7 +30,13 @@ instead of in front of the next one, and ``select`` for that viewpoint reuses th
 
 ``select(..., frustum=(planes, radius_scale))`` / ``prefetch(..., frustum=...)`` (the pair of hgs.frustum.frustum_planes): the
 cut, every retry of the regulator and the prefetch drop the entries the view cannot draw (hgs.frustum.cut_view), so rows
-beside and behind the camera are neither fetched nor held and the budget goes to a finer cut of what is in view."""
+beside and behind the camera are neither fetched nor held and the budget goes to a finer cut of what is in view.
+
+``select(..., fit="budget")`` / ``prefetch(..., fit="budget")`` replace the regulator's search by ONE
+``hgs.frustum.cut_to_budget(tau_min=tau, budget=B, cost="rows")``: the finest granularity at or above the request whose
+rows fit the budget is selected on the device from the node sizes ("Budget-exact cut"), so
+``make_resident`` runs once, nothing is retried and ``Selection.tau`` does not depend on the views before.  It needs a
+hierarchy whose boxes nest; the default ``fit="regulate"`` is the path described above."""
 from __future__ import annotations
 
 import ctypes as C
@@ -78,6 +84,7 @@ class Selection:
     kids: torch.Tensor                  # int32 [>= n]
     misses: int                         # rows fetched for this view
     attempts: int                       # cuts tried (1 = the requested granularity fitted)
+    cost: int = 0                       # fit="budget": rows the cut was counted at (entries + parent rows, <= budget)
 
 
 class BudgetedHierarchy:
@@ -132,7 +139,7 @@ class BudgetedHierarchy:
         self._side = None               # the prefetch stream (created on first use)
         self._resid_done = None         # event: the residency kernels of the last select are enqueued (before its render)
         self._prefetch_done = None      # event: the last prefetch has finished on the side stream
-        self._prefetched = None         # (viewpoint + frustum key, tau, t, (n, culled)) of the cut waiting in the other buffer set
+        self._prefetched = None         # (viewpoint + frustum key, tau, t, (n, culled), fit, cost) of the cut waiting in the other buffer set
         self._regulated = None          # granularity the previous view was coarsened to (None: the request fitted)
         self._skip_batch = 0            # evictions left that skip the batch attempt (it failed recently)
         self._since_probe, self.probe_every = 0, 16
@@ -365,7 +372,21 @@ class BudgetedHierarchy:
             return n, t, ro, po, m, attempt
         raise RuntimeError(f"no granularity up to tau = {t:g} fits a budget of {self.B} rows")
 
-    def prefetch(self, nodes, boxes, tau, viewpoint_gpu, viewpoint_cpu, frustum=None) -> int:
+    def _cut_budget(self, nodes, boxes, tau, viewpoint_cpu, bufs, frustum):
+        """fit="budget": the one cut of a view into ``bufs`` -> hgs.frustum.BudgetCut (its tau is >= ``tau``, its cost
+        <= the budget).  The coarsest cut not fitting raises _lib.HgsError (ERR_CAPACITY)."""
+        from .frustum import cut_to_budget
+        if frustum is None:
+            return cut_to_budget(nodes, boxes, None, self.B, viewpoint_cpu, tau_min=tau, cost="rows", out=bufs)
+        return cut_to_budget(nodes, boxes, self._cull_bounds(nodes), self.B, viewpoint_cpu, frustum[0], frustum[1],
+                             tau_min=tau, cost="rows", out=bufs)
+
+    @staticmethod
+    def _check_fit(fit):
+        if fit not in ("regulate", "budget"):
+            raise ValueError(f"fit must be 'regulate' or 'budget', not {fit!r}")
+
+    def prefetch(self, nodes, boxes, tau, viewpoint_gpu, viewpoint_cpu, frustum=None, fit="regulate") -> int:
         """The NEXT view's cut, weights and residency on a second stream, to be called right after the current view's
         render was enqueued (its pose known or predicted: a viewer extrapolates its camera).  BEST EFFORT: rows the
         current view uses are never evicted (they carry the current frame's stamp; so do the rows fetched here), nothing
@@ -373,8 +394,11 @@ class BudgetedHierarchy:
         receives the indices -- and no granularity is changed.  When everything the next view needs became resident,
         ``select`` for the same viewpoint and request starts from this cut (its mark pass only stamps the rows); otherwise
         it finds that many fewer rows missing.  ``frustum``: the NEXT view's (planes, radius_scale) pair; ``select`` reuses
-        the cut only when it is given the same one.  Returns the rows fetched."""
+        the cut only when it is given the same one.  ``fit="budget"``: the cut is the one ``cut_to_budget`` of
+        ``select(..., fit="budget")`` -- a function of the viewpoint, the frustum and the request alone, so ``select``
+        reuses it under the same three and the same ``fit``.  Returns the rows fetched."""
         from gaussian_hierarchy._C import get_interpolation_weights
+        self._check_fit(fit)
         if frustum is not None:
             self._cull_bounds(nodes)    # (a first use builds the balls on the current stream, before the side stream waits)
         if self._side is None:
@@ -391,6 +415,15 @@ class BudgetedHierarchy:
         m = 0
         with torch.cuda.stream(side):
             try:
+                if fit == "budget":
+                    cut = self._cut_budget(nodes, boxes, float(tau), viewpoint_cpu, other, frustum)
+                    ro, _, m = self.make_resident(other.ri[:cut.n], other.pi[:cut.n], other.w, _bufs=other,
+                                                  _new_frame=False, _best_effort=True)
+                    if ro is not None:
+                        self._prefetched = (self._vp_key(viewpoint_cpu, frustum), float(tau), cut.tau,
+                                            (cut.n, cut.n_unculled - cut.n), fit, cut.cost)
+                    self.stats["prefetched_rows"] = self.stats.get("prefetched_rows", 0) + m
+                    return m
                 n, culled, weighted = self._cut(nodes, boxes, t, viewpoint_gpu, viewpoint_cpu, other, frustum)
                 if n <= self.B:
                     if not weighted:
@@ -398,7 +431,7 @@ class BudgetedHierarchy:
                     ro, _, m = self.make_resident(other.ri[:n], other.pi[:n], other.w, _bufs=other, _new_frame=False,
                                                   _best_effort=True)
                     if ro is not None:
-                        self._prefetched = (self._vp_key(viewpoint_cpu, frustum), float(tau), t, (n, culled))
+                        self._prefetched = (self._vp_key(viewpoint_cpu, frustum), float(tau), t, (n, culled), fit, 0)
                     self.stats["prefetched_rows"] = self.stats.get("prefetched_rows", 0) + m
             finally:
                 self._prefetch_done = torch.cuda.Event()
@@ -406,18 +439,25 @@ class BudgetedHierarchy:
         return m
 
     def select(self, nodes, boxes, tau, viewpoint_gpu, viewpoint_cpu, max_attempts: int = 96, growth: float = 1.2,
-               fine_growth: float = 1.05, frustum=None) -> Selection:
+               fine_growth: float = 1.05, frustum=None, fit="regulate") -> Selection:
         """expand_to_size + get_interpolation_weights at ``tau`` (train_post.py:91-113, render_hierarchy.py:58-80), the
         cut's rows made resident; a cut that does not fit the budget is repeated at ``growth`` x tau (from 1e-4 when the
         request was tau = 0: every leaf) -- at ``fine_growth`` x tau once the cut is within a tenth of the budget, so that
         the regulator settles on the last few per cent of it.  ``frustum``: the view's (planes, radius_scale) pair of
         hgs.frustum.frustum_planes -- the cut and every retry of the regulator then drop the entries outside it
         (hgs.frustum.cut_view: the kept entries are those of the plain cut, unchanged), ``stats["entries_culled"]`` counts
-        them, and rows no view looks at are neither fetched nor held."""
+        them, and rows no view looks at are neither fetched nor held.
+        ``fit="budget"``: no search -- one ``hgs.frustum.cut_to_budget(tau_min=tau, budget=B, cost="rows")`` selects the
+        finest granularity >= ``tau`` whose rows fit (``Selection.tau``; ``tau`` itself when the request fits) and
+        ``make_resident`` runs once: ``attempts`` is 1, nothing is retried, and ``max_attempts``, ``growth``,
+        ``fine_growth`` and the state the regulator keeps between views play no part.  Needs boxes that nest."""
+        self._check_fit(fit)
         self._join_prefetch()
         pre, self._prefetched = self._prefetched, None
+        if fit == "budget":
+            return self._select_budget(nodes, boxes, tau, viewpoint_cpu, frustum, pre)
         (t, probing), reuse_n = self._start_tau(tau, fine_growth), None
-        if not probing and pre is not None and pre[0] == self._vp_key(viewpoint_cpu, frustum) and pre[1] == float(tau) and pre[2] == t:
+        if not probing and pre is not None and pre[4] == fit and pre[0] == self._vp_key(viewpoint_cpu, frustum) and pre[1] == float(tau) and pre[2] == t:
             self._cur = 1 - self._cur   # the cut and its weights are waiting in the other buffer set
             reuse_n = pre[3]
         bufs = self._sets[self._cur]
@@ -427,3 +467,19 @@ class BudgetedHierarchy:
         self._resid_done = torch.cuda.Event()
         self._resid_done.record(torch.cuda.current_stream(self.dev))
         return Selection(n, t, ro, po, bufs.w, bufs.ns, m, attempt)
+
+    def _select_budget(self, nodes, boxes, tau, viewpoint_cpu, frustum, pre) -> Selection:
+        if pre is not None and pre[4] == "budget" and pre[0] == self._vp_key(viewpoint_cpu, frustum) and pre[1] == float(tau):
+            self._cur = 1 - self._cur   # the cut and its weights are waiting in the other buffer set
+            bufs = self._sets[self._cur]
+            t, (n, culled), cost = pre[2], pre[3], pre[5]
+        else:
+            bufs = self._sets[self._cur]
+            cut = self._cut_budget(nodes, boxes, float(tau), viewpoint_cpu, bufs, frustum)
+            t, n, culled, cost = cut.tau, cut.n, cut.n_unculled - cut.n, cut.cost
+        ro, po, m = self.make_resident(bufs.ri[:n], bufs.pi[:n], bufs.w, _bufs=bufs)
+        self.stats["entries_culled"] += culled
+        self.stats["views"] += 1
+        self._resid_done = torch.cuda.Event()
+        self._resid_done.record(torch.cuda.current_stream(self.dev))
+        return Selection(n, t, ro, po, bufs.w, bufs.ns, m, 1, cost)

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define HGS_ABI_VERSION 11
+#define HGS_ABI_VERSION 12
 #define HGS_TILE 16
 #define HGS_INST_GRAD_STRIDE 10 /* floats per (tile, Gaussian) instance in the backward scratch (40 bytes: the ten sums) */
 
@@ -347,6 +347,44 @@ int hgs_lod_cut_view(const int32_t* nodes, const float* boxes, const float* boun
                      int32_t* render_indices, int32_t* parent_indices, int32_t* nodes_for_render_indices,
                      float* weights, int32_t* num_siblings, int32_t capacity, void* tmp, int32_t* count_out_host,
                      int32_t* unculled_out_host, hgs_stream_t stream, int device);
+
+/* ---------------------------------------------------------------------------
+ * Budget-exact cut (ABI 12; opt-in: the calls above are unchanged).  The finest
+ * granularity tau* >= tau_min whose cut costs at most `budget`, and the cut at tau* -- exactly what hgs_lod_cut_view
+ * returns at tau*: entries, order, parents, weights, sibling counts, bit for bit -- in one call with one host wait.
+ * Precondition: the boxes NEST (hgs_hier_boxes_nested); the cost of the cut at tau is then a sum of indicator functions.
+ * With s_n = size(n, v), s_par the parent's (+inf at the root), L / M = count_leafs / count_merged and k_n = 1 unless the
+ * cull above drops the entry of n (planes == NULL: k_n = 1):
+ *   HGS_CUT_COST_ENTRIES  entries(tau) = sum_n k_n ([s_par >= tau] (L + M) - [s_n >= tau] M)
+ *   HGS_CUT_COST_ROWS     rows(tau) = entries(tau) + #{p : s_p / 2 < tau <= s_p and m_p < tau}, m_p = the smallest s_c
+ *                         over p's children c with k_c = 1 and L_c + M_c > 0: the entries plus the distinct parent rows
+ *                         that entries of weight < 1 read (the weight is 1 whenever s_p >= 2 tau) = the rows
+ *                         hgs_resid_mark needs when no node with children owns leaf rows (else an upper bound).
+ * Every comparison is on the float32 sizes as size() gives them; s_p / 2 is exact (sizes are not subnormal in practice).
+ * Write cost(t) for the cost at the tau whose bit pattern is t (non-negative floats order as their bit patterns).
+ *   cost(tau_min) <= budget: tau* = tau_min (the request fits).
+ *   Else a radix descent over t with the invariant cost(lo) > budget >= cost(hi), from lo = bits(tau_min),
+ *   hi = bits(+inf) (cost: the root's kept rows), in THREE digits of 11, 10 and 10 bits (steps 2^20, 2^10, 1): at each
+ *   digit the cost is evaluated at the multiples of the step inside (lo, hi] (hi is one of them), lo moves to the
+ *   highest one whose cost exceeds the budget (stays if none does) and hi to the next one above it; after the last
+ *   digit hi = lo + 1 and tau* = hi.  So cost(tau*) <= budget < cost(prev(tau*)): tau* is locally tight, and the
+ *   smallest fitting granularity wherever the cost does not increase with tau (always for ENTRIES without planes).
+ *   budget < cost(+inf): HGS_ERR_CAPACITY, the message and *cost_out_host give the count, no output is written.
+ * bounds and planes are both given or both NULL.  The five outputs hold `capacity` >= budget entries each.  NULL
+ * pointers, N <= 0, budget < 0, a negative or NaN tau_min, an unknown cost_mode and capacity < budget are refused before
+ * any HIP call.  Node records that point outside the list, sizes that are negative or NaN and (ROWS) a child larger
+ * than its parent from this viewpoint: HGS_ERR_INVALID, no output is written.  All sums are integer: two calls give
+ * the same bits.  *count_out_host = kept entries, *unculled_out_host = entries of the unculled cut at tau*.
+ * ------------------------------------------------------------------------- */
+#define HGS_CUT_COST_ENTRIES 0
+#define HGS_CUT_COST_ROWS 1
+size_t hgs_lod_cut_budget_tmp_bytes(int32_t N);
+int hgs_lod_cut_budget(const int32_t* nodes, const float* boxes, const float* bounds, int32_t N, float tau_min,
+                       int32_t budget, int32_t cost_mode, const float viewpoint[3], const float planes[20],
+                       float radius_scale, int32_t* render_indices, int32_t* parent_indices,
+                       int32_t* nodes_for_render_indices, float* weights, int32_t* num_siblings, int32_t capacity,
+                       void* tmp, int32_t* count_out_host, int32_t* unculled_out_host, float* tau_out_host,
+                       int32_t* cost_out_host, hgs_stream_t stream, int device);
 
 /* In-op LOD attribute interpolation: the gather + lerp that render_post does in Python
  * (gaussian_renderer/__init__.py:199-218), for callers that pass GaussianRasterizationSettings.render_indices /
