@@ -7,30 +7,10 @@
 // proportional to the nodes ABOVE the cut, not to the hierarchy size; the only
 // full-size pass is the flag compaction (4 B per node), which also makes the output
 // order deterministic (ascending node index) despite the atomic frontier appends.
-#include "common.h"
+#include "lod_cut.h"
 
 namespace hgs {
 namespace {
-
-constexpr int kNodeInts = 7;   // depth,parent,start,count_leafs,count_merged,start_children,count_children
-// boxes: 8 floats per node = min.xyz+extent, max.xyz+pad
-constexpr int kMaxLevels = 64;
-constexpr float kFltMax = 3.4028234663852886e38f;
-
-struct Vec3 { float x, y, z; };
-
-__device__ __forceinline__ float node_size(const float* __restrict__ boxes, int n, Vec3 v) {
-#pragma clang fp contract(off)
-  const float4 mn = reinterpret_cast<const float4*>(boxes)[(size_t)n * 2 + 0];
-  const float4 mx = reinterpret_cast<const float4*>(boxes)[(size_t)n * 2 + 1];
-  const float dx = fmaxf(fmaxf(mn.x - v.x, v.x - mx.x), 0.0f);
-  const float dy = fmaxf(fmaxf(mn.y - v.y, v.y - mx.y), 0.0f);
-  const float dz = fmaxf(fmaxf(mn.z - v.z, v.z - mx.z), 0.0f);
-  const float d2 = (dx * dx + dy * dy) + dz * dz;
-  const float dist = sqrtf(d2);
-  const float s = mn.w / dist;
-  return d2 > 0.0f ? s : kFltMax;
-}
 
 __global__ void lod_init_kernel(uint32_t* counts, int32_t* frontier, int N) {
   if (threadIdx.x == 0) {
@@ -51,16 +31,12 @@ __global__ __launch_bounds__(256) void lod_expand_level_kernel(const int32_t* __
     const int n = fin[i];
     const int32_t* nd = nodes + (size_t)n * kNodeInts;
     const int nch = nd[6];
-    const float s = node_size(boxes, n, vp);
-    if (s >= tau) {            // too coarse for this view: only the Gaussians no child stands for, then the children
-      emit_cnt[n] = (uint32_t)nd[3];
-      if (nch > 0) {
-        const uint32_t base = atomicAdd(count_out, (uint32_t)nch);
-        const int c0 = nd[5];
-        for (int k = 0; k < nch; ++k) fout[base + k] = c0 + k;
-      }
-    } else {                   // fine enough (and its parent was not): the node as a whole
-      emit_cnt[n] = (uint32_t)(nd[3] + nd[4]);
+    const bool coarse = node_size(boxes, n, vp) >= tau;
+    emit_cnt[n] = cut_count(true, coarse, nd);      // (on the frontier: its parent was too coarse)
+    if (coarse && nch > 0) {                        // the children are next
+      const uint32_t base = atomicAdd(count_out, (uint32_t)nch);
+      const int c0 = nd[5];
+      for (int k = 0; k < nch; ++k) fout[base + k] = c0 + k;
     }
   }
 }
@@ -73,9 +49,7 @@ __global__ __launch_bounds__(256) void lod_mark_kernel(const int32_t* __restrict
                                                        int N, float tau, Vec3 vp, uint32_t* __restrict__ emit_cnt,
                                                        uint32_t* __restrict__ block_sums,
                                                        unsigned long long* __restrict__ chain) {
-  __shared__ uint32_t wave_tot[4];
-  if (blockIdx.x == 0)
-    for (int t = threadIdx.x; t < scan_chunks(gridDim.x); t += 256) chain[t] = 0ull;
+  clear_scan_chain(chain);
   const int n = blockIdx.x * 256 + threadIdx.x;
   uint32_t cnt = 0;
   if (n < N) {
@@ -87,15 +61,10 @@ __global__ __launch_bounds__(256) void lod_mark_kernel(const int32_t* __restrict
     const float sn = node_size(boxes, n, vp);
     const bool coarse = sn >= tau;
     const bool reached = coarse || par < 0 || node_size(boxes, par, vp) >= tau;
-    if (reached) cnt = coarse ? (uint32_t)nd[3] : (uint32_t)(nd[3] + nd[4]);
+    cnt = cut_count(reached, coarse, nd);
     emit_cnt[n] = cnt;
   }
-  uint32_t v = cnt;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) block_sums[blockIdx.x] = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+  block_totals<1>({cnt}, {block_sums});
 }
 
 // flag[0] = 1 if some node's box is not inside its parent's or has a larger extent (view independent)
@@ -119,16 +88,9 @@ __global__ __launch_bounds__(256) void lod_nested_kernel(const int32_t* __restri
 __global__ __launch_bounds__(256) void lod_block_sums_kernel(const uint32_t* __restrict__ emit_cnt, int N,
                                                              uint32_t* __restrict__ block_sums,
                                                              unsigned long long* __restrict__ chain) {
-  __shared__ uint32_t wave_tot[4];
-  if (blockIdx.x == 0)
-    for (int t = threadIdx.x; t < scan_chunks(gridDim.x); t += 256) chain[t] = 0ull;
+  clear_scan_chain(chain);
   const int i = blockIdx.x * 256 + threadIdx.x;
-  uint32_t v = (i < N) ? emit_cnt[i] : 0u;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) block_sums[blockIdx.x] = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+  block_totals<1>({(i < N) ? emit_cnt[i] : 0u}, {block_sums});
 }
 
 __global__ __launch_bounds__(1024) void lod_scan_sums_kernel(uint32_t* __restrict__ sums, int n,
@@ -143,34 +105,16 @@ __global__ __launch_bounds__(256) void lod_emit_kernel(const int32_t* __restrict
                                                        int32_t* __restrict__ render_indices,
                                                        int32_t* __restrict__ parent_indices,
                                                        int32_t* __restrict__ node_indices, int capacity) {
-  __shared__ uint32_t wave_tot[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = blockIdx.x * 256 + tid;
+  const int n = blockIdx.x * 256 + threadIdx.x;
   const uint32_t cnt = (n < N) ? emit_cnt[n] : 0u;
-  uint32_t inc = cnt;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t t = __shfl_up(inc, off, 64);
-    if (lane >= off) inc += t;
-  }
-  if (lane == 63) wave_tot[wave] = inc;
-  __syncthreads();
-  uint32_t wbase = 0;
-  for (int w = 0; w < wave; ++w) wbase += wave_tot[w];
+  const uint32_t off = block_exclusive_offset(cnt);
   if (cnt == 0) return;
-  const uint32_t pos = block_sums[blockIdx.x] + wbase + inc - cnt;
   const int32_t* nd = nodes + (size_t)n * kNodeInts;
   const int start = nd[2];
   const int par = nd[1];
   const int pstart = par >= 0 ? nodes[(size_t)par * kNodeInts + 2] : -1;
-  for (uint32_t k = 0; k < cnt; ++k) {
-    const uint32_t o = pos + k;
-    if (o < (uint32_t)capacity) {
-      render_indices[o] = start + (int)k;
-      parent_indices[o] = pstart >= 0 ? pstart : start + (int)k;
-      node_indices[o] = n;
-    }
-  }
+  write_entries<false>(block_sums[blockIdx.x] + off, cnt, capacity, n, start, pstart, render_indices, parent_indices,
+                       node_indices);
 }
 
 __global__ __launch_bounds__(256) void lod_weights_kernel(const int32_t* __restrict__ node_indices, int n, float tau,
@@ -178,7 +122,6 @@ __global__ __launch_bounds__(256) void lod_weights_kernel(const int32_t* __restr
                                                           const float* __restrict__ boxes, Vec3 vp,
                                                           float* __restrict__ weights,
                                                           int32_t* __restrict__ num_siblings) {
-#pragma clang fp contract(off)
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const int nd = node_indices[i];
@@ -186,47 +129,46 @@ __global__ __launch_bounds__(256) void lod_weights_kernel(const int32_t* __restr
   float w = 1.0f;
   int kids = 1;
   if (par >= 0) {
-    // restated from the public gaussian-hierarchy source (not vendored in the reference checkout): the transition
-    // runs while the parent's size falls from 2 tau to tau
-    const float two_tau = 2.0f * tau;
-    float sp = node_size(boxes, par, vp);
-    if (sp > two_tau) sp = two_tau;
-    const float sn = node_size(boxes, nd, vp);
+    w = interp_weight(node_size(boxes, par, vp), node_size(boxes, nd, vp), tau);
     kids = nodes[(size_t)par * kNodeInts + 6];
-    const float start = fmaxf(0.5f * sp, sn);
-    const float diff = sp - start;
-    if (diff > 0.0f) {
-      const float tdiff = fmaxf(0.0f, tau - start);
-      w = fmaxf(1.0f - tdiff / diff, 0.0f);
-    }
   }
   weights[i] = w;
   num_siblings[i] = kids;
 }
 
-struct ExpandTmp {
-  uint32_t* emit_cnt;    // [N]
-  int32_t* frontier_a;   // [N]
-  int32_t* frontier_b;   // [N]
-  uint32_t* counts;      // [kMaxLevels + 2]
-  uint32_t* block_sums;  // [nblk + 1]
-  unsigned long long* chain;  // [scan_chunks(nblk)] published chunk totals of the scan (cleared by the kernel before it)
-};
+}  // namespace
 
-inline ExpandTmp carve_expand(void* tmp, int32_t N) {
-  const size_t n = (size_t)(N > 0 ? N : 1);
-  char* p = static_cast<char*>(tmp);
-  ExpandTmp t;
-  t.emit_cnt = carve<uint32_t>(p, n);
-  t.frontier_a = carve<int32_t>(p, n);
-  t.frontier_b = carve<int32_t>(p, n);
-  t.counts = carve<uint32_t>(p, kMaxLevels + 2);
-  t.block_sums = carve<uint32_t>(p, (n + 255) / 256 + 1);
-  t.chain = carve<unsigned long long>(p, (size_t)scan_chunks((n + 255) / 256));
-  return t;
+int launch_level_marking(const int32_t* nodes, const float* boxes, int32_t N, float tau, Vec3 vp, const LevelTmp& t,
+                         hipStream_t s) {
+  HGS_HIP(hipMemsetAsync(t.emit_cnt, 0, (size_t)N * 4, s));
+  HGS_HIP(hipMemsetAsync(t.counts, 0, kCountWords * 4, s));
+  hipLaunchKernelGGL(lod_init_kernel, dim3(1), dim3(64), 0, s, t.counts, t.frontier_a, N);
+  HGS_LAUNCH_CHECK("lod_init", s, false);
+  // Level-synchronous expansion.  The frontier size of a level is only known on the device, so
+  // every level is launched with a grid-stride kernel; the host polls the level counters every
+  // 8 levels to stop early (a hierarchy deeper than kMaxLevels is rejected).
+  int32_t* fin = t.frontier_a;
+  int32_t* fout = t.frontier_b;
+  const int grid = 1024;
+  int level = 0;
+  bool finished = false;
+  while (!finished) {
+    const int stop = level + 8;
+    for (; level < stop && level < kMaxLevels; ++level) {
+      hipLaunchKernelGGL(lod_expand_level_kernel, dim3(grid), dim3(256), 0, s, nodes, boxes, tau, vp, fin,
+                         t.counts + level, fout, t.counts + level + 1, t.emit_cnt);
+      HGS_LAUNCH_CHECK("lod_expand_level", s, false);
+      int32_t* sw = fin; fin = fout; fout = sw;
+    }
+    uint32_t next = 0;
+    HGS_HIP(hipMemcpyAsync(&next, t.counts + level, 4, hipMemcpyDeviceToHost, s));
+    HGS_HIP(wait_stream(s));
+    if (next == 0) finished = true;
+    else if (level >= kMaxLevels) { set_error("hierarchy deeper than %d levels", kMaxLevels); return HGS_ERR_INVALID; }
+  }
+  return HGS_OK;
 }
 
-}  // namespace
 }  // namespace hgs
 
 using namespace hgs;
@@ -234,22 +176,17 @@ using namespace hgs;
 extern "C" {
 
 size_t hgs_expand_tmp_bytes(int32_t N) {
-  const size_t n = (size_t)(N > 0 ? N : 1);
-  return 3 * align_up(n * 4) + align_up((kMaxLevels + 2) * 4) + align_up(((n + 255) / 256 + 1) * 4) +
-         align_up((size_t)scan_chunks((n + 255) / 256) * 8) + kAlign;
+  char* p = nullptr;
+  carve_levels(p, N, false);
+  return carved_bytes(p);
 }
 
-static int expand_finish(const int32_t* nodes, const ExpandTmp& t, int32_t N, int32_t* render_indices,
+static int expand_finish(const int32_t* nodes, const LevelTmp& t, int32_t N, int32_t* render_indices,
                          int32_t* parent_indices, int32_t* nodes_for_render_indices, int32_t capacity,
                          int32_t* count_out_host, hipStream_t s) {
   const int nblk = (N + 255) / 256;
-  // (at most `resident` chunk workgroups per launch: common.h, chained_scan_inplace)
-  const int chunks = scan_chunks(nblk), resident = scan_resident_workgroups();
-  for (int c0 = 0; c0 < chunks; c0 += resident) {
-    hipLaunchKernelGGL(lod_scan_sums_kernel, dim3(min(resident, chunks - c0)), dim3(1024), 0, s, t.block_sums, nblk, t.chain,
-                       c0, chunks);
-    HGS_LAUNCH_CHECK("lod_scan_sums", s, false);
-  }
+  const int rc = launch_scan_chunks(lod_scan_sums_kernel, "lod_scan_sums", nblk, s, t.block_sums, nblk, t.chain);
+  if (rc != HGS_OK) return rc;
   hipLaunchKernelGGL(lod_emit_kernel, dim3(nblk), dim3(256), 0, s, nodes, t.emit_cnt, N, t.block_sums,
                      render_indices, parent_indices, nodes_for_render_indices, capacity);
   HGS_LAUNCH_CHECK("lod_emit", s, false);
@@ -278,34 +215,11 @@ int hgs_expand_to_size(const int32_t* nodes, const float* boxes, int32_t N, floa
   }
   HGS_HIP(hipSetDevice(device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const ExpandTmp t = carve_expand(tmp, N);
+  char* p = static_cast<char*>(tmp);
+  const LevelTmp t = carve_levels(p, N, false);
   const Vec3 vp = {viewpoint[0], viewpoint[1], viewpoint[2]};
-  HGS_HIP(hipMemsetAsync(t.emit_cnt, 0, (size_t)N * 4, s));
-  HGS_HIP(hipMemsetAsync(t.counts, 0, (kMaxLevels + 2) * 4, s));
-  hipLaunchKernelGGL(lod_init_kernel, dim3(1), dim3(64), 0, s, t.counts, t.frontier_a, N);
-  HGS_LAUNCH_CHECK("lod_init", s, false);
-  // Level-synchronous expansion.  The frontier size of a level is only known on the device, so
-  // every level is launched with a grid-stride kernel; the host polls the level counters every
-  // 8 levels to stop early (a hierarchy deeper than kMaxLevels is rejected).
-  int32_t* fin = t.frontier_a;
-  int32_t* fout = t.frontier_b;
-  const int grid = 1024;
-  int level = 0;
-  bool finished = false;
-  while (!finished) {
-    const int stop = level + 8;
-    for (; level < stop && level < kMaxLevels; ++level) {
-      hipLaunchKernelGGL(lod_expand_level_kernel, dim3(grid), dim3(256), 0, s, nodes, boxes, size, vp, fin,
-                         t.counts + level, fout, t.counts + level + 1, t.emit_cnt);
-      HGS_LAUNCH_CHECK("lod_expand_level", s, false);
-      int32_t* sw = fin; fin = fout; fout = sw;
-    }
-    uint32_t next = 0;
-    HGS_HIP(hipMemcpyAsync(&next, t.counts + level, 4, hipMemcpyDeviceToHost, s));
-    HGS_HIP(wait_stream(s));
-    if (next == 0) finished = true;
-    else if (level >= kMaxLevels) { set_error("hierarchy deeper than %d levels", kMaxLevels); return HGS_ERR_INVALID; }
-  }
+  const int rc = launch_level_marking(nodes, boxes, N, size, vp, t, s);
+  if (rc != HGS_OK) return rc;
   const int nblk = (N + 255) / 256;
   hipLaunchKernelGGL(lod_block_sums_kernel, dim3(nblk), dim3(256), 0, s, t.emit_cnt, N, t.block_sums, t.chain);
   HGS_LAUNCH_CHECK("lod_block_sums", s, false);
@@ -326,7 +240,8 @@ int hgs_expand_to_size_nested(const int32_t* nodes, const float* boxes, int32_t 
   }
   HGS_HIP(hipSetDevice(device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const ExpandTmp t = carve_expand(tmp, N);
+  char* p = static_cast<char*>(tmp);
+  const LevelTmp t = carve_levels(p, N, false);
   const Vec3 vp = {viewpoint[0], viewpoint[1], viewpoint[2]};
   hipLaunchKernelGGL(lod_mark_kernel, dim3((N + 255) / 256), dim3(256), 0, s, nodes, boxes, N, size, vp, t.emit_cnt,
                      t.block_sums, t.chain);

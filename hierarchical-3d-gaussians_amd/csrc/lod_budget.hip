@@ -1,5 +1,5 @@
-// Budget-exact hierarchy cut (opt-in, beside hgs_lod_cut_view of lod_frustum.hip, which stays as it is): the finest
-// granularity tau* >= tau_min whose cut costs at most `budget`, and the cut at tau*, in ONE call with one host wait.
+// Budget-exact hierarchy cut (opt-in, beside hgs_lod_cut_view of lod_frustum.hip): the finest granularity
+// tau* >= tau_min whose cut costs at most `budget`, and the cut at tau*, in ONE call with one host wait.
 //
 // The rule (include/hgs.h "Budget-exact cut"; tests/budget_cut_spec.py restates it).  When the
 // boxes nest, the cost of the cut at tau is a sum over nodes of indicator functions of tau.  With s_n = node_size(n),
@@ -17,15 +17,13 @@
 //
 // Layout: size pass (s_n and k_n in 4 bytes per node: the later passes gather 4 bytes instead of a 32-byte box and a
 // 16-byte ball), parent-event pass (rows only), 3 x (histogram, pick), then mark / scan / emit as lod_frustum.hip with
-// tau* read from device memory.  The helpers that file keeps in its anonymous namespace are restated here.
-#include "common.h"
+// tau* read from device memory: the rules and the parts of those passes are lod_cut.h's.
+#include "lod_cut.h"
 #include <string.h>
 
 namespace hgs {
 namespace {
 
-constexpr int kNodeInts = 7;   // depth,parent,start,count_leafs,count_merged,start_children,count_children
-constexpr float kFltMax = 3.4028234663852886e38f;
 constexpr uint32_t kInfBits = 0x7F800000u;
 constexpr uint32_t kKeyMask = 0x7FFFFFFFu;
 constexpr uint32_t kNoEvent = 0xFFFFFFFFu;
@@ -37,43 +35,6 @@ constexpr uint32_t kTauBadInput = 0xFFFFFFFEu;   //                a size that i
 // state words (device memory, behind the histogram)
 enum { S_LO = 0, S_HI, S_COST_HI, S_FIRST, S_DONE, S_FAIL, S_BAD, S_PAD, S_RESULT /* kept, unculled, tau bits, cost */,
        S_WORDS = 12 };
-
-struct Vec3 { float x, y, z; };
-struct Frustum { float4 p[5]; float rs; };
-
-// lod.hip's node_size, restated
-__device__ __forceinline__ float node_size(const float* __restrict__ boxes, int n, Vec3 v) {
-#pragma clang fp contract(off)
-  const float4 mn = reinterpret_cast<const float4*>(boxes)[(size_t)n * 2 + 0];
-  const float4 mx = reinterpret_cast<const float4*>(boxes)[(size_t)n * 2 + 1];
-  const float dx = fmaxf(fmaxf(mn.x - v.x, v.x - mx.x), 0.0f);
-  const float dy = fmaxf(fmaxf(mn.y - v.y, v.y - mx.y), 0.0f);
-  const float dz = fmaxf(fmaxf(mn.z - v.z, v.z - mx.z), 0.0f);
-  const float d2 = (dx * dx + dy * dy) + dz * dz;
-  const float dist = sqrtf(d2);
-  const float s = mn.w / dist;
-  return d2 > 0.0f ? s : kFltMax;
-}
-
-// lod_frustum.hip's ball_outside / entry_culled, restated
-__device__ __forceinline__ bool ball_outside(float4 b, float4 pl, float rs) {
-#pragma clang fp contract(off)
-  const float t = ((pl.x * b.x + pl.y * b.y) + pl.z * b.z) + pl.w;
-  return t + rs * b.w < 0.0f;
-}
-
-__device__ __forceinline__ bool entry_culled(const float4* __restrict__ bounds, int n, int par, const Frustum& f) {
-  const float4 bn = bounds[n];
-  uint32_t out = 0;
-#pragma unroll
-  for (int k = 0; k < 5; ++k) out |= ball_outside(bn, f.p[k], f.rs) ? (1u << k) : 0u;
-  if (out == 0) return false;
-  const float4 bp = bounds[par >= 0 ? par : n];
-  bool both = false;
-#pragma unroll
-  for (int k = 0; k < 5; ++k) both |= ((out >> k) & 1u) && ball_outside(bp, f.p[k], f.rs);
-  return both;
-}
 
 // Size pass, one thread per node: sk[n] = bits(s_n) | k_n << 31.  Its first thread sets the bracket of the descent (the
 // histogram and the other state words were zeroed by the memset in front).  A node record that points outside the node
@@ -289,23 +250,6 @@ __global__ __launch_bounds__(1024) void budget_pick_kernel(uint32_t* __restrict_
   }
 }
 
-// sums of one workgroup's kept and unculled counts -> block_sums[blockIdx.x], block_all[blockIdx.x]
-__device__ __forceinline__ void block_totals(uint32_t kept, uint32_t all, uint32_t* __restrict__ block_sums,
-                                             uint32_t* __restrict__ block_all) {
-  __shared__ uint32_t wave_kept[4], wave_all[4];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    kept += __shfl_xor(kept, off, 64);
-    all += __shfl_xor(all, off, 64);
-  }
-  if ((threadIdx.x & 63) == 0) { wave_kept[threadIdx.x >> 6] = kept; wave_all[threadIdx.x >> 6] = all; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    block_sums[blockIdx.x] = wave_kept[0] + wave_kept[1] + wave_kept[2] + wave_kept[3];
-    block_all[blockIdx.x] = wave_all[0] + wave_all[1] + wave_all[2] + wave_all[3];
-  }
-}
-
 // frustum_mark_kernel on the 4-byte sizes, tau* from device memory; a failed call marks nothing
 __global__ __launch_bounds__(256) void budget_mark_kernel(const int32_t* __restrict__ nodes,
                                                           const uint32_t* __restrict__ sk, int N,
@@ -314,10 +258,7 @@ __global__ __launch_bounds__(256) void budget_mark_kernel(const int32_t* __restr
                                                           uint32_t* __restrict__ block_sums,
                                                           uint32_t* __restrict__ block_all,
                                                           unsigned long long* __restrict__ chain) {
-  if (blockIdx.x == 0) {      // for the scan launch behind this one: its chain, and the unculled total it adds up
-    for (int t = threadIdx.x; t < scan_chunks(gridDim.x); t += 256) chain[t] = 0ull;
-    if (threadIdx.x == 0) block_sums[gridDim.x + 1] = 0u;
-  }
+  clear_scan_chain(chain, block_sums);
   const uint32_t tau_bits = state[S_RESULT + 2];
   const bool ok = tau_bits <= kInfBits;
   const int n = blockIdx.x * 256 + threadIdx.x;
@@ -329,34 +270,18 @@ __global__ __launch_bounds__(256) void budget_mark_kernel(const int32_t* __restr
     // bit patterns of non-negative floats order as the floats do: s >= tau on the integers
     const bool coarse = (w & kKeyMask) >= tau_bits;
     const bool reached = coarse || par < 0 || (sk[par] & kKeyMask) >= tau_bits;
-    if (reached) cnt = coarse ? (uint32_t)nd[3] : (uint32_t)(nd[3] + nd[4]);
+    cnt = cut_count(reached, coarse, nd);
     kept = (w >> 31) ? cnt : 0u;
   }
   if (n < N) emit_cnt[n] = kept;
-  block_totals(kept, cnt, block_sums, block_all);
+  block_totals<2>({kept, cnt}, {block_sums, block_all});
 }
 
-// frustum_scan_sums_kernel, restated
 __global__ __launch_bounds__(1024) void budget_scan_sums_kernel(uint32_t* __restrict__ sums,
                                                                 const uint32_t* __restrict__ block_all, int n,
                                                                 unsigned long long* __restrict__ chain, int c_off,
                                                                 int chunks) {
-  __shared__ uint32_t all_wave[16];
-  const int i0 = ((int)blockIdx.x + c_off) * kScanChunk + (int)threadIdx.x * kScanPer;
-  uint32_t a = 0;
-#pragma unroll
-  for (int k = 0; k < kScanPer; ++k) a += (i0 + k < n) ? block_all[i0 + k] : 0u;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
-  if ((threadIdx.x & 63) == 0) all_wave[threadIdx.x >> 6] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) t += all_wave[w];
-    if (t) atomicAdd(sums + n + 1, t);
-  }
-  (void)chained_scan_inplace(sums, n, chain, c_off, chunks);
+  scan_sums_and_unculled_total(sums, block_all, n, chain, c_off, chunks);
 }
 
 // frustum_emit_kernel with the sizes from sk (the very bits node_size gave) and tau* from device memory; its first
@@ -371,28 +296,15 @@ __global__ __launch_bounds__(256) void budget_emit_kernel(const int32_t* __restr
                                                           int32_t* __restrict__ node_indices,
                                                           float* __restrict__ weights,
                                                           int32_t* __restrict__ num_siblings, int capacity) {
-#pragma clang fp contract(off)
-  __shared__ uint32_t wave_tot[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = blockIdx.x * 256 + tid;
+  const int n = blockIdx.x * 256 + threadIdx.x;
   if (n == 0) {
     state[S_RESULT + 0] = block_sums[gridDim.x];
     state[S_RESULT + 1] = block_sums[gridDim.x + 1];
   }
   const uint32_t cnt = (n < N) ? emit_cnt[n] : 0u;
-  uint32_t inc = cnt;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t t = __shfl_up(inc, off, 64);
-    if (lane >= off) inc += t;
-  }
-  if (lane == 63) wave_tot[wave] = inc;
-  __syncthreads();
-  uint32_t wbase = 0;
-  for (int w = 0; w < wave; ++w) wbase += wave_tot[w];
+  const uint32_t off = block_exclusive_offset(cnt);
   if (cnt == 0) return;
   const float tau = __uint_as_float(state[S_RESULT + 2]);
-  const uint32_t pos = block_sums[blockIdx.x] + wbase + inc - cnt;
   const int32_t* nd = nodes + (size_t)n * kNodeInts;
   const int start = nd[2];
   const int par = nd[1];
@@ -401,51 +313,28 @@ __global__ __launch_bounds__(256) void budget_emit_kernel(const int32_t* __restr
   int kids = 1;
   if (par >= 0) {
     pstart = nodes[(size_t)par * kNodeInts + 2];
-    const float two_tau = 2.0f * tau;
-    float sp = __uint_as_float(sk[par] & kKeyMask);
-    if (sp > two_tau) sp = two_tau;
-    const float sn = __uint_as_float(sk[n] & kKeyMask);
+    w = interp_weight(__uint_as_float(sk[par] & kKeyMask), __uint_as_float(sk[n] & kKeyMask), tau);
     kids = nodes[(size_t)par * kNodeInts + 6];
-    const float s0 = fmaxf(0.5f * sp, sn);
-    const float diff = sp - s0;
-    if (diff > 0.0f) {
-      const float tdiff = fmaxf(0.0f, tau - s0);
-      w = fmaxf(1.0f - tdiff / diff, 0.0f);
-    }
   }
-  for (uint32_t k = 0; k < cnt; ++k) {
-    const uint32_t o = pos + k;
-    if (o < (uint32_t)capacity) {
-      render_indices[o] = start + (int)k;
-      parent_indices[o] = pstart >= 0 ? pstart : start + (int)k;
-      node_indices[o] = n;
-      weights[o] = w;
-      num_siblings[o] = kids;
-    }
-  }
+  write_entries<true>(block_sums[blockIdx.x] + off, cnt, capacity, n, start, pstart, render_indices, parent_indices,
+                      node_indices, weights, w, num_siblings, kids);
 }
 
-struct BudgetTmp {
+struct BudgetTmp : SumsTmp {
   uint32_t* sk;          // [N] bits(s_n) | k_n << 31
   uint32_t* ev;          // [N] key of the parent's -1 event (cost = rows)
   uint32_t* emit_cnt;    // [N]
-  uint32_t* block_sums;  // [nblk + 2] kept sums, scanned in place; [nblk] = kept total, [nblk + 1] = unculled total
-  uint32_t* block_all;   // [nblk] unculled sums
-  unsigned long long* chain;  // [scan_chunks(nblk)]
   uint32_t* hist;        // [kBins]
   uint32_t* state;       // [S_WORDS]
 };
 
-inline BudgetTmp carve_budget(void* tmp, int32_t N) {
+inline BudgetTmp carve_budget(char*& p, int32_t N) {
   const size_t n = (size_t)(N > 0 ? N : 1);
-  char* p = static_cast<char*>(tmp);
   BudgetTmp t;
   t.sk = carve<uint32_t>(p, n);
   t.ev = carve<uint32_t>(p, n);
   t.emit_cnt = carve<uint32_t>(p, n);
-  t.block_sums = carve<uint32_t>(p, (n + 255) / 256 + 2);
-  t.block_all = carve<uint32_t>(p, (n + 255) / 256);
-  t.chain = carve<unsigned long long>(p, (size_t)scan_chunks((n + 255) / 256));
+  static_cast<SumsTmp&>(t) = carve_sums(p, n, true);
   t.hist = carve<uint32_t>(p, kBins);
   t.state = carve<uint32_t>(p, S_WORDS);
   return t;
@@ -459,9 +348,9 @@ using namespace hgs;
 extern "C" {
 
 size_t hgs_lod_cut_budget_tmp_bytes(int32_t N) {
-  const size_t n = (size_t)(N > 0 ? N : 1);
-  return 3 * align_up(n * 4) + align_up(((n + 255) / 256 + 2) * 4) + align_up(((n + 255) / 256) * 4) +
-         align_up((size_t)scan_chunks((n + 255) / 256) * 8) + align_up(kBins * 4) + align_up(S_WORDS * 4) + kAlign;
+  char* p = nullptr;
+  carve_budget(p, N);
+  return carved_bytes(p);
 }
 
 int hgs_lod_cut_budget(const int32_t* nodes, const float* boxes, const float* bounds, int32_t N, float tau_min,
@@ -500,7 +389,8 @@ int hgs_lod_cut_budget(const int32_t* nodes, const float* boxes, const float* bo
   }
   HGS_HIP(hipSetDevice(device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const BudgetTmp t = carve_budget(tmp, N);
+  char* p = static_cast<char*>(tmp);
+  const BudgetTmp t = carve_budget(p, N);
   const Vec3 vp = {viewpoint[0], viewpoint[1], viewpoint[2]};
   Frustum f;
   for (int k = 0; k < 5; ++k)
@@ -532,12 +422,9 @@ int hgs_lod_cut_budget(const int32_t* nodes, const float* boxes, const float* bo
   hipLaunchKernelGGL(budget_mark_kernel, dim3(nblk), dim3(256), 0, s, nodes, t.sk, N, t.state, t.emit_cnt,
                      t.block_sums, t.block_all, t.chain);
   HGS_LAUNCH_CHECK("budget_mark", s, false);
-  const int chunks = scan_chunks(nblk), resident = scan_resident_workgroups();
-  for (int c0 = 0; c0 < chunks; c0 += resident) {
-    hipLaunchKernelGGL(budget_scan_sums_kernel, dim3(min(resident, chunks - c0)), dim3(1024), 0, s, t.block_sums,
-                       t.block_all, nblk, t.chain, c0, chunks);
-    HGS_LAUNCH_CHECK("budget_scan_sums", s, false);
-  }
+  const int rc = launch_scan_chunks(budget_scan_sums_kernel, "budget_scan_sums", nblk, s, t.block_sums, t.block_all,
+                                    nblk, t.chain);
+  if (rc != HGS_OK) return rc;
   hipLaunchKernelGGL(budget_emit_kernel, dim3(nblk), dim3(256), 0, s, nodes, t.sk, t.emit_cnt, N, t.state,
                      t.block_sums, render_indices, parent_indices, nodes_for_render_indices, weights, num_siblings,
                      capacity);

@@ -125,6 +125,33 @@ def _host_floats(t, n, name):
     return (C.c_float * n)(*[float(x) for x in v])
 
 
+def _check_hierarchy(nodes, boxes, bounds, planes, cull=True):
+    """What cut_view and cut_to_budget ask of their hierarchy -> (N, device, the planes as 20 host floats).  ``cull``
+    False: a cut without the frustum cull, ``bounds`` and ``planes`` are not looked at and the planes come back None."""
+    _need(nodes, "nodes", torch.int32, lambda t: t.dim() == 2 and t.shape[1] == 7, "[N,7]")
+    N = int(nodes.shape[0])
+    _need(boxes, "boxes", torch.float32, lambda t: t.numel() == N * 8, "[N,2,4]")
+    dev = nodes.device
+    if not cull:
+        if boxes.device != dev:
+            raise ValueError("nodes and boxes must live on one device")
+        return N, dev, None
+    _need(bounds, "bounds", torch.float32, lambda t: t.dim() == 2 and tuple(t.shape) == (N, 4), "[N,4]")
+    if boxes.device != dev or bounds.device != dev:
+        raise ValueError("nodes, boxes and bounds must live on one device")
+    if torch.is_tensor(planes) and tuple(planes.shape) != (5, 4):
+        raise ValueError(f"planes must be [5,4], not {tuple(planes.shape)}")
+    return N, dev, _host_floats(planes, 20, "planes")
+
+
+def _check_out(bufs, dev):
+    for name, dtype in (("ri", torch.int32), ("pi", torch.int32), ("ni", torch.int32), ("w", torch.float32),
+                        ("ns", torch.int32)):
+        _need(getattr(bufs, name), f"out.{name}", dtype, lambda t: t.dim() == 1, "one-dimensional")
+        if getattr(bufs, name).device != dev:
+            raise ValueError(f"out.{name} must live on the hierarchy's device")
+
+
 def cut_view(nodes, boxes, bounds, tau, viewpoint, planes, radius_scale, out=None, nested=None) -> CutView:
     """The LOD cut at granularity ``tau`` from ``viewpoint`` minus the entries outside ``planes`` (``frustum_planes``),
     with the kept entries' weights and sibling counts: ``expand_to_size`` + ``get_interpolation_weights`` + the cull in
@@ -132,24 +159,11 @@ def cut_view(nodes, boxes, bounds, tau, viewpoint, planes, radius_scale, out=Non
     ``out``: preallocated buffers (``CutBuffers``) -- a cut that does not fit them raises ``_lib.HgsError`` naming the
     count; without it the outputs are allocated to fit.  ``nested``: force the single-pass (True) or level-by-level
     (False) route; default: single pass when the boxes nest, as ``expand_to_size`` decides."""
-    _need(nodes, "nodes", torch.int32, lambda t: t.dim() == 2 and t.shape[1] == 7, "[N,7]")
-    N = int(nodes.shape[0])
-    _need(boxes, "boxes", torch.float32, lambda t: t.numel() == N * 8, "[N,2,4]")
-    _need(bounds, "bounds", torch.float32, lambda t: t.dim() == 2 and tuple(t.shape) == (N, 4), "[N,4]")
-    dev = nodes.device
-    if boxes.device != dev or bounds.device != dev:
-        raise ValueError("nodes, boxes and bounds must live on one device")
-    if torch.is_tensor(planes) and tuple(planes.shape) != (5, 4):
-        raise ValueError(f"planes must be [5,4], not {tuple(planes.shape)}")
-    pl = _host_floats(planes, 20, "planes")
+    N, dev, pl = _check_hierarchy(nodes, boxes, bounds, planes)
     vp = _host_floats(viewpoint, 3, "viewpoint")
     own = out is None
     bufs = CutBuffers(max(N, 1), dev) if own else out
-    for name, dtype in (("ri", torch.int32), ("pi", torch.int32), ("ni", torch.int32), ("w", torch.float32),
-                        ("ns", torch.int32)):
-        _need(getattr(bufs, name), f"out.{name}", dtype, lambda t: t.dim() == 1, "one-dimensional")
-        if getattr(bufs, name).device != dev:
-            raise ValueError(f"out.{name} must live on the hierarchy's device")
+    _check_out(bufs, dev)
     lib = _lib.lib()
     if nested is None:
         from gaussian_hierarchy._C import _boxes_nested
@@ -193,22 +207,9 @@ def cut_to_budget(nodes, boxes, bounds, budget, viewpoint, planes=None, radius_s
     None.  The boxes must nest (every hierarchy this package builds or merges); a budget below the cost of the coarsest
     cut raises ``_lib.HgsError`` with code ``ERR_CAPACITY`` naming that cost, and nothing is written.  ``out``:
     preallocated buffers of at least ``budget`` entries (``CutBuffers``)."""
-    _need(nodes, "nodes", torch.int32, lambda t: t.dim() == 2 and t.shape[1] == 7, "[N,7]")
-    N = int(nodes.shape[0])
-    _need(boxes, "boxes", torch.float32, lambda t: t.numel() == N * 8, "[N,2,4]")
-    dev = nodes.device
-    if boxes.device != dev:
-        raise ValueError("nodes and boxes must live on one device")
     if (bounds is None) != (planes is None):
         raise ValueError("bounds and planes go together: give both or neither")
-    pl = None
-    if bounds is not None:
-        _need(bounds, "bounds", torch.float32, lambda t: t.dim() == 2 and tuple(t.shape) == (N, 4), "[N,4]")
-        if bounds.device != dev:
-            raise ValueError("nodes, boxes and bounds must live on one device")
-        if torch.is_tensor(planes) and tuple(planes.shape) != (5, 4):
-            raise ValueError(f"planes must be [5,4], not {tuple(planes.shape)}")
-        pl = _host_floats(planes, 20, "planes")
+    N, dev, pl = _check_hierarchy(nodes, boxes, bounds, planes, cull=bounds is not None)
     vp = _host_floats(viewpoint, 3, "viewpoint")
     if cost not in _COSTS:
         raise ValueError(f"cost must be 'entries' or 'rows', not {cost!r}")
@@ -230,11 +231,7 @@ def cut_to_budget(nodes, boxes, bounds, budget, viewpoint, planes=None, radius_s
         bufs = CutBuffers(max(budget, 1), dev)
     else:
         bufs = out
-    for name, dtype in (("ri", torch.int32), ("pi", torch.int32), ("ni", torch.int32), ("w", torch.float32),
-                        ("ns", torch.int32)):
-        _need(getattr(bufs, name), f"out.{name}", dtype, lambda t: t.dim() == 1, "one-dimensional")
-        if getattr(bufs, name).device != dev:
-            raise ValueError(f"out.{name} must live on the hierarchy's device")
+    _check_out(bufs, dev)
     lib = _lib.lib()
     tmp = torch.empty(lib.hgs_lod_cut_budget_tmp_bytes(N), dtype=torch.uint8, device=dev)
     p = _lib.ptr

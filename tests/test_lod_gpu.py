@@ -518,3 +518,65 @@ def test_per_pixel_lod_remap_matches_the_oracle(gpu, do_depth, monkeypatch):
     other = pa.run_hip(scene, cam, bg, gc, gd, gpu, interpolation_weights=w, num_node_kids=kids, do_depth=do_depth,
                        grad_mask=None)
     assert (other["color"] - hip["color"]).abs().max() > 1e-2        # the two readings are different images
+
+
+def _chain(n):
+    """Node k has the single child k + 1 and one row, k: merged at the inner nodes, a leaf row at the last.  Every box
+    is the same box, so the boxes nest and every node has the same size from every viewpoint."""
+    nodes = np.zeros((n, 7), dtype=np.int32)
+    k = np.arange(n)
+    nodes[:, 0], nodes[:, 1], nodes[:, 2] = k, k - 1, k
+    nodes[:-1, 4], nodes[:-1, 5], nodes[:-1, 6] = 1, k[1:], 1
+    nodes[-1, 3] = 1
+    boxes = np.tile(np.array([[-1.0, -1.0, -1.0, 1e3], [1.0, 1.0, 1.0, 0.0]], dtype=np.float32), (n, 1, 1))
+    return nodes, boxes
+
+
+@pytest.mark.parametrize("n", [8, 9, 64, 65])
+def test_level_route_polls_every_8_levels_and_refuses_more_than_64(gpu, n):
+    """The level-by-level route launches 8 levels, then looks at the frontier size: chains of 8, 9 and 64 nodes end at
+    the first poll, need a second one, and end at the last poll the route has.  hgs_expand_to_size and
+    cut_view(nested=False) share that loop and give the oracle's cut; at 65 levels both refuse a cut that has to go
+    all the way down (a clean invalid-argument return), still answer one that stops at the root, and the single-pass
+    routes give the oracle's cut whatever the depth."""
+    import ctypes as C
+    from hgs import _lib, frustum
+    ERR_INVALID = 1                                        # HGS_ERR_INVALID (include/hgs.h)
+    nodes_np, boxes_np = _chain(n)
+    nodes, boxes = torch.from_numpy(nodes_np).to(gpu), torch.from_numpy(boxes_np).to(gpu)
+    bounds = torch.zeros(n, 4, device=gpu)
+    planes = torch.tensor([[0.0, 0.0, 1.0, 1e30]] * 5)     # every ball is inside
+    vp = np.array([0.0, 0.0, 10.0], dtype=np.float32)
+    lib, p = _lib.lib(), _lib.ptr
+    ri = torch.zeros(n, dtype=torch.int32, device=gpu); pi = torch.zeros_like(ri); ni = torch.zeros_like(ri)
+    tmp = torch.empty(lib.hgs_expand_tmp_bytes(n), dtype=torch.uint8, device=gpu)
+    v3 = lambda t: (C.c_float * 3)(*[float(x) for x in t])
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for tau, rows in ((1.0, (n - 1, n - 2)), (1e9, (0, 0))):
+        r_o, p_o, n_o = lo.expand_to_size(nodes_np, boxes_np, tau, vp)
+        w_o, k_o = lo.get_interpolation_weights(n_o, tau, nodes_np, boxes_np, vp)
+        assert (r_o.tolist(), p_o.tolist(), w_o.tolist(), k_o.tolist()) == ([rows[0]], [rows[1]], [1.0], [1])
+        too_deep = n > 64 and tau == 1.0
+        for fn, fails in ((lib.hgs_expand_to_size, too_deep), (lib.hgs_expand_to_size_nested, False)):
+            cnt = C.c_int32(0)
+            ri.fill_(-7); pi.fill_(-7); ni.fill_(-7)
+            rc = fn(p(nodes), p(boxes), n, tau, v3(vp), v3((0, 0, 0)), p(ri), p(pi), p(ni), n, p(tmp), C.byref(cnt),
+                    stream, 0)
+            if fails:
+                assert rc == ERR_INVALID and b"deeper than 64 levels" in lib.hgs_last_error()
+                continue
+            _lib.check(rc, "expand")
+            assert cnt.value == 1
+            assert (ri[:1].tolist(), pi[:1].tolist(), ni[:1].tolist()) == (r_o.tolist(), p_o.tolist(), n_o.tolist())
+        for nested, fails in ((False, too_deep), (True, False)):
+            if fails:
+                with pytest.raises(_lib.HgsError, match="deeper than 64 levels") as e:
+                    frustum.cut_view(nodes, boxes, bounds, tau, vp, planes, 1.0, nested=nested)
+                assert e.value.code == ERR_INVALID
+                continue
+            cv = frustum.cut_view(nodes, boxes, bounds, tau, vp, planes, 1.0, nested=nested)
+            assert (cv.n, cv.n_unculled) == (1, 1)
+            assert (cv.render_indices.tolist(), cv.parent_indices.tolist(), cv.node_indices.tolist()) == \
+                (r_o.tolist(), p_o.tolist(), n_o.tolist())
+            assert np.array_equal(cv.weights.cpu().numpy().view(np.uint32), w_o.view(np.uint32))
+            assert cv.kids.tolist() == k_o.tolist()

@@ -63,3 +63,22 @@ def test_geom_bytes_cover_whole_wave_stores():
         # fall outside the workspace, nor may the Jacobian stores reach the chain
         need = jac + up(ceil64(P) * JAC_BYTES) + up(chain)
         assert geom >= need, f"P={P}: geom_bytes {geom} < {need} (whole-wave Jacobian rows + scan chain)"
+
+
+def test_cut_workspace_sizes_keep_their_closed_forms():
+    """hgs_expand_tmp_bytes, hgs_lod_cut_view_tmp_bytes and hgs_lod_cut_budget_tmp_bytes are answered by the code that
+    carves the workspaces (csrc/lod_cut.h): no byte formula beside the layout can drift from it.  The closed forms
+    below restate the three layouts; the sizes straddle the last partial workgroup of 256 nodes and the first second
+    chunk of the scan (8192 workgroup sums)."""
+    lib = _lib.lib()
+    LEVELS, BINS, STATE = 64 + 2, 2048, 12
+    for N in (0, 1, 255, 256, 257, 256 * SCAN_CHUNK - 1, 256 * SCAN_CHUNK, 256 * SCAN_CHUNK + 1, 50_000_000):
+        n = max(N, 1)
+        nblk = (n + 255) // 256
+        chain = up(((nblk + SCAN_CHUNK - 1) // SCAN_CHUNK) * 8)
+        expand = 3 * up(n * 4) + up(LEVELS * 4) + up((nblk + 1) * 4) + chain + ALIGN
+        view = 3 * up(n * 4) + up(LEVELS * 4) + up((nblk + 2) * 4) + up(nblk * 4) + chain + ALIGN
+        budget = 3 * up(n * 4) + up((nblk + 2) * 4) + up(nblk * 4) + chain + up(BINS * 4) + up(STATE * 4) + ALIGN
+        assert lib.hgs_expand_tmp_bytes(N) == expand, N
+        assert lib.hgs_lod_cut_view_tmp_bytes(N) == view, N
+        assert lib.hgs_lod_cut_budget_tmp_bytes(N) == budget, N
