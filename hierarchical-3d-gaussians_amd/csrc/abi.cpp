@@ -655,6 +655,21 @@ int hgs_hier_merge_root(const hgs_hier_view* merged, int32_t k, hgs_stream_t str
   return launch_hier_merge_root(*merged, k, static_cast<hipStream_t>(stream));
 }
 
+size_t hgs_hier_align_tmp_bytes(int64_t N) {
+  if (N < 1 || N > kHierMergeMaxN) return 0;
+  return hier_align_tmp_bytes(N);
+}
+
+int hgs_hier_align(const int32_t* nodes, int64_t N, float* log_scales, float* rots, void* tmp,
+                   hgs_hier_align_report* report, hgs_stream_t stream, int device) {
+  if (N < 1 || N > kHierMergeMaxN) { set_error("bad sizes: N=%lld not in [1, 2^31 - 1]", (long long)N); return HGS_ERR_INVALID; }
+  if (!nodes || !log_scales || !rots || !tmp || !report) { set_error("null argument"); return HGS_ERR_INVALID; }
+  if ((uintptr_t)rots & 15u) { set_error("rots must be 16-byte aligned"); return HGS_ERR_INVALID; }
+  if ((uintptr_t)tmp & (kAlign - 1)) { set_error("tmp must be %d-byte aligned", (int)kAlign); return HGS_ERR_INVALID; }
+  HGS_HIP(hipSetDevice(device));
+  return launch_hier_align(nodes, N, log_scales, rots, tmp, report, static_cast<hipStream_t>(stream));
+}
+
 size_t hgs_ssim_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W) {
   if (!ssim_sizes_ok(N, C, H, W)) return 0;
   return ssim_tmp_bytes(N, C, H, W);

@@ -308,6 +308,10 @@ int launch_hier_build(const float* xyz, const float* scales, const float* rots, 
 int launch_hier_merge_place(const hgs_hier_view& chunk, int32_t index, int64_t base, const hgs_hier_view& merged,
                             void* tmp, hgs_hier_merge_report* report, hipStream_t s);
 int launch_hier_merge_root(const hgs_hier_view& merged, int32_t k, hipStream_t s);
+// rotation alignment (hier_align.hip): sizes, pointers and alignment checked by the caller (1 <= N <= 2^31 - 1)
+size_t hier_align_tmp_bytes(int64_t N);
+int launch_hier_align(const int32_t* nodes, int64_t N, float* log_scales, float* rots, void* tmp,
+                      hgs_hier_align_report* report, hipStream_t s);
 // fused SSIM loss (ssim.hip): ssim_sizes_ok sets the error message; the launches expect sizes it accepted
 bool ssim_sizes_ok(int32_t N, int32_t C, int32_t H, int32_t W);
 size_t ssim_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W);

@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libhgs.so")
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 INST_GRAD_STRIDE = 10          # floats per (tile, Gaussian) record of the backward scratch (HGS_INST_GRAD_STRIDE)
 ERR_CAPACITY = 5
 CUT_COST_ENTRIES, CUT_COST_ROWS = 0, 1
@@ -69,6 +69,10 @@ class HierMergeReport(C.Structure):
 
 
 HIER_MERGE_TMP_BYTES = 256
+
+
+class HierAlignReport(C.Structure):
+    _fields_ = [("first_bad", C.c_int32 * 4), ("roots", C.c_int32), ("levels", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class ResidRows(C.Structure):
@@ -155,6 +159,8 @@ SIGNATURES = {
     "hgs_hier_merge_place": (C.c_int, [C.POINTER(HierView), C.c_int32, C.c_int32, C.c_int64, C.POINTER(HierView), _P,
                                        C.POINTER(HierMergeReport), _P, C.c_int]),
     "hgs_hier_merge_root": (C.c_int, [C.POINTER(HierView), C.c_int32, _P, C.c_int]),
+    "hgs_hier_align_tmp_bytes": (C.c_size_t, [C.c_int64]),
+    "hgs_hier_align": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.POINTER(HierAlignReport), _P, C.c_int]),
     "hgs_ssim_tmp_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "hgs_ssim_fwd": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int]),
     "hgs_ssim_bwd": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,

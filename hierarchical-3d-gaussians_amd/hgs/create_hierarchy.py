@@ -1,6 +1,6 @@
 """Hierarchy creator: a trained chunk's ``point_cloud.ply`` -> ``<out dir>/hierarchy.hier``.
 
-    python -m hgs.create_hierarchy <point_cloud.ply> <chunk dir> <out dir> [<scaffold dir>]
+    python -m hgs.create_hierarchy [--align] <point_cloud.ply> <chunk dir> <out dir> [<scaffold dir>]
 
 The positional form of the reference's per-chunk creator call (scripts/full_train.py:185-196), so only the executable
 changes; the output is what ``train_post.py --hierarchy`` and ``render_hierarchy.py`` load.  Steps:
@@ -13,6 +13,10 @@ changes; the output is what ``train_post.py --hierarchy`` and ``render_hierarchy
      -- the complement of the reference's "outside the chunk" test (scene/gaussian_model.py:232-235), which drops the
      scaffold ring train_single.py put in front of the chunk's own Gaussians;
   4. build with ``hgs.hierarchy.build_hierarchy_gpu`` and write the upstream .hier layout (write_hierarchy).
+
+``--align`` (opt-in, anywhere among the arguments) runs ``hgs.hierarchy.align_hierarchy_gpu`` between the build and the
+write: every node's rotation and scales re-parametrised to lie close to its parent's frame, the
+Gaussians unchanged.  Without the flag the output is byte for byte what it was before the flag existed.
 
 This project's construction rule, not a restatement of the reference's creator."""
 from __future__ import annotations
@@ -65,11 +69,16 @@ def subset(scene: Scene, rows) -> Scene:
                                                     scene.shs)), scene.sh_degree)
 
 
-def run(ply_path, chunk_dir, out_dir, scaffold_dir=None) -> dict:
-    """Read, select, build, write; -> figures of the run (rows read / kept, N, read / write seconds, build ms from
-    device events)."""
+def split_flags(argv, flags=("--align",)):
+    """-> (the positional arguments in order, the set of ``flags`` present): a flag may stand anywhere."""
+    return [a for a in argv if a not in flags], {a for a in argv if a in flags}
+
+
+def run(ply_path, chunk_dir, out_dir, scaffold_dir=None, align=False) -> dict:
+    """Read, select, build, (align,) write; -> figures of the run (rows read / kept, N, read / write seconds, build ms
+    and, with ``align``, align ms from device events)."""
     from gaussian_hierarchy._C import write_hierarchy
-    from .hierarchy import build_hierarchy_gpu
+    from .hierarchy import align_hierarchy_gpu, build_hierarchy_gpu
     if not torch.cuda.is_available():
         raise RuntimeError("hgs.create_hierarchy builds on the GPU; no GPU is visible")
     t0 = time.perf_counter()
@@ -86,23 +95,27 @@ def run(ply_path, chunk_dir, out_dir, scaffold_dir=None) -> dict:
     h = build_hierarchy_gpu(sel_dev, dev)
     ev[1].record()
     ev[1].synchronize()
+    stats = {}
+    if align:
+        align_hierarchy_gpu(h, stats)
     t1 = time.perf_counter()
     os.makedirs(out_dir, exist_ok=True)
     out_path = os.path.join(out_dir, "hierarchy.hier")
     write_hierarchy(out_path, h.xyz, h.shs, h.alpha, h.log_scales, h.rots, h.nodes, h.boxes)
     return dict(rows_read=scene.P, rows_kept=int(rows.numel()), nodes=h.num_nodes, build_ms=ev[0].elapsed_time(ev[1]),
-                read_s=t_read, write_s=time.perf_counter() - t1, path=out_path)
+                align_ms=stats.get("align_ms"), read_s=t_read, write_s=time.perf_counter() - t1, path=out_path)
 
 
 def main(argv=None) -> int:
-    argv = sys.argv[1:] if argv is None else list(argv)
+    argv, flags = split_flags(sys.argv[1:] if argv is None else list(argv))
     if len(argv) not in (3, 4):
-        print("usage: python -m hgs.create_hierarchy <point_cloud.ply> <chunk dir> <out dir> [<scaffold dir>]",
+        print("usage: python -m hgs.create_hierarchy [--align] <point_cloud.ply> <chunk dir> <out dir> [<scaffold dir>]",
               file=sys.stderr)
         return 2
-    r = run(*argv)
+    r = run(*argv, align="--align" in flags)
+    aligned = f", align {r['align_ms']:.2f} ms" if r["align_ms"] is not None else ""
     print(f"create_hierarchy: read {r['rows_read']} rows, kept {r['rows_kept']}, N = {r['nodes']} nodes, "
-          f"build {r['build_ms']:.2f} ms (read {r['read_s']:.2f} s, write {r['write_s']:.2f} s) -> {r['path']}",
+          f"build {r['build_ms']:.2f} ms{aligned} (read {r['read_s']:.2f} s, write {r['write_s']:.2f} s) -> {r['path']}",
           flush=True)
     return 0
 

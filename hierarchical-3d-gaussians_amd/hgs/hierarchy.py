@@ -6,7 +6,9 @@ project's own construction rule (``build_hierarchy``, the float64 numpy spec; ``
 the same rule on the device, behind ``python -m hgs.create_hierarchy``): a balanced binary BVH over
 Morton-sorted leaves, interior nodes holding a moment-matched merge of their children.  Chunk hierarchies are joined
 under one root by ``merge_hierarchies`` (the torch spec) and ``merge_hierarchies_gpu`` (the same rule on the device, one
-chunk at a time, behind ``python -m hgs.merge_hierarchies``).
+chunk at a time, behind ``python -m hgs.merge_hierarchies``).  ``align_hierarchy`` (the numpy spec) and ``align_hierarchy_gpu``
+(the same rule on the device, behind ``--align`` and ``python -m hgs.align_hierarchy``) re-express every node's rotation
+and scales in the frame closest to its parent's, opt-in.
 Layout = DESIGN.md '.hier layout':
 
   one Gaussian per node, Gaussian index == node index (``start`` = node id)
@@ -174,12 +176,12 @@ def build_hierarchy(scene) -> Hierarchy:
                      nodes=torch.from_numpy(nodes), boxes=torch.from_numpy(boxes))
 
 
-def build_hierarchy_gpu(scene, device=None) -> Hierarchy:
+def build_hierarchy_gpu(scene, device=None, align=False) -> Hierarchy:
     """``build_hierarchy`` on the GPU (csrc/hier_build.hip, hgs_hier_build): same input (an hgs.synth.Scene of activated
     rows, M in {1, 4, 9, 16} SH coefficients), same topology, numbering and merge rule, a ``Hierarchy`` of tensors on
     ``device`` (default: the current GPU).  nodes, boxes and the leaf rows of xyz / shs / alpha / rots are bit-exact
-    against ``build_hierarchy``; interior rows agree to rounding.  No CPU fallback: raises without
-    libhgs.so or a GPU."""
+    against ``build_hierarchy``; interior rows agree to rounding.  ``align`` (opt-in): run
+    ``align_hierarchy_gpu`` on the result.  No CPU fallback: raises without libhgs.so or a GPU."""
     import ctypes as C
     from . import _lib
     lib = _lib.lib()
@@ -206,7 +208,7 @@ def build_hierarchy_gpu(scene, device=None) -> Hierarchy:
         _lib.check(lib.hgs_hier_build(p(xyz), p(scales), p(rots), p(opacity), p(shs), P, M, p(out.xyz), p(out.shs),
                                       p(out.alpha), p(out.log_scales), p(out.rots), p(out.nodes), p(out.boxes), p(tmp),
                                       stream, dev.index or 0), "hgs_hier_build")
-    return out
+    return align_hierarchy_gpu(out) if align else out
 
 
 def build_hierarchy_on_device(P, cam, device, seed=0, sh_degree=3, s_px=(0.5, 4.0), z_range=(2.0, 20.0)) -> Hierarchy:
@@ -462,7 +464,7 @@ def _tensor_sizes(h):
     return G, N, M
 
 
-def merge_hierarchies_gpu(sources, device=None, stats=None) -> Hierarchy:
+def merge_hierarchies_gpu(sources, device=None, stats=None, align=False) -> Hierarchy:
     """``merge_hierarchies`` on the GPU (csrc/hier_merge.hip, hgs_hier_merge_place / hgs_hier_merge_root), applied to
     chunks trimmed to their first N rows: rows at index >= N (a skybox tail, G > N) are dropped.  ``sources``: chunk
     ``Hierarchy``s (host or device tensors) or ``.hier`` paths, in merge order.  The merged tensors are allocated once on
@@ -471,8 +473,9 @@ def merge_hierarchies_gpu(sources, device=None, stats=None) -> Hierarchy:
     nodes, boxes and every non-root row equal ``merge_hierarchies`` on the trimmed chunks bit for bit; the root row
     agrees to float32 rounding.  Each chunk is validated as it is placed: one that fails raises
     ``ChunkValidationError`` naming it, the check and the first offending node.  ``stats`` (a dict, optional) receives
-    ``read_s`` (host seconds loading paths) and ``merge_ms`` (device events around the placements and the root).  No
-    CPU fallback: raises without libhgs.so or a GPU."""
+    ``read_s`` (host seconds loading paths) and ``merge_ms`` (device events around the placements and the root).
+    ``align`` (opt-in): run ``align_hierarchy_gpu`` on the merged hierarchy once the root is written (``stats`` then
+    also receives ``align_ms``).  No CPU fallback: raises without libhgs.so or a GPU."""
     import ctypes as C
     from . import _lib
     lib = _lib.lib()
@@ -550,8 +553,167 @@ def merge_hierarchies_gpu(sources, device=None, stats=None) -> Hierarchy:
         _lib.check(lib.hgs_hier_merge_root(C.byref(merged), k, stream, dev.index or 0), "hgs_hier_merge_root")
         ev[1].record()
         events.append(ev)
+    align_stats = {}
+    if align:
+        align_hierarchy_gpu(out, align_stats)
     if stats is not None:
         events[-1][1].synchronize()
         stats["read_s"] = read_s
         stats["merge_ms"] = sum(a.elapsed_time(b) for a, b in events)
+        stats.update(align_stats)
     return out
+
+
+# ---- rotation alignment: every node's frame re-parametrised to lie close to its parent's -------------------------------
+ALIGN_BOUND = (2.0 + 2.0 ** 0.5) / 4.0   # the least |<q_child, q_parent>| (normalised) the best of 24 frames can have
+ALIGN_MAX_NODES = (1 << 31) - 1
+# hgs_hier_align_report.first_bad, in the order they are reported
+ALIGN_CHECKS = ("depth outside [0, 255]",
+                "parent outside [0, N) at a node of depth > 0",
+                "parent's depth is not the node's depth - 1",
+                "more than one node of depth 0")
+
+
+def align_group():
+    """-> (quats float64 [24,4] (w,x,y,z), perms int64 [24,3]): the 24 proper signed permutation matrices M in the
+    order of the rule (permutations of (0,1,2) outermost, the signs (1,-1)^3 inside, det(M) > 0 kept), M[perm[k], k] =
+    signs[k]: R(q (x) g) = R(q) M has +- column perm[k] of R(q) as its column k.  Element 0 is the identity."""
+    import itertools
+    quats, perms = [], []
+    for perm in itertools.permutations(range(3)):
+        for signs in itertools.product((1, -1), repeat=3):
+            M = np.zeros((3, 3))
+            for k in range(3):
+                M[perm[k], k] = signs[k]
+            if np.linalg.det(M) > 0:
+                quats.append(_quat_from_rot(M[None])[0])
+                perms.append(perm)
+    return np.array(quats), np.array(perms, dtype=np.int64)
+
+
+def _quat_mul(a, b):
+    """Hamilton product a (x) b, (w,x,y,z), every sum left to right (the order csrc/hier_align.hip repeats)."""
+    a0, a1, a2, a3 = a[..., 0], a[..., 1], a[..., 2], a[..., 3]
+    b0, b1, b2, b3 = b[..., 0], b[..., 1], b[..., 2], b[..., 3]
+    return np.stack([a0 * b0 - a1 * b1 - a2 * b2 - a3 * b3,
+                     a0 * b1 + a1 * b0 + a2 * b3 - a3 * b2,
+                     a0 * b2 - a1 * b3 + a2 * b0 + a3 * b1,
+                     a0 * b3 + a1 * b2 - a2 * b1 + a3 * b0], -1)
+
+
+def align_choice(q, qp):
+    """The rule at nodes with float32 quaternions ``q`` [n,4] under parents with FINAL quaternions ``qp`` [n,4]:
+    -> (j int64 [n], negate bool [n], aligned float32 [n,4]).  Candidates c_j = q (x) g_j and d_j = <c_j, qp> in
+    float64, the first j of the largest |d_j|, the sign of d_j folded in (sign(0) = +); j = 0 keeps the input's bits."""
+    g, _ = align_group()
+    qd, pd = np.asarray(q, dtype=np.float64), np.asarray(qp, dtype=np.float64)
+    c = _quat_mul(qd[:, None, :], g[None, :, :])                                    # [n,24,4]
+    d = c[..., 0] * pd[:, None, 0] + c[..., 1] * pd[:, None, 1] + c[..., 2] * pd[:, None, 2] + c[..., 3] * pd[:, None, 3]
+    j = np.argmax(np.abs(d), axis=1)                                                 # the first maximum
+    rows = np.arange(qd.shape[0])
+    neg = d[rows, j] < 0
+    best = np.where(neg[:, None], -c[rows, j], c[rows, j]).astype(np.float32)
+    q32 = np.asarray(q, dtype=np.float32)
+    best = np.where((j == 0)[:, None], np.where(neg[:, None], -q32, q32), best)
+    return j, neg, best
+
+
+def align_hierarchy(h: Hierarchy, choice=None) -> Hierarchy:
+    """Rotation alignment (the float64 numpy spec; ``align_hierarchy_gpu`` is the same rule on the device): every
+    non-root node's (rotation, scales) pair is replaced by the one of its 24 equivalent parametrisations -- the frame's
+    axes permuted and negated by a proper signed permutation, the log-scales permuted with them -- whose quaternion
+    lies closest to the parent's FINAL quaternion, parents before children (``align_choice``).  The Gaussian a node
+    represents does not change; the quaternion norm is kept; the normalised dot with the parent becomes >= ALIGN_BOUND.
+    xyz, shs, alpha, nodes, boxes, the root row and rows at index >= N are untouched.  Nodes are levelled by their
+    ``depth`` column, so any numbering works (the builder's BFS, the merger's chunks side by side).
+    ``choice`` (optional int64 [N] array) receives the chosen group element per node.  -> a new Hierarchy (host)."""
+    nodes = h.nodes.cpu().numpy()
+    N = nodes.shape[0]
+    depth, parent = nodes[:, 0].astype(np.int64), nodes[:, 1].astype(np.int64)
+    assert N >= 1 and int((depth == 0).sum()) == 1 and depth.min() >= 0 and depth.max() <= 255
+    nonroot = depth > 0
+    assert bool(((parent[nonroot] >= 0) & (parent[nonroot] < N)).all())
+    assert bool((depth[parent[nonroot]] == depth[nonroot] - 1).all())
+    _, perms = align_group()
+    rots = h.rots.detach().cpu().numpy().astype(np.float32).copy()
+    ls = h.log_scales.detach().cpu().numpy().astype(np.float32).copy()
+    if choice is not None:
+        choice[:] = 0
+    for d in range(1, int(depth.max()) + 1):
+        ids = np.nonzero(depth == d)[0]
+        j, _, best = align_choice(rots[ids], rots[parent[ids]])
+        rots[ids] = best
+        ls[ids] = np.take_along_axis(ls[ids], perms[j], axis=1)
+        if choice is not None:
+            choice[ids] = j
+    cp = lambda t: t.detach().cpu().clone()
+    return Hierarchy(xyz=cp(h.xyz), shs=cp(h.shs), alpha=cp(h.alpha), log_scales=torch.from_numpy(ls),
+                     rots=torch.from_numpy(rots), nodes=cp(h.nodes), boxes=cp(h.boxes))
+
+
+def alignment_dots(h: Hierarchy):
+    """|<q_i, q_parent>| of the normalised quaternions at every node of depth > 0 (float64 numpy [N - 1], node order):
+    what the rule maximises; below ALIGN_BOUND the node's frame is more than 62.8 degrees from its parent's."""
+    nodes = h.nodes.cpu().numpy()
+    N = nodes.shape[0]
+    q = h.rots[:N].detach().cpu().numpy().astype(np.float64)
+    q = q / np.linalg.norm(q, axis=1, keepdims=True)
+    ids = np.nonzero(nodes[:, 0] > 0)[0]
+    return np.abs((q[ids] * q[nodes[ids, 1]]).sum(1))
+
+
+class HierarchyAlignError(ValueError):
+    """A hierarchy ``align_hierarchy_gpu`` rejected (and left untouched): ``check`` (what failed, one of ALIGN_CHECKS)
+    and ``node`` (the first offending node, None when no node has depth 0)."""
+
+    def __init__(self, check, node, message):
+        super().__init__(message)
+        self.check, self.node = check, node
+
+
+def align_hierarchy_gpu(h: Hierarchy, stats=None) -> Hierarchy:
+    """``align_hierarchy`` on the GPU (csrc/hier_align.hip, hgs_hier_align), in place: ``h.log_scales`` and ``h.rots``
+    (contiguous float32 device tensors of >= N rows; rows behind the N nodes -- a skybox tail -- are not touched) are
+    rewritten, nothing else is; -> ``h``.  The choice of frame and the written bits are the spec's (double arithmetic
+    in the spec's order).  ``h.nodes`` is validated first (depths in [0, 255], parents in range and one level up, one
+    node of depth 0): a hierarchy that fails raises ``HierarchyAlignError`` naming the check and the first offending
+    node, and is left untouched.  ``stats`` (a dict, optional) receives ``align_ms`` (device events around the call).
+    No CPU fallback: raises without libhgs.so or a GPU."""
+    import ctypes as C
+    from . import _lib
+    lib = _lib.lib()
+    if not torch.cuda.is_available():
+        raise RuntimeError("align_hierarchy_gpu needs a GPU (there is no CPU fallback; align_hierarchy is the numpy spec)")
+    N = int(h.nodes.shape[0])
+    if N < 1 or N > ALIGN_MAX_NODES:
+        raise ValueError(f"N = {N} nodes; 1 .. 2^31 - 1 expected")
+    dev = h.nodes.device
+    for name, dtype, width in (("nodes", torch.int32, 7), ("log_scales", torch.float32, 3), ("rots", torch.float32, 4)):
+        t = getattr(h, name)
+        if not (t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor on {dev} (align_hierarchy_gpu works in place)")
+        if t.numel() % width or t.numel() // width < N:
+            raise ValueError(f"{name} has {t.numel()} values; at least {N} rows of {width} expected")
+    tmp = torch.empty(lib.hgs_hier_align_tmp_bytes(N), dtype=torch.uint8, device=dev)
+    rep = _lib.HierAlignReport()
+    rep.first_bad[:] = [-1] * 4              # (a call that fails its size checks does not fill the report)
+    p = _lib.ptr
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        rc = lib.hgs_hier_align(p(h.nodes), N, p(h.log_scales), p(h.rots), p(tmp), C.byref(rep), stream, dev.index or 0)
+        ev[1].record()
+    if rc != 0:
+        msg = lib.hgs_last_error()
+        msg = msg.decode() if msg else "?"
+        for check, node in zip(ALIGN_CHECKS, rep.first_bad):
+            if node >= 0:
+                raise HierarchyAlignError(check, int(node), f"hgs_hier_align: {msg}")
+        if rc == 1 and "no node of depth 0" in msg:
+            raise HierarchyAlignError("no node of depth 0", None, f"hgs_hier_align: {msg}")
+        raise _lib.HgsError(f"hgs_hier_align failed (code {rc}): {msg}", rc)
+    if stats is not None:
+        ev[1].synchronize()
+        stats["align_ms"] = ev[0].elapsed_time(ev[1])
+    return h

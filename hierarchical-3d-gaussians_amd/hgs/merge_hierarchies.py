@@ -1,6 +1,6 @@
 """Hierarchy consolidation: every trained chunk's hierarchy -> one ``merged.hier``.
 
-    python -m hgs.merge_hierarchies <trained chunks dir> <root type> <chunks dir> <output .hier> <chunk name> [...]
+    python -m hgs.merge_hierarchies [--align] <trained chunks dir> <root type> <chunks dir> <output .hier> <chunk name> [...]
 
 The positional form of the reference's consolidation call (scripts/full_train.py:240-250), so only the executable
 changes; the output is what ``render_hierarchy.py`` and the viewer load.  Steps:
@@ -10,7 +10,10 @@ changes; the output is what ``render_hierarchy.py`` and the viewer load.  Steps:
   2. merge with ``hgs.hierarchy.merge_hierarchies_gpu``: a new root over the chunk roots, every chunk's nodes behind
      them, rows and boxes unchanged.  Rows behind a chunk's N node rows (the scaffold's skybox, appended by save_hier)
      are dropped; render_hierarchy.py / train_post.py append the scaffold's skybox again when they load the result;
-  3. write the merged hierarchy (write_hierarchy).
+  3. with ``--align`` (opt-in, anywhere among the arguments): ``hgs.hierarchy.align_hierarchy_gpu`` on the merged
+     hierarchy -- the chunk roots against the new axis-aligned root, and every chunk's nodes below them (DESIGN.md
+     section 4).  Without the flag the output is byte for byte what it was before the flag existed;
+  4. write the merged hierarchy (write_hierarchy).
 
 Root type 0 (what full_train.py passes) is the only one.  ``<chunks dir>/<name>/center.txt`` / ``extent.txt`` serve a
 report only: the leaves whose means lie outside their chunk's square (create_hierarchy.select_rows' float32 test),
@@ -25,9 +28,9 @@ import time
 
 import torch
 
-from .create_hierarchy import read_chunk_bounds, select_rows
+from .create_hierarchy import read_chunk_bounds, select_rows, split_flags
 
-USAGE = ("usage: python -m hgs.merge_hierarchies <trained chunks dir> <root type> <chunks dir> <output .hier> "
+USAGE = ("usage: python -m hgs.merge_hierarchies [--align] <trained chunks dir> <root type> <chunks dir> <output .hier> "
          "<chunk name> [<chunk name> ...]")
 
 
@@ -56,8 +59,8 @@ def count_drifted(h, node_counts, bounds):
     return total
 
 
-def run(trained_dir, chunks_dir, out_path, names) -> dict:
-    """Read, merge, write; -> figures of the run."""
+def run(trained_dir, chunks_dir, out_path, names, align=False) -> dict:
+    """Read, merge, (align,) write; -> figures of the run."""
     from gaussian_hierarchy._C import write_hierarchy
     from .hierarchy import merge_hierarchies_gpu, read_hier_header
     if not torch.cuda.is_available():
@@ -68,7 +71,7 @@ def run(trained_dir, chunks_dir, out_path, names) -> dict:
     dev = torch.device("cuda", torch.cuda.current_device())
     stats = {}
     t0 = time.perf_counter()
-    h = merge_hierarchies_gpu(paths, dev, stats)
+    h = merge_hierarchies_gpu(paths, dev, stats, align=align)
     t_merge = time.perf_counter() - t0
     node_counts = [hd[1] for hd in headers]
     drifted = count_drifted(h, node_counts, bounds)
@@ -77,12 +80,13 @@ def run(trained_dir, chunks_dir, out_path, names) -> dict:
     write_hierarchy(out_path, h.xyz, h.shs, h.alpha, h.log_scales, h.rots, h.nodes, h.boxes)
     return dict(chunks=len(names), nodes=node_counts, merged=h.num_nodes,
                 skybox_dropped=sum(hd[0] - hd[1] for hd in headers), drifted=drifted,
-                bounded=sum(b is not None for b in bounds), merge_ms=stats["merge_ms"], read_s=stats["read_s"],
+                bounded=sum(b is not None for b in bounds), merge_ms=stats["merge_ms"], align_ms=stats.get("align_ms"),
+                read_s=stats["read_s"],
                 merge_s=t_merge, write_s=time.perf_counter() - t1, path=out_path)
 
 
 def main(argv=None) -> int:
-    argv = sys.argv[1:] if argv is None else list(argv)
+    argv, flags = split_flags(sys.argv[1:] if argv is None else list(argv))
     if len(argv) < 5:
         print(USAGE, file=sys.stderr)
         return 2
@@ -101,13 +105,14 @@ def main(argv=None) -> int:
             print(f"merge_hierarchies: {n}: no hierarchy.hier_opt, merging its hierarchy.hier", flush=True)
     from .hierarchy import ChunkValidationError
     try:
-        r = run(trained_dir, chunks_dir, out_path, names)
+        r = run(trained_dir, chunks_dir, out_path, names, align="--align" in flags)
     except ChunkValidationError as e:
         print(f"merge_hierarchies: {e}; nothing written", file=sys.stderr)
         return 1
+    aligned = f", align {r['align_ms']:.2f} ms" if r["align_ms"] is not None else ""
     print(f"merge_hierarchies: {r['chunks']} chunks of {'/'.join(str(n) for n in r['nodes'])} nodes, merged N = "
           f"{r['merged']} nodes, dropped {r['skybox_dropped']} skybox rows, {r['drifted']} leaves outside their chunk "
-          f"({r['bounded']} chunks with bounds), merge {r['merge_ms']:.2f} ms on the device (read {r['read_s']:.2f} s, "
+          f"({r['bounded']} chunks with bounds), merge {r['merge_ms']:.2f} ms{aligned} on the device (read {r['read_s']:.2f} s, "
           f"write {r['write_s']:.2f} s) -> {r['path']}", flush=True)
     return 0
 

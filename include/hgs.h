@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define HGS_ABI_VERSION 12
+#define HGS_ABI_VERSION 13
 #define HGS_TILE 16
 #define HGS_INST_GRAD_STRIDE 10 /* floats per (tile, Gaussian) instance in the backward scratch (40 bytes: the ten sums) */
 
@@ -524,6 +524,36 @@ typedef struct hgs_hier_merge_report {
 int hgs_hier_merge_place(const hgs_hier_view* chunk, int32_t index, int32_t k, int64_t base, const hgs_hier_view* merged,
                          void* tmp, hgs_hier_merge_report* report, hgs_stream_t stream, int device);
 int hgs_hier_merge_root(const hgs_hier_view* merged, int32_t k, hgs_stream_t stream, int device);
+
+/* ---------------------------------------------------------------------------
+ * Rotation alignment of a hierarchy, in place on the device: the rule of hgs.hierarchy.align_hierarchy (DESIGN.md
+ * section 7 f-13).  Opt-in: no other call aligns.  A node's (rotation, scales) pair has 24 equivalent parametrisations:
+ * the group G of proper signed permutation matrices M, enumerated as "for perm in permutations(0,1,2): for signs in
+ * (1,-1)^3: M[perm[k], k] = signs[k], kept if det M > 0" (element 0 = identity), each with the quaternion g of M and
+ * the scale permutation perm (new axis k = +- old axis perm[k]).  Nodes are processed parents before children; the
+ * node of depth 0 is untouched.  For node i with parent p whose FINAL quaternion is q'_p: c_j = q_i (x) g_j (Hamilton
+ * product, (w,x,y,z)), d_j = <c_j, q'_p>, both in double; j = the first index that maximises |d_j|;
+ * q'_i = sign(d_j) c_j with sign(0) = +, rounded to float32 (j = 0: the input's bits or their exact negation);
+ * log_scales'_i[k] = log_scales_i[perm_j[k]].  The Gaussian of a node, the norm of its quaternion, xyz, shs, alpha,
+ * nodes, boxes and rows at index >= N are unchanged; afterwards |<q'_i, q'_p>| / (|q'_i| |q'_p|) >= (2 + sqrt 2) / 4.
+ * nodes int32 [N,7] (only depth and parent are read: any numbering), log_scales [>= N,3], rots [>= N,4] 16-byte aligned,
+ * all device memory; 1 <= N <= 2^31 - 1.  tmp: hgs_hier_align_tmp_bytes(N) of device memory, 256-byte aligned.
+ * hgs_hier_align_tmp_bytes: host only (no GPU needed); 0 for an N outside [1, 2^31 - 1].
+ * hgs_hier_align: sizes and pointers are checked before any HIP call.  The level lists come from the depth column (a
+ * stable 8-bit sort of the node ids and a 256-bin count), then one launch per depth; ONE host wait, for the level sizes
+ * and the checks.  The hierarchy is validated before anything is written: a failed check returns HGS_ERR_INVALID with
+ * the check and its first offending node in the message and in `report`, and leaves log_scales and rots untouched. */
+typedef struct hgs_hier_align_report {
+  int32_t first_bad[4]; /* first offending node per check, -1 if none: [0] depth outside [0, 255]; [1] a node of depth
+                         * > 0 whose parent is outside [0, N); [2] a node of depth > 0 whose parent's depth is not its
+                         * own - 1; [3] the second node of depth 0 */
+  int32_t roots;        /* nodes of depth 0: 1 for a valid hierarchy */
+  int32_t levels;       /* depths in use, counted from 0 up to the first empty one */
+  int32_t reserved[2];
+} hgs_hier_align_report;
+size_t hgs_hier_align_tmp_bytes(int64_t N);
+int hgs_hier_align(const int32_t* nodes, int64_t N, float* log_scales, float* rots, void* tmp,
+                   hgs_hier_align_report* report, hgs_stream_t stream, int device);
 
 /* ---------------------------------------------------------------------------
  * Fused SSIM loss (hgs.loss.ssim): the standard SSIM of the reference's loss -- an 11-tap
