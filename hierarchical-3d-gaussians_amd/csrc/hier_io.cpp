@@ -14,6 +14,7 @@
 //      float  log_scale[P][3]         (half)
 //      float  alpha[P]                (half)
 //      float  sh[P][16][3]            (half)
+//  (HGS_HIER_UPSTREAM_HALF writes the compressed variant; a file of P = 0 Gaussians reads back as the float variant)
 //      int32  N                       number of nodes
 //      int32  nodes[N][7]             depth, parent, start, count_leafs, count_merged, start_children, count_children
 //      float  boxes[N][2][4]          min.xyz + extent, max.xyz + pad
@@ -49,6 +50,40 @@ float half_to_float(uint16_t h) {
   float f;
   memcpy(&f, &bits, 4);
   return f;
+}
+
+// float -> IEEE half under the narrowing rule of include/hgs.h (HGS_RESID_HOST_ROW_BYTES_HALF): round to nearest even,
+// subnormal halves kept, a finite value beyond +-65504 becomes +-65504, NaN stays NaN (0x7e00 under its sign), an infinity
+// stays an infinity
+uint16_t float_to_half(float f) {
+  uint32_t x;
+  memcpy(&x, &f, 4);
+  const uint16_t sign = (uint16_t)((x >> 16) & 0x8000u);
+  x &= 0x7fffffffu;
+  if (x > 0x7f800000u) return sign | 0x7e00u;            // every NaN becomes the quiet NaN of its sign
+  if (x == 0x7f800000u) return sign | 0x7c00u;
+  if (x >= 0x477fe000u) return sign | 0x7bffu;           // >= 65504: saturates (65520 and beyond would round to infinity)
+  if (x < 0x33000000u) return sign;                      // < 2^-25: rounds to zero (2^-25 itself is a tie, to even = 0)
+  uint32_t man = (x & 0x7fffffu) | 0x800000u;
+  const int e = (int)(x >> 23) - 127;                    // value = man * 2^(e - 23)
+  // bits dropped: 13 for a normal half (e >= -14), more in the subnormal range (the half's unit is 2^-24)
+  const int shift = e >= -14 ? 13 : 13 + (-14 - e);
+  const uint32_t kept = man >> shift, rest = man & ((1u << shift) - 1u), halfway = 1u << (shift - 1);
+  uint32_t h = e >= -14 ? ((uint32_t)(e + 15) << 10) + (kept & 0x3ffu) : kept;
+  if (rest > halfway || (rest == halfway && (h & 1u))) ++h;      // (a carry out of the mantissa raises the exponent)
+  return sign | (uint16_t)h;
+}
+
+// writes `count` floats as float or, narrowed block by block, as IEEE half
+bool write_values(FILE* f, const float* src, size_t count, bool half) {
+  if (!half) return write_all(f, src, count * 4);
+  uint16_t block[4096];
+  for (size_t at = 0; at < count; at += 4096) {
+    const size_t k = count - at < 4096 ? count - at : 4096;
+    for (size_t i = 0; i < k; ++i) block[i] = float_to_half(src[at + i]);
+    if (!write_all(f, block, k * 2)) return false;
+  }
+  return true;
 }
 
 int alloc_parts(hgs_hier_host* out) {
@@ -148,16 +183,19 @@ int hgs_hier_write(const char* path, const hgs_hier_host* in) {
   if (!path || !in) { set_error("null argument"); return HGS_ERR_INVALID; }
   if (in->P < 0 || in->N < 0 || in->M < 0) { set_error("negative sizes"); return HGS_ERR_INVALID; }
   const int fmt = in->reserved;
-  if (fmt != HGS_HIER_UPSTREAM && fmt != HGS_HIER_PRIVATE) { set_error("hgs_hier_write: format %d cannot be written (0 = upstream float layout, 1 = HGSHIER1)", fmt); return HGS_ERR_INVALID; }
-  if (fmt == HGS_HIER_UPSTREAM && in->M != 16) { set_error("the upstream .hier layout stores exactly 16 SH coefficients per Gaussian (got %d); use HGS_HIER_PRIVATE", in->M); return HGS_ERR_INVALID; }
+  if (fmt != HGS_HIER_UPSTREAM && fmt != HGS_HIER_PRIVATE && fmt != HGS_HIER_UPSTREAM_HALF) { set_error("hgs_hier_write: format %d cannot be written (0 = upstream float layout, 1 = HGSHIER1, 2 = upstream half layout)", fmt); return HGS_ERR_INVALID; }
+  if (fmt != HGS_HIER_PRIVATE && in->M != 16) { set_error("the upstream .hier layout stores exactly 16 SH coefficients per Gaussian (got %d); use HGS_HIER_PRIVATE", in->M); return HGS_ERR_INVALID; }
   FILE* f = fopen(path, "wb");
   if (!f) { set_error("cannot create %s", path); return HGS_ERR_IO; }
   const size_t p = (size_t)in->P, n = (size_t)in->N, m = (size_t)in->M;
   bool ok;
-  if (fmt == HGS_HIER_UPSTREAM) {
-    ok = write_all(f, &in->P, 4) && write_all(f, in->xyz, p * 12) && write_all(f, in->rots, p * 16) &&
-         write_all(f, in->log_scales, p * 12) && write_all(f, in->alpha, p * 4) && write_all(f, in->shs, p * 192) &&
-         write_all(f, &in->N, 4) && write_all(f, in->nodes, n * 28) && write_all(f, in->boxes, n * 32);
+  if (fmt != HGS_HIER_PRIVATE) {
+    const bool half = fmt == HGS_HIER_UPSTREAM_HALF;
+    const int32_t P_raw = half ? -in->P : in->P;           // a negative count marks the half variant (load_upstream)
+    ok = write_all(f, &P_raw, 4) && write_all(f, in->xyz, p * 12) && write_values(f, in->rots, p * 4, half) &&
+         write_values(f, in->log_scales, p * 3, half) && write_values(f, in->alpha, p, half) &&
+         write_values(f, in->shs, p * 48, half) && write_all(f, &in->N, 4) && write_all(f, in->nodes, n * 28) &&
+         write_all(f, in->boxes, n * 32);
   } else {
     const int32_t hdr[4] = {in->P, in->N, in->M, 0};
     ok = write_all(f, kMagic, 8) && write_all(f, hdr, sizeof(hdr)) && write_all(f, in->xyz, p * 12) &&

@@ -127,6 +127,130 @@ __global__ __launch_bounds__(256) void resid_fetch_kernel(const int32_t* __restr
   }
 }
 
+// ---- half-precision host rows (HGS_RESID_HOST_ROW_BYTES_HALF, include/hgs.h) ---------------------------------------
+// A row is eight 16-byte chunks: chunks 0..5 hold 48 halves of SH, chunk 6 rotation (4 halves), scale (3) and opacity
+// (1), chunk 7 the mean as three float32 and four bytes of padding.
+
+// IEEE half (bits) -> float: exact (v_cvt_f32_f16; subnormal halves become normal floats)
+__device__ __forceinline__ float widen_half(uint32_t h) {
+  const uint16_t b = (uint16_t)h;
+  _Float16 x;
+  __builtin_memcpy(&x, &b, 2);
+  return (float)x;
+}
+
+__device__ __forceinline__ void widen8(const uint4 v, float* f) {
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    f[2 * t] = widen_half(w[t] & 0xffffu);
+    f[2 * t + 1] = widen_half(w[t] >> 16);
+  }
+}
+
+// float -> IEEE half (bits), the narrowing rule of include/hgs.h: round to nearest even with subnormal halves kept, a
+// finite value beyond +-65504 becomes +-65504 (narrowing never makes an infinity), NaN stays NaN (0x7e00 under its sign),
+// an infinity stays one
+__device__ __forceinline__ uint32_t narrow_half(float x) {
+  if (x != x) return (__float_as_uint(x) >> 16 & 0x8000u) | 0x7e00u;
+  if (fabsf(x) <= 3.402823466e+38f) x = fminf(fmaxf(x, -65504.0f), 65504.0f);       // (false for infinities)
+  const _Float16 h = (_Float16)x;
+  uint16_t b;
+  __builtin_memcpy(&b, &h, 2);
+  return b;
+}
+
+__device__ __forceinline__ uint32_t narrow2(float lo, float hi) { return narrow_half(lo) | narrow_half(hi) << 16; }
+
+// Eight lanes per missing row, eight rows per wave, 32 rows per workgroup: every lane loads ONE 16-byte chunk of the
+// packed half row (one fully coalesced 128-byte read per row = two 64-byte PCIe requests), widens it and stores floats
+// into the slot arrays the float kernel fills: lanes 0..5 the SH block, lane 6 rotation, scale and opacity, lane 7 the
+// mean and the bookkeeping.  Slot assignment as in resid_fetch_kernel: miss j takes free_list[free_top - 1 - j].
+template <bool kVec>
+__global__ __launch_bounds__(256) void resid_fetch_half_kernel(const int32_t* __restrict__ miss_ids, uint32_t m,
+                                                               const int32_t* __restrict__ free_list, uint32_t free_top,
+                                                               int32_t* __restrict__ slot_of, int32_t* __restrict__ id_of_slot,
+                                                               uint32_t* __restrict__ stamp, uint32_t frame,
+                                                               const uint4* __restrict__ src, hgs_resid_rows dst, int nsh) {
+  const uint32_t j = blockIdx.x * 32u + (threadIdx.x >> 3);
+  const int sub = threadIdx.x & 7;
+  if (j >= m) return;
+  const size_t id = (size_t)miss_ids[j];
+  const size_t s = (size_t)free_list[free_top - 1u - j];
+  const uint4 v = src[id * (HGS_RESID_HOST_ROW_BYTES_HALF / 16) + sub];
+  if (sub < 6) {
+    float f[8];
+    widen8(v, f);
+    if (kVec) {                                    // nsh % 4 == 0: slot rows of the SH array are 16-byte aligned
+      float4* row = reinterpret_cast<float4*>(dst.shs + s * nsh);
+      if (sub * 8 < nsh) row[sub * 2] = make_float4(f[0], f[1], f[2], f[3]);
+      if (sub * 8 + 4 < nsh) row[sub * 2 + 1] = make_float4(f[4], f[5], f[6], f[7]);
+    } else {
+#pragma unroll
+      for (int t = 0; t < 8; ++t)
+        if (sub * 8 + t < nsh) dst.shs[s * nsh + sub * 8 + t] = f[t];
+    }
+  } else if (sub == 6) {                           // halves 48..55: rotation, scale, opacity
+    float f[8];
+    widen8(v, f);
+    reinterpret_cast<float4*>(dst.rotations)[s] = make_float4(f[0], f[1], f[2], f[3]);
+    dst.scales[s * 3 + 0] = f[4]; dst.scales[s * 3 + 1] = f[5]; dst.scales[s * 3 + 2] = f[6];
+    dst.opacities[s] = f[7];
+  } else {                                         // bytes 112..127: mean (float32), padding
+    dst.means3D[s * 3 + 0] = __uint_as_float(v.x);
+    dst.means3D[s * 3 + 1] = __uint_as_float(v.y);
+    dst.means3D[s * 3 + 2] = __uint_as_float(v.z);
+    slot_of[id] = (int32_t)s;
+    id_of_slot[s] = (int32_t)id;
+    stamp[s] = frame;
+  }
+}
+
+// Device attribute arrays -> packed rows in pinned, device-mapped host memory, written by the kernel itself with plain
+// 16-byte vector stores (one per lane, a row's lanes adjacent: whole rows leave as 128- / 256-byte writes).  kHalf: eight
+// lanes per row in the half layout above; else sixteen lanes per row in the float layout resid_fetch_kernel reads.
+// Padding is written as zeros in both.  A row's lanes read consecutive floats of the SH array.
+template <bool kHalf>
+__global__ __launch_bounds__(256) void resid_pack_kernel(hgs_resid_rows src, size_t G, int nsh, uint4* __restrict__ out) {
+  constexpr int kLanes = kHalf ? 8 : 16;
+  const size_t g = (size_t)blockIdx.x * (256 / kLanes) + threadIdx.x / kLanes;
+  const int sub = threadIdx.x % kLanes;
+  if (g >= G) return;
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  if (kHalf) {
+    if (sub < 6) {
+      float f[8];
+#pragma unroll
+      for (int t = 0; t < 8; ++t) f[t] = sub * 8 + t < nsh ? src.shs[g * nsh + sub * 8 + t] : 0.0f;
+      v = make_uint4(narrow2(f[0], f[1]), narrow2(f[2], f[3]), narrow2(f[4], f[5]), narrow2(f[6], f[7]));
+    } else if (sub == 6) {
+      const float* q = src.rotations + g * 4;
+      v = make_uint4(narrow2(q[0], q[1]), narrow2(q[2], q[3]), narrow2(src.scales[g * 3 + 0], src.scales[g * 3 + 1]),
+                     narrow2(src.scales[g * 3 + 2], src.opacities[g]));
+    } else {
+      v = make_uint4(__float_as_uint(src.means3D[g * 3 + 0]), __float_as_uint(src.means3D[g * 3 + 1]),
+                     __float_as_uint(src.means3D[g * 3 + 2]), 0u);
+    }
+  } else {
+    if (sub < 12) {
+      uint32_t w[4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) w[t] = sub * 4 + t < nsh ? __float_as_uint(src.shs[g * nsh + sub * 4 + t]) : 0u;
+      v = make_uint4(w[0], w[1], w[2], w[3]);
+    } else if (sub == 12) {
+      const float* q = src.rotations + g * 4;
+      v = make_uint4(__float_as_uint(q[0]), __float_as_uint(q[1]), __float_as_uint(q[2]), __float_as_uint(q[3]));
+    } else if (sub == 13) {                        // floats 52..55: mean, scale.x
+      v = make_uint4(__float_as_uint(src.means3D[g * 3 + 0]), __float_as_uint(src.means3D[g * 3 + 1]),
+                     __float_as_uint(src.means3D[g * 3 + 2]), __float_as_uint(src.scales[g * 3 + 0]));
+    } else if (sub == 14) {                        // floats 56..59: scale.y, scale.z, opacity, padding
+      v = make_uint4(__float_as_uint(src.scales[g * 3 + 1]), __float_as_uint(src.scales[g * 3 + 2]),
+                     __float_as_uint(src.opacities[g]), 0u);
+    }
+  }
+  out[g * kLanes + sub] = v;
+}
+
 }  // namespace
 }  // namespace hgs
 
@@ -219,9 +343,10 @@ int hgs_resid_evict(uint32_t* stamp, int32_t* id_of_slot, int32_t* slot_of, int3
   return HGS_OK;
 }
 
-int hgs_resid_fetch(const int32_t* miss_ids, uint32_t m, const int32_t* free_list, uint32_t free_top, int32_t* slot_of,
-                    int32_t* id_of_slot, uint32_t* stamp, uint32_t frame, const float* host_rows_packed,
-                    const hgs_resid_rows* slot_rows, int32_t M, hgs_stream_t stream, int device) {
+// the two fetch calls: the checks, the device-side address of the host rows, one launch
+static int resid_fetch(bool half, const int32_t* miss_ids, uint32_t m, const int32_t* free_list, uint32_t free_top,
+                       int32_t* slot_of, int32_t* id_of_slot, uint32_t* stamp, uint32_t frame, const void* host_rows_packed,
+                       const hgs_resid_rows* slot_rows, int32_t M, hgs_stream_t stream, int device) {
   if (m == 0) return HGS_OK;
   if (!miss_ids || !free_list || !slot_of || !id_of_slot || !stamp || !host_rows_packed || !slot_rows) {
     set_error("null argument");
@@ -233,7 +358,7 @@ int hgs_resid_fetch(const int32_t* miss_ids, uint32_t m, const int32_t* free_lis
   hipStream_t s = static_cast<hipStream_t>(stream);
   // the packed host rows by their device-side address
   void* d = nullptr;
-  if (hipHostGetDevicePointer(&d, const_cast<float*>(host_rows_packed), 0) != hipSuccess) {
+  if (hipHostGetDevicePointer(&d, const_cast<void*>(host_rows_packed), 0) != hipSuccess) {
     (void)hipGetLastError();
     set_error("the packed host rows must come from hgs_host_alloc (pinned, device-mapped)");
     return HGS_ERR_INVALID;
@@ -242,8 +367,19 @@ int hgs_resid_fetch(const int32_t* miss_ids, uint32_t m, const int32_t* free_lis
     set_error("packed host rows / slot rotations must be 16-byte aligned");
     return HGS_ERR_INVALID;
   }
-  const float4* src = static_cast<const float4*>(d);
   const bool vec = ((M * 3) & 3) == 0 && (((uintptr_t)slot_rows->shs & 15u) == 0);
+  if (half) {
+    const uint4* src = static_cast<const uint4*>(d);
+    if (vec)
+      hipLaunchKernelGGL(resid_fetch_half_kernel<true>, dim3((m + 31) / 32), dim3(256), 0, s, miss_ids, m, free_list,
+                         free_top, slot_of, id_of_slot, stamp, frame, src, *slot_rows, M * 3);
+    else
+      hipLaunchKernelGGL(resid_fetch_half_kernel<false>, dim3((m + 31) / 32), dim3(256), 0, s, miss_ids, m, free_list,
+                         free_top, slot_of, id_of_slot, stamp, frame, src, *slot_rows, M * 3);
+    HGS_LAUNCH_CHECK("resid_fetch_half", s, false);
+    return HGS_OK;
+  }
+  const float4* src = static_cast<const float4*>(d);
   if (vec)
     hipLaunchKernelGGL(resid_fetch_kernel<true>, dim3((m + 15) / 16), dim3(256), 0, s, miss_ids, m, free_list, free_top,
                        slot_of, id_of_slot, stamp, frame, src, *slot_rows, M * 3);
@@ -251,6 +387,48 @@ int hgs_resid_fetch(const int32_t* miss_ids, uint32_t m, const int32_t* free_lis
     hipLaunchKernelGGL(resid_fetch_kernel<false>, dim3((m + 15) / 16), dim3(256), 0, s, miss_ids, m, free_list, free_top,
                        slot_of, id_of_slot, stamp, frame, src, *slot_rows, M * 3);
   HGS_LAUNCH_CHECK("resid_fetch", s, false);
+  return HGS_OK;
+}
+
+int hgs_resid_fetch(const int32_t* miss_ids, uint32_t m, const int32_t* free_list, uint32_t free_top, int32_t* slot_of,
+                    int32_t* id_of_slot, uint32_t* stamp, uint32_t frame, const float* host_rows_packed,
+                    const hgs_resid_rows* slot_rows, int32_t M, hgs_stream_t stream, int device) {
+  return resid_fetch(false, miss_ids, m, free_list, free_top, slot_of, id_of_slot, stamp, frame, host_rows_packed, slot_rows,
+                     M, stream, device);
+}
+
+int hgs_resid_fetch_half(const int32_t* miss_ids, uint32_t m, const int32_t* free_list, uint32_t free_top, int32_t* slot_of,
+                         int32_t* id_of_slot, uint32_t* stamp, uint32_t frame, const void* host_rows_packed,
+                         const hgs_resid_rows* slot_rows, int32_t M, hgs_stream_t stream, int device) {
+  return resid_fetch(true, miss_ids, m, free_list, free_top, slot_of, id_of_slot, stamp, frame, host_rows_packed, slot_rows,
+                     M, stream, device);
+}
+
+int hgs_resid_pack_rows(const hgs_resid_rows* src, int64_t G, int32_t M, int32_t half, void* host_rows_packed,
+                        hgs_stream_t stream, int device) {
+  if (!src || !host_rows_packed || !src->means3D || !src->shs || !src->opacities || !src->scales || !src->rotations) {
+    set_error("null argument");
+    return HGS_ERR_INVALID;
+  }
+  if (G < 0 || G > 0x7fffffffLL) { set_error("G = %lld rows: 0..2^31-1", (long long)G); return HGS_ERR_INVALID; }
+  if (M < 1 || M > 16) { set_error("M = %d SH coefficients per channel: 1..16", M); return HGS_ERR_INVALID; }
+  if (half != 0 && half != 1) { set_error("half = %d: 0 (float rows) or 1 (half rows)", half); return HGS_ERR_INVALID; }
+  if (G == 0) return HGS_OK;
+  HGS_HIP(hipSetDevice(device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  void* d = nullptr;
+  if (hipHostGetDevicePointer(&d, host_rows_packed, 0) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("the packed host rows must come from hgs_host_alloc (pinned, device-mapped)");
+    return HGS_ERR_INVALID;
+  }
+  if ((uintptr_t)d & 15u) { set_error("packed host rows must be 16-byte aligned"); return HGS_ERR_INVALID; }
+  uint4* out = static_cast<uint4*>(d);
+  if (half)
+    hipLaunchKernelGGL(resid_pack_kernel<true>, dim3((unsigned)((G + 31) / 32)), dim3(256), 0, s, *src, (size_t)G, M * 3, out);
+  else
+    hipLaunchKernelGGL(resid_pack_kernel<false>, dim3((unsigned)((G + 15) / 16)), dim3(256), 0, s, *src, (size_t)G, M * 3, out);
+  HGS_LAUNCH_CHECK("resid_pack", s, false);
   return HGS_OK;
 }
 

@@ -162,8 +162,10 @@ def load_hierarchy(path: str):
     return xyz, shs, alpha, scales, rots, nodes, boxes
 
 
-def write_hierarchy(path: str, xyz, shs, alpha, log_scales, rots, nodes, boxes) -> None:
-    """scene/gaussian_model.py:420-427 (tensors may live on the GPU)."""
+def write_hierarchy(path: str, xyz, shs, alpha, log_scales, rots, nodes, boxes, *, half: bool = False) -> None:
+    """scene/gaussian_model.py:420-427 (tensors may live on the GPU).  ``half=True`` (keyword only; the reference's call
+    is positional): the upstream tools' compressed variant -- positions float32, rotations, log-scales, alpha and SH as
+    IEEE half under the narrowing rule of include/hgs.h, 124 bytes per Gaussian instead of 236; 16 SH coefficients only."""
     lib = _lib.lib()
     f = lambda t: np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
     a_xyz, a_shs, a_alpha, a_sc, a_rot = f(xyz), f(shs), f(alpha), f(log_scales), f(rots)
@@ -178,7 +180,8 @@ def write_hierarchy(path: str, xyz, shs, alpha, log_scales, rots, nodes, boxes) 
         raise RuntimeError("write_hierarchy: nodes must be [N,7] and boxes [N,2,4]")
     h = _lib.HierHost()
     # the upstream tools' layout whenever it can express the data (16 SH coefficients), else the private one
-    h.P, h.N, h.M, h.reserved = P, N, M, (_lib.HIER_UPSTREAM if M == 16 else _lib.HIER_PRIVATE)
+    h.P, h.N, h.M = P, N, M
+    h.reserved = _lib.HIER_UPSTREAM_HALF if half else (_lib.HIER_UPSTREAM if M == 16 else _lib.HIER_PRIVATE)
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
     h.xyz, h.shs, h.alpha, h.log_scales, h.rots = vp(a_xyz), vp(a_shs), vp(a_alpha), vp(a_sc), vp(a_rot)
     h.nodes, h.boxes = vp(a_nodes), vp(a_boxes)

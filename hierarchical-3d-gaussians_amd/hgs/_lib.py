@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libhgs.so")
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 INST_GRAD_STRIDE = 10          # floats per (tile, Gaussian) record of the backward scratch (HGS_INST_GRAD_STRIDE)
 ERR_CAPACITY = 5
 CUT_COST_ENTRIES, CUT_COST_ROWS = 0, 1
@@ -229,10 +229,14 @@ SIGNATURES = {
     "hgs_resid_fetch": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P,
                                   C.POINTER(ResidRows), C.c_int32, _P, C.c_int]),
     "hgs_resid_remap": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int]),
+    "hgs_resid_fetch_half": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P,
+                                       C.POINTER(ResidRows), C.c_int32, _P, C.c_int]),
+    "hgs_resid_pack_rows": (C.c_int, [C.POINTER(ResidRows), C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int]),
 }
 P2P_MAX_WORLD, P2P_HANDLE_BYTES, P2P_FLAG_BYTES = 8, 64, 256
 RESID_COUNTER_WORDS = 68
 RESID_HOST_ROW_FLOATS = 64     # packed host row: [0, 3M) SH, [48, 52) rotation, [52, 55) mean, [55, 58) scale, [58] opacity
+RESID_HOST_ROW_BYTES_HALF = 128   # half rows: 48 halves SH, 4 rotation, 3 scale, 1 opacity, 3 float32 mean, 4 bytes padding
 
 _lib = None
 

@@ -36,7 +36,13 @@ beside and behind the camera are neither fetched nor held and the budget goes to
 ``hgs.frustum.cut_to_budget(tau_min=tau, budget=B, cost="rows")``: the finest granularity at or above the request whose
 rows fit the budget is selected on the device from the node sizes ("Budget-exact cut"), so
 ``make_resident`` runs once, nothing is retried and ``Selection.tau`` does not depend on the views before.  It needs a
-hierarchy whose boxes nest; the default ``fit="regulate"`` is the path described above."""
+hierarchy whose boxes nest; the default ``fit="regulate"`` is the path described above.
+
+``rows="half"`` (constructor, ``from_hier_file``, ``from_device_arrays``) keeps the host rows in the 128-byte half layout
+of include/hgs.h (HGS_RESID_HOST_ROW_BYTES_HALF: SH, rotation, scale and opacity as IEEE half, the mean as float32): half
+the pinned memory and two 64-byte PCIe reads per row instead of four.  The fetch kernel widens the rows into the same
+float32 slot arrays, so everything behind the slots -- and the number of rows a budget buys -- is unchanged; what the
+viewer sees is ``round_rows_to_half`` of the attributes.  ``pack_rows_half`` is the layout's specification in numpy."""
 from __future__ import annotations
 
 import ctypes as C
@@ -58,6 +64,94 @@ def _host_array(shape, dtype=np.float32):
     buf = (C.c_char * max(n, 1)).from_address(p)
     arr = np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape))).reshape(shape)
     return arr, p
+
+
+HOST_ROW_BYTES = {"float": 4 * _lib.RESID_HOST_ROW_FLOATS, "half": _lib.RESID_HOST_ROW_BYTES_HALF}
+HALF_MAX = 65504.0
+
+
+def narrow_to_half(a) -> np.ndarray:
+    """float32 -> IEEE half bits (uint16) under the narrowing rule of include/hgs.h: round to nearest even with subnormal
+    halves kept; a finite value beyond +-65504 becomes +-65504; NaN becomes 0x7e00 under its sign; an infinity stays."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        bits = np.where(np.isfinite(a), np.clip(a, -HALF_MAX, HALF_MAX), a).astype(np.float16).view(np.uint16).copy()
+    nan = np.isnan(a)
+    bits[nan] = ((a.view(np.uint32)[nan] >> 16) & 0x8000).astype(np.uint16) | np.uint16(0x7E00)
+    return bits
+
+
+def widen_half(bits) -> np.ndarray:
+    """IEEE half bits (uint16) -> float32, exact."""
+    return np.ascontiguousarray(bits, dtype=np.uint16).view(np.float16).astype(np.float32)
+
+
+def _as_rows(means3D, shs, opacities, scales, rotations):
+    """The five attribute arrays (numpy or CPU tensors, float32) as 2-D float32 numpy arrays [G,3], [G,3M], [G,1], [G,3],
+    [G,4]; ValueError on another dtype or shape."""
+    _check_arrays(means3D, shs, opacities, scales, rotations, on_gpu=False)
+    G = int(means3D.shape[0])
+    a = lambda t: np.ascontiguousarray((t.detach() if torch.is_tensor(t) else t).reshape(G, -1))
+    return tuple(np.asarray(a(t)) for t in (means3D, shs, opacities, scales, rotations))
+
+
+def pack_rows_half(means3D, shs, opacities, scales, rotations) -> np.ndarray:
+    """The half host rows of include/hgs.h (HGS_RESID_HOST_ROW_BYTES_HALF) as uint8 [G, 128] -- the specification of the
+    layout, in numpy: halves [0, 3 M) SH in the slot array's order, [48, 52) rotation, [52, 55) scale, [55] opacity, then
+    the mean as three float32 at bytes 112..123; padding is zero.  Inputs: numpy arrays or CPU tensors, float32,
+    activated as the rasterizer takes them."""
+    m, sh, op, sc, rot = _as_rows(means3D, shs, opacities, scales, rotations)
+    G = m.shape[0]
+    out = np.zeros((G, HOST_ROW_BYTES["half"]), np.uint8)
+    halves = out[:, :112].view(np.uint16)
+    halves[:, :sh.shape[1]] = narrow_to_half(sh)
+    halves[:, 48:52] = narrow_to_half(rot)
+    halves[:, 52:55] = narrow_to_half(sc)
+    halves[:, 55:56] = narrow_to_half(op)
+    out[:, 112:124] = m.view(np.uint8)
+    return out
+
+
+def round_rows_to_half(means3D, shs, opacities, scales, rotations):
+    """The five arrays as a ``rows="half"`` viewer sees them: every value but the mean narrowed to half and widened again.
+    Shapes are kept; tensors in, CPU tensors out (numpy in, numpy out)."""
+    arrays = (means3D, shs, opacities, scales, rotations)
+    rows = _as_rows(*arrays)
+    out = []
+    for k, (t, r) in enumerate(zip(arrays, rows)):
+        r = (r.copy() if k == 0 else widen_half(narrow_to_half(r))).reshape(tuple(t.shape))
+        out.append(torch.from_numpy(r) if torch.is_tensor(t) else r)
+    return tuple(out)
+
+
+def _check_rows(rows):
+    if rows not in HOST_ROW_BYTES:
+        raise ValueError(f"rows must be 'float' or 'half', not {rows!r}")
+
+
+def _check_arrays(means3D, shs, opacities, scales, rotations, on_gpu):
+    """ValueError unless the five arrays are float32, agree on G, have the rasterizer's shapes and live where the
+    constructor expects them (``on_gpu``); nothing here touches the device.  -> (G, M)"""
+    named = dict(means3D=means3D, shs=shs, opacities=opacities, scales=scales, rotations=rotations)
+    for k, t in named.items():
+        if on_gpu and not (torch.is_tensor(t) and t.is_cuda):
+            raise ValueError(f"{k}: from_device_arrays takes GPU tensors (host arrays go to BudgetedHierarchy(...))")
+        if not on_gpu and torch.is_tensor(t) and t.is_cuda:
+            raise ValueError(f"{k}: a GPU tensor; this constructor copies CPU tensors (GPU tensors go to "
+                             f"BudgetedHierarchy.from_device_arrays)")
+        if not (torch.is_tensor(t) or isinstance(t, np.ndarray)):
+            raise ValueError(f"{k}: a tensor is expected, not {type(t).__name__}")
+        if t.dtype not in (torch.float32, np.float32):
+            raise ValueError(f"{k}: float32 expected, not {t.dtype}")
+    if means3D.ndim != 2 or means3D.shape[1] != 3:
+        raise ValueError(f"means3D: [G,3] expected, not {tuple(means3D.shape)}")
+    G = int(means3D.shape[0])
+    if shs.ndim != 3 or shs.shape[0] != G or shs.shape[2] != 3 or not 1 <= shs.shape[1] <= 16:
+        raise ValueError(f"shs: [{G},M,3] with M in 1..16 expected, not {tuple(shs.shape)}")
+    for k, shape in (("opacities", ((G,), (G, 1))), ("scales", ((G, 3),)), ("rotations", ((G, 4),))):
+        if tuple(named[k].shape) not in shape:
+            raise ValueError(f"{k}: {' or '.join(str(list(x)) for x in shape)} expected, not {tuple(named[k].shape)}")
+    return G, int(shs.shape[1])
 
 
 class _CutBuffers:
@@ -89,33 +183,51 @@ class Selection:
 
 class BudgetedHierarchy:
     def __init__(self, means3D, shs, opacities, scales, rotations, device, budget_mb: Optional[float] = None,
-                 budget_rows: Optional[int] = None, index_capacity: Optional[int] = None):
+                 budget_rows: Optional[int] = None, index_capacity: Optional[int] = None, rows: str = "float"):
         """The five attribute arrays as CPU tensors ([G,3], [G,M,3], [G] or [G,1], [G,3], [G,4], float32, already in the
         form the rasterizer takes: activated).  They are COPIED into pinned host memory.  ``budget_mb``: megabytes of
-        GPU memory for the attribute rows (the reference's ``--budget``); or ``budget_rows`` directly."""
+        GPU memory for the attribute rows (the reference's ``--budget``); or ``budget_rows`` directly.  ``rows``:
+        ``"float"`` -- 256-byte host rows -- or ``"half"`` -- 128-byte host rows (module docstring); the slots, and so the
+        rows a budget buys, are float32 either way."""
+        _check_rows(rows)
+        G, M = _check_arrays(means3D, shs, opacities, scales, rotations, on_gpu=False)
+        self._setup(G, M, device, budget_mb, budget_rows, index_capacity, rows)
+        if rows == "half":
+            step = 1 << 20              # narrowed block by block: no second copy of the whole hierarchy
+            for a in range(0, G, step):
+                self._rows[a:a + step] = pack_rows_half(*[t[a:a + step] for t in (means3D, shs, opacities, scales, rotations)])
+            return
+        f = lambda t, shape: t.detach().to("cpu", torch.float32).reshape(shape).numpy()
+        r = self._rows
+        r[:, :3 * M] = f(shs, (G, 3 * M))
+        r[:, 3 * M:48] = 0.0
+        r[:, 48:52] = f(rotations, (G, 4))
+        r[:, 52:55] = f(means3D, (G, 3))
+        r[:, 55:58] = f(scales, (G, 3))
+        r[:, 58] = f(opacities, (G,))
+        r[:, 59:] = 0.0
+
+    def _setup(self, G, M, device, budget_mb, budget_rows, index_capacity, rows):
+        """Everything but the contents of the host rows: the pinned rows, the slot arrays, the bookkeeping."""
         self.dev = torch.device(device)
         self.lib = _lib.lib()
-        G = int(means3D.shape[0])
-        M = int(shs.shape[1])
         self.G, self.M = G, M
-        self.row_bytes = 4 * (3 * M + 11)
+        self.rows_format = rows
+        self.row_bytes = 4 * (3 * M + 11)                   # bytes of a row in the SLOT arrays: what a budget is counted in
+        self.host_row_bytes = HOST_ROW_BYTES[rows]          # bytes of a row in pinned host memory, and over PCIe
         if budget_rows is None:
             if budget_mb is None:
                 raise ValueError("budget_mb or budget_rows")
             budget_rows = int(budget_mb * 1e6 // self.row_bytes)
         self.B = B = max(1, min(int(budget_rows), G))
-        R = _lib.RESID_HOST_ROW_FLOATS
         assert 3 * M <= 48
-        self._rows, self._rows_ptr = _host_array((G, R))           # the packed host rows (include/hgs.h)
-        f = lambda t, shape: t.detach().to("cpu", torch.float32).reshape(shape).numpy()
-        rows = self._rows
-        rows[:, :3 * M] = f(shs, (G, 3 * M))
-        rows[:, 3 * M:48] = 0.0
-        rows[:, 48:52] = f(rotations, (G, 4))
-        rows[:, 52:55] = f(means3D, (G, 3))
-        rows[:, 55:58] = f(scales, (G, 3))
-        rows[:, 58] = f(opacities, (G,))
-        rows[:, 59:] = 0.0
+        # the packed host rows (include/hgs.h): float32 [G, 64] or, rows="half", bytes [G, 128]
+        if rows == "half":
+            self._rows, self._rows_ptr = _host_array((G, self.host_row_bytes), np.uint8)
+            self._fetch, self._fetch_name = self.lib.hgs_resid_fetch_half, "hgs_resid_fetch_half"
+        else:
+            self._rows, self._rows_ptr = _host_array((G, _lib.RESID_HOST_ROW_FLOATS))
+            self._fetch, self._fetch_name = self.lib.hgs_resid_fetch, "hgs_resid_fetch"
         f32 = dict(dtype=torch.float32, device=self.dev)
         self.means3D = torch.zeros(B, 3, **f32)
         self.shs = torch.zeros(B, M, 3, **f32)
@@ -151,15 +263,43 @@ class BudgetedHierarchy:
                                            (self.means3D, self.shs, self.opacities, self.scales, self.rotations)])
 
     @classmethod
-    def from_hier_file(cls, path: str, device, budget_mb: Optional[float] = None, budget_rows: Optional[int] = None):
+    def from_device_arrays(cls, means3D, shs, opacities, scales, rotations, *, rows: str = "float",
+                           budget_mb: Optional[float] = None, budget_rows: Optional[int] = None,
+                           index_capacity: Optional[int] = None):
+        """The constructor for attributes that are already on the GPU (a hierarchy built or merged there): float32 GPU
+        tensors of the constructor's shapes, on one device.  The host rows are written by a kernel through the mapped
+        pointer (hgs_resid_pack_rows) in either format -- the same bytes the constructor writes -- and no float copy of
+        the attributes is made on the host."""
+        _check_rows(rows)
+        G, M = _check_arrays(means3D, shs, opacities, scales, rotations, on_gpu=True)
+        dev = means3D.device
+        if any(t.device != dev for t in (shs, opacities, scales, rotations)):
+            raise ValueError("from_device_arrays: the five tensors must live on one device")
+        self = cls.__new__(cls)
+        self._setup(G, M, dev, budget_mb, budget_rows, index_capacity, rows)
+        src = [t.detach().contiguous() for t in (means3D, shs, opacities, scales, rotations)]
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            _lib.check(self.lib.hgs_resid_pack_rows(C.byref(_lib.ResidRows(*[C.c_void_p(t.data_ptr()) for t in src])), G, M,
+                                                    int(rows == "half"), C.c_void_p(self._rows_ptr),
+                                                    C.c_void_p(stream.cuda_stream), dev.index or 0), "hgs_resid_pack_rows")
+            stream.synchronize()        # the host reads the rows (culling balls) and ``src`` may be freed
+        return self
+
+    @classmethod
+    def from_hier_file(cls, path: str, device, budget_mb: Optional[float] = None, budget_rows: Optional[int] = None,
+                       rows: str = "float"):
         """A ``.hier`` file (gaussian_hierarchy._C.load_hierarchy, scene/gaussian_model.py:329) straight into the
         budgeted form, with the activations the reference applies to a loaded hierarchy: opacity = |alpha|
         (scene/gaussian_model.py:393), scales = exp(log-scales), rotations normalised (scene/gaussian_model.py:108-116).
-        Returns (BudgetedHierarchy, nodes, boxes) with nodes / boxes on ``device`` (they stay resident: 60 B per node)."""
+        Returns (BudgetedHierarchy, nodes, boxes) with nodes / boxes on ``device`` (they stay resident: 60 B per node).
+        ``rows="half"``: 128-byte host rows, narrowed from the ACTIVATED values (a file written with ``half=True`` stores
+        log-scales as halves; its activated scales are narrowed once more here)."""
         from gaussian_hierarchy._C import load_hierarchy
+        _check_rows(rows)
         xyz, shs, alpha, log_scales, rots, nodes, boxes = load_hierarchy(path)
         bh = cls(xyz, shs, alpha.abs(), torch.exp(log_scales), torch.nn.functional.normalize(rots), device,
-                 budget_mb=budget_mb, budget_rows=budget_rows)
+                 budget_mb=budget_mb, budget_rows=budget_rows, rows=rows)
         return bh, nodes.to(device), boxes.to(device)
 
     def __del__(self):
@@ -260,6 +400,11 @@ class BudgetedHierarchy:
                     self.stats["evictions"] += int(top.value) - self.free_top
                     self.free_top = int(top.value)
                 if _best_effort and m > self.free_top:
+                    # The mark pass queues rows in the order its atomics complete.  A pass that can only bring in PART of
+                    # the list takes the lowest rows, not whichever were queued first: which rows are resident afterwards
+                    # (and so what later views fetch and evict) is then a function of the views alone.
+                    if m <= 4096:
+                        self.miss_ids[:m] = torch.sort(self.miss_ids[:m]).values
                     unqueue(self.free_top)
                     m = self.free_top
                     if m == 0:
@@ -267,10 +412,9 @@ class BudgetedHierarchy:
                 if self.profile_fetch:
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record()
-                _lib.check(self.lib.hgs_resid_fetch(p(self.miss_ids), m, p(self.free_list), self.free_top, p(self.slot_of),
-                                                    p(self.id_of_slot), p(self.stamp), self.frame,
-                                                    C.c_void_p(self._rows_ptr), C.byref(self._slot_rows), self.M, s, dev_i),
-                           "hgs_resid_fetch")
+                _lib.check(self._fetch(p(self.miss_ids), m, p(self.free_list), self.free_top, p(self.slot_of),
+                                       p(self.id_of_slot), p(self.stamp), self.frame, C.c_void_p(self._rows_ptr),
+                                       C.byref(self._slot_rows), self.M, s, dev_i), self._fetch_name)
                 if self.profile_fetch:
                     e1.record()
                     self.fetch_events.append((m, e0, e1))
@@ -280,12 +424,12 @@ class BudgetedHierarchy:
             self.free_top -= m
             if _best_effort and m < int(miss.value):
                 self.stats["rows_fetched"] += m
-                self.stats["bytes_fetched"] += m * self.row_bytes
+                self.stats["bytes_fetched"] += m * self.host_row_bytes
                 return None, None, m            # (part of the view is still missing: no slot indices)
             _lib.check(self.lib.hgs_resid_remap(p(render_indices), p(parent_indices), p(weights), n, p(self.slot_of),
                                                 p(ro_buf), p(po_buf), s, dev_i), "hgs_resid_remap")
             self.stats["rows_fetched"] += m
-            self.stats["bytes_fetched"] += m * self.row_bytes
+            self.stats["bytes_fetched"] += m * self.host_row_bytes
         return ro_buf[:n], po_buf[:n], m
 
     @staticmethod
@@ -301,8 +445,12 @@ class BudgetedHierarchy:
         key = (nodes.data_ptr(), int(nodes.shape[0]), nodes._version)
         if self._bounds is None or self._bounds[0] != key:
             from .frustum import cull_bounds
-            means = torch.from_numpy(np.ascontiguousarray(self._rows[:, 52:55])).to(self.dev)
-            scales = torch.from_numpy(np.ascontiguousarray(self._rows[:, 55:58])).to(self.dev)
+            if self.rows_format == "half":
+                means = np.ascontiguousarray(self._rows[:, 112:124]).view(np.float32)
+                scales = widen_half(np.ascontiguousarray(self._rows[:, 104:110]).view(np.uint16))
+            else:
+                means, scales = np.ascontiguousarray(self._rows[:, 52:55]), np.ascontiguousarray(self._rows[:, 55:58])
+            means, scales = torch.from_numpy(means).to(self.dev), torch.from_numpy(scales).to(self.dev)
             self._bounds = (key, cull_bounds(nodes, means, scales))
             del means, scales
         return self._bounds[1]

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define HGS_ABI_VERSION 13
+#define HGS_ABI_VERSION 14
 #define HGS_TILE 16
 #define HGS_INST_GRAD_STRIDE 10 /* floats per (tile, Gaussian) instance in the backward scratch (40 bytes: the ten sums) */
 
@@ -446,13 +446,15 @@ enum {
   HGS_HIER_UPSTREAM = 0,      /* header-less layout of the gaussian-hierarchy tools: int P, pos, rot, log-scale, alpha,
                                * sh[16][3], int N, nodes, boxes (restated from the public repository; see hier_io.cpp) */
   HGS_HIER_PRIVATE = 1,       /* "HGSHIER1" + P, N, M: any SH count */
-  HGS_HIER_UPSTREAM_HALF = 2  /* upstream layout with P < 0: rot / scale / alpha / sh stored as IEEE half (read only) */
+  HGS_HIER_UPSTREAM_HALF = 2  /* upstream layout with P < 0 (the file stores -P): rot / log-scale / alpha / sh stored as
+                               * IEEE half under the narrowing rule of HGS_RESID_HOST_ROW_BYTES_HALF below, positions
+                               * float32: 124 bytes per Gaussian instead of 236.  M = 16 only */
 };
 typedef struct hgs_hier_host {
   int32_t P;      /* Gaussians */
   int32_t N;      /* nodes */
   int32_t M;      /* SH coefficients per Gaussian (16) */
-  int32_t reserved; /* layout: hgs_hier_write takes HGS_HIER_UPSTREAM or HGS_HIER_PRIVATE; hgs_hier_load reports what it found */
+  int32_t reserved; /* layout: one of the HGS_HIER_* above for hgs_hier_write; hgs_hier_load reports what it found */
   float* xyz;         /* [P,3] */
   float* shs;         /* [P,M,3] */
   float* alpha;       /* [P] activated opacity */
@@ -815,6 +817,32 @@ int hgs_resid_fetch(const int32_t* miss_ids, uint32_t m, const int32_t* free_lis
                     const hgs_resid_rows* slot_rows, int32_t M, hgs_stream_t stream, int device);
 int hgs_resid_remap(const int32_t* render_indices, const int32_t* parent_indices, const float* weights, int32_t n,
                     const int32_t* slot_of, int32_t* ro, int32_t* po, hgs_stream_t stream, int device);
+
+/* Half-precision host rows (opt-in): 128 bytes per Gaussian = two 64-byte PCIe reads and half the pinned memory.  The
+ * slot arrays on the device stay float32; only the host side and the bus carry halves.  Eight 16-byte chunks:
+ *   bytes   0 ..  95   48 halves: SH coefficients [0, 3 M) in the slot array's order, the rest padding
+ *   bytes  96 .. 103   rotation, 4 halves
+ *   bytes 104 .. 109   scale, 3 halves (activated, as the float rows hold it)
+ *   bytes 110 .. 111   opacity, 1 half
+ *   bytes 112 .. 123   mean, 3 float32 (never narrowed: scene coordinates need the mantissa)
+ *   bytes 124 .. 127   padding
+ * Narrowing rule, wherever this library turns a float into a half (hgs_resid_pack_rows, hgs_hier_write with
+ * HGS_HIER_UPSTREAM_HALF, hgs.residency.pack_rows_half): round to nearest even, subnormal halves kept; a FINITE value
+ * beyond +-65504 becomes +-65504 -- narrowing never makes an infinity (an infinite SH coefficient would turn into NaN
+ * pixels); NaN stays NaN (the quiet NaN 0x7e00 under its sign) and an infinity stays an infinity.  Widening is exact.
+ *   hgs_resid_fetch_half  hgs_resid_fetch on rows of this layout: same arguments, refusals and slot assignment; the
+ *                         kernel reads the half rows over PCIe and widens them into the float slot arrays.
+ *   hgs_resid_pack_rows   device attribute arrays (`src`, G rows, activated) -> packed host rows, written by the kernel
+ *                         through the mapped pointer: `half` = 1 this layout, 0 the float layout of
+ *                         HGS_RESID_HOST_ROW_FLOATS; padding is written as zeros in both.  host_rows_packed: G rows
+ *                         from hgs_host_alloc.  Ordered on `stream`: the host may read the rows once it has waited for
+ *                         the stream.  G = 0 returns without a HIP call. */
+#define HGS_RESID_HOST_ROW_BYTES_HALF 128
+int hgs_resid_fetch_half(const int32_t* miss_ids, uint32_t m, const int32_t* free_list, uint32_t free_top, int32_t* slot_of,
+                         int32_t* id_of_slot, uint32_t* stamp, uint32_t frame, const void* host_rows_packed,
+                         const hgs_resid_rows* slot_rows, int32_t M, hgs_stream_t stream, int device);
+int hgs_resid_pack_rows(const hgs_resid_rows* src, int64_t G, int32_t M, int32_t half, void* host_rows_packed,
+                        hgs_stream_t stream, int device);
 
 #ifdef __cplusplus
 }
