@@ -11,7 +11,7 @@
 //
 // HBM-bound streaming: 16 B read + 12 B written per updated element; one thread per element, consecutive
 // threads walk consecutive floats of a row so every access is a contiguous run of row_len floats.
-#include "common.h"
+#include "adam_update.h"
 
 namespace hgs {
 namespace {
@@ -40,15 +40,12 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamLaunch L, int n_tensors, 
   if (MODE == 1) row = rows[r];
   if (MODE == 2 && row_mask_grad[r] == 0.0f) return;
   const int64_t idx = row * T.row_len + c;
-  float g = T.grad[idx];
-  const float p = T.param[idx];
-  if (T.weight_decay != 0.0f) g = fmaf(T.weight_decay, p, g);
-  const float m = fmaf(T.one_minus_beta1, g, T.exp_avg[idx] * T.beta1);
-  const float v = fmaf(T.one_minus_beta2 * g, g, T.exp_avg_sq[idx] * T.beta2);
-  const float denom = sqrtf(v) / T.bias_correction2_sqrt + T.eps;
+  const float g = T.grad[idx];
+  float p = T.param[idx], m = T.exp_avg[idx], v = T.exp_avg_sq[idx];
+  adam_update(T, g, p, m, v);
   T.exp_avg[idx] = m;
   T.exp_avg_sq[idx] = v;
-  T.param[idx] = fmaf(-T.step_size, m / denom, p);
+  T.param[idx] = p;
 }
 
 }  // namespace

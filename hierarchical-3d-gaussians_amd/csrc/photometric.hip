@@ -7,6 +7,10 @@
 //   L1 = mean |x - gt|,  S = SSIM(x, gt) as ssim.hip,  D = mean |(d - d_mono) m_d|
 //   loss = (1 - lambda) L1 + lambda (1 - S) + depth_weight D
 //
+// The SSIM tile -- staging, the four filter passes, S and its three maps, the workgroup sums -- is ssim_tile.h, the text
+// ssim.hip instantiates: S, the maps and the SSIM part of the gradient have ssim.hip's bits.  This file holds what the
+// fused loss adds: the exposure, the clamp and the mask while staging, the L1 and depth terms, the exposure partials.
+//
 //   forward    photo_fwd_kernel: one workgroup per 32x16 tile of one IMAGE (ssim.hip has one per plane): the exposure
 //              mixes channels, so the workgroup loops over the output channels of its tile and re-stages ssim.hip's two
 //              LDS buffers -- x_j, computed while staging from all channels of r, and gt_j -- per channel.  LDS stays at
@@ -22,32 +26,12 @@
 //              sign(q) m_d.
 //   reduce     photo_exposure_reduce_kernel: workgroup (n, k) adds image n's partials of exposure entry k in a fixed
 //              order.  No atomics anywhere: two calls give bit-identical results.
-#include "common.h"
-
-#include <math.h>
+#include "ssim_tile.h"
 
 namespace hgs {
 namespace {
 
-// The tiling of ssim.hip, restated: its kernels must not change with this file.
-constexpr int kTaps = 11;
-constexpr int kHalo = kTaps / 2;
-constexpr int kTW = 32;
-constexpr int kTH = 16;
-constexpr int kIW = kTW + 2 * kHalo;
-constexpr int kIH = kTH + 2 * kHalo;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kRowsPerPass = kThreads / kTW;
-constexpr int kRows = kTH / kRowsPerPass;      // output pixels per thread (2)
-constexpr int kReduceThreads = 1024;
 constexpr int kExp = 12;                       // entries of a 3x4 exposure
-constexpr float kC1 = 0.01f * 0.01f;
-constexpr float kC2 = 0.03f * 0.03f;
-
-struct Window {
-  float w[kTaps];
-};
 
 struct Images {
   const float* r;       // [N,C,H,W]
@@ -59,24 +43,6 @@ struct Images {
   const float* md;
   int C, H, W, tiles_x, tiles_per_image, clamp;
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// One workgroup's sum in a fixed order (every lane's value, then the wave sums in wave order), valid in thread 0.
-__device__ __forceinline__ double block_sum(double v, double* wsum) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) wsum[wave] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += wsum[i];
-  return s;
-}
 
 // K sums of a kThreads workgroup at once: thread k < K adds the wave sums of value k in wave order and stores
 // out[k * stride + blockIdx.x].
@@ -168,20 +134,11 @@ __global__ __launch_bounds__(kThreads) void photo_fwd_kernel(Images im, Window w
     const ExpCol ec = exp_col<EXP>(En, j);
     // every thread is past the previous channel's horizontal pass (the barrier behind it) and has taken its own
     // pixels of s1 / s2 into registers before that barrier: the buffers are free
-    for (int i = tid; i < kIH * kIW; i += kThreads) {
-      const int r = i / kIW, cc = i - r * kIW;
-      const int gy = t.y0 - kHalo + r, gx = t.x0 - kHalo + cc;
-      const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-      const int64_t o = (int64_t)gy * W + gx;
-      float xv = 0.f, gv = 0.f;
-      if (in) {
-        xv = clamped(exposed<EXP>(rn, hw, o, j, ec), im.clamp);
-        if (mn) xv *= mn[o];
-        gv = gn[j * hw + o];
-      }
-      s1[r][cc] = xv;
-      s2[r][cc] = gv;
-    }
+    stage_pair(s1, s2, t.y0, t.x0, H, W, [&](int64_t o, float& xv, float& gv) {
+      xv = clamped(exposed<EXP>(rn, hw, o, j, ec), im.clamp);
+      if (mn) xv *= mn[o];
+      gv = gn[j * hw + o];
+    });
     __syncthreads();
 
     float own_x[kRows], own_g[kRows];
@@ -190,24 +147,7 @@ __global__ __launch_bounds__(kThreads) void photo_fwd_kernel(Images im, Window w
       own_x[k] = s1[r0 + k * kRowsPerPass + kHalo][c + kHalo];
       own_g[k] = s2[r0 + k * kRowsPerPass + kHalo][c + kHalo];
     }
-    for (int i = tid; i < kIH * kTW; i += kThreads) {
-      const int r = i / kTW, cc = i - r * kTW;
-      float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f, m4 = 0.f;
-#pragma unroll
-      for (int k = 0; k < kTaps; ++k) {
-        const float a = s1[r][cc + k], b = s2[r][cc + k], w = win.w[k];
-        m0 += w * a;
-        m1 += w * b;
-        m2 += w * (a * a);
-        m3 += w * (b * b);
-        m4 += w * (a * b);
-      }
-      hm[0][r][cc] = m0;
-      hm[1][r][cc] = m1;
-      hm[2][r][cc] = m2;
-      hm[3][r][cc] = m3;
-      hm[4][r][cc] = m4;
-    }
+    filter_rows_moments(s1, s2, hm, win);
     __syncthreads();
 
     const int64_t base = (t.n * im.C + j) * hw;
@@ -215,35 +155,12 @@ __global__ __launch_bounds__(kThreads) void photo_fwd_kernel(Images im, Window w
     for (int k = 0; k < kRows; ++k) {
       const int rr = r0 + k * kRowsPerPass;
       const int y = t.y0 + rr;
-      float mu1 = 0.f, mu2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-      for (int q = 0; q < kTaps; ++q) {
-        const float w = win.w[q];
-        mu1 += w * hm[0][rr + q][c];
-        mu2 += w * hm[1][rr + q][c];
-        e11 += w * hm[2][rr + q][c];
-        e22 += w * hm[3][rr + q][c];
-        e12 += w * hm[4][rr + q][c];
-      }
+      float f[5];
+      filter_column(hm, rr, c, win, f);
       if (y < H && x < W) {
-        // one fused multiply-add per (co)variance, as ssim.hip: x == gt gives N2 == D2 exactly
-        const float sg1 = fmaf(-mu1, mu1, e11), sg2 = fmaf(-mu2, mu2, e22), sg12 = fmaf(-mu1, mu2, e12);
-        const float n1 = 2.f * mu1 * mu2 + kC1, n2 = 2.f * sg12 + kC2;
-        const float d1 = mu1 * mu1 + mu2 * mu2 + kC1, d2 = sg1 + sg2 + kC2;
-        const float inv = 1.f / (d1 * d2);
-        const float S = n1 * n2 * inv;
+        const int64_t o = base + (int64_t)y * W + x;
         acc[0] += (double)fabsf(own_x[k] - own_g[k]);
-        acc[1] += (double)S;
-        if (maps) {
-          const float B = -S / d2;
-          const float Cc = 2.f * n1 * inv;
-          const float dmu1 = 2.f * mu2 * n2 * inv - 2.f * mu1 * S / d1;
-          const float A = dmu1 - 2.f * mu1 * B - mu2 * Cc;
-          const int64_t o = base + (int64_t)y * W + x;
-          maps[o] = A;
-          maps[total + o] = B;
-          maps[2 * total + o] = Cc;
-        }
+        acc[1] += (double)ssim_pixel(f, maps ? maps + o : nullptr, total);
       }
     }
   }
@@ -326,50 +243,23 @@ __global__ __launch_bounds__(kThreads) void photo_bwd_kernel(Images im, Window w
   auto channel = [&](int j, float (&du_j)[kRows]) {
     const float* mj = maps + (t.n * im.C + j) * hw;
     // hm of the previous channel may still be read; sm is not (a barrier separates its last read from here)
-    for (int i = tid; i < kIH * kIW; i += kThreads) {
-      const int r = i / kIW, cc = i - r * kIW;
-      const int gy = t.y0 - kHalo + r, gx = t.x0 - kHalo + cc;
-      const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-      const int64_t o = (int64_t)gy * W + gx;
-      sm[0][r][cc] = in ? mj[o] : 0.f;
-      sm[1][r][cc] = in ? mj[total + o] : 0.f;
-      sm[2][r][cc] = in ? mj[2 * total + o] : 0.f;
-    }
+    stage_maps(sm, mj, total, t.y0, t.x0, H, W);
     __syncthreads();
-    for (int i = tid; i < kIH * kTW; i += kThreads) {
-      const int r = i / kTW, cc = i - r * kTW;
-      float m0 = 0.f, m1 = 0.f, m2 = 0.f;
-#pragma unroll
-      for (int k = 0; k < kTaps; ++k) {
-        const float w = win.w[k];
-        m0 += w * sm[0][r][cc + k];
-        m1 += w * sm[1][r][cc + k];
-        m2 += w * sm[2][r][cc + k];
-      }
-      hm[0][r][cc] = m0;
-      hm[1][r][cc] = m1;
-      hm[2][r][cc] = m2;
-    }
+    filter_rows_maps(sm, hm, win);
     __syncthreads();
     const ExpCol ec = exp_col<EXP>(En, j);
 #pragma unroll
     for (int k = 0; k < kRows; ++k) {
       const int rr = r0 + k * kRowsPerPass;
-      float fa = 0.f, fb = 0.f, fc = 0.f;
-#pragma unroll
-      for (int q = 0; q < kTaps; ++q) {
-        const float w = win.w[q];
-        fa += w * hm[0][rr + q][c];
-        fb += w * hm[1][rr + q][c];
-        fc += w * hm[2][rr + q][c];
-      }
+      float f[3];
+      filter_column(hm, rr, c, win, f);
       du_j[k] = 0.f;
       if (own[k]) {
         const float u = exposed<EXP>(rn, hw, off[k], j, ec);
         const bool pass = !im.clamp || (u >= 0.f && u <= 1.f);
         const float xv = clamped(u, im.clamp) * mk[k];
         const float gv = gn[j * hw + off[k]];
-        const float dx = cs * (fa + 2.f * xv * fb + gv * fc) + cl1 * sign_of(xv - gv);
+        const float dx = cs * ssim_pixel_grad(f, xv, gv) + cl1 * sign_of(xv - gv);
         du_j[k] = pass ? dx * mk[k] : 0.f;
       }
     }
@@ -438,18 +328,6 @@ __global__ __launch_bounds__(kThreads) void photo_exposure_reduce_kernel(const d
   for (int i = threadIdx.x; i < tiles_per_image; i += kThreads) v += p[i];
   const double s = block_sum(v, wsum);
   if (threadIdx.x == 0) grad_E[blockIdx.x] = (float)s;
-}
-
-Window gaussian_window() {
-  double g[kTaps], sum = 0.0;
-  for (int k = 0; k < kTaps; ++k) {
-    const double d = k - kHalo;
-    g[k] = exp(-d * d / (2.0 * 1.5 * 1.5));
-    sum += g[k];
-  }
-  Window w;
-  for (int k = 0; k < kTaps; ++k) w.w[k] = (float)(g[k] / sum);
-  return w;
 }
 
 struct Grid {

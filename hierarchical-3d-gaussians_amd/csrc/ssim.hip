@@ -15,46 +15,14 @@
 //   backward   ssim_bwd_kernel: the same tiling.  grad_x1(q) = g (F[A](q) + 2 x1(q) F[B](q) + x2(q) F[Cc](q)), where
 //              F is the same (symmetric) window and A, B, Cc are zero outside the image; g is the upstream gradient
 //              over the number of pixels averaged.
-#include "common.h"
+// The tile itself (constants, window, staging, the filter passes, the per-pixel formula, the workgroup sums) is
+// ssim_tile.h, shared with photometric.hip; this file holds the kernels around it, the reduction and the launchers.
+#include "ssim_tile.h"
 
 namespace hgs {
 namespace {
 
-constexpr int kTaps = 11;
-constexpr int kHalo = kTaps / 2;
-constexpr int kTW = 32;                 // output tile width (one column per lane of a half-wave)
-constexpr int kTH = 16;                 // output tile height
-constexpr int kIW = kTW + 2 * kHalo;    // staged width (42)
-constexpr int kIH = kTH + 2 * kHalo;    // staged height (26)
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kRowsPerPass = kThreads / kTW;   // 8 output rows per vertical step
-constexpr int kReduceThreads = 1024;
 constexpr int64_t kMaxTiles = (int64_t)UINT32_MAX / kThreads;   // 16 777 215 workgroups of a 1-D grid
-constexpr float kC1 = 0.01f * 0.01f;
-constexpr float kC2 = 0.03f * 0.03f;
-
-struct Window {
-  float w[kTaps];
-};
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// The block's partial in a fixed order: every lane's value, the wave sums in wave order.
-__device__ __forceinline__ double block_sum(double v, double* wsum) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) wsum[wave] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += wsum[i];
-  return s;
-}
 
 struct TileCoords {
   int64_t plane;    // n * C + c
@@ -84,34 +52,9 @@ __global__ __launch_bounds__(kThreads) void ssim_fwd_kernel(const float* __restr
   const float* p2 = x2 + base;
   const int tid = threadIdx.x;
 
-  for (int i = tid; i < kIH * kIW; i += kThreads) {
-    const int r = i / kIW, c = i - r * kIW;
-    const int gy = t.y0 - kHalo + r, gx = t.x0 - kHalo + c;
-    const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-    const int64_t o = (int64_t)gy * W + gx;
-    s1[r][c] = in ? p1[o] : 0.f;
-    s2[r][c] = in ? p2[o] : 0.f;
-  }
+  stage_pair(s1, s2, t.y0, t.x0, H, W, [&](int64_t o, float& a, float& b) { a = p1[o], b = p2[o]; });
   __syncthreads();
-
-  for (int i = tid; i < kIH * kTW; i += kThreads) {
-    const int r = i / kTW, c = i - r * kTW;
-    float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f, m4 = 0.f;
-#pragma unroll
-    for (int k = 0; k < kTaps; ++k) {
-      const float a = s1[r][c + k], b = s2[r][c + k], w = win.w[k];
-      m0 += w * a;
-      m1 += w * b;
-      m2 += w * (a * a);
-      m3 += w * (b * b);
-      m4 += w * (a * b);
-    }
-    hm[0][r][c] = m0;
-    hm[1][r][c] = m1;
-    hm[2][r][c] = m2;
-    hm[3][r][c] = m3;
-    hm[4][r][c] = m4;
-  }
+  filter_rows_moments(s1, s2, hm, win);
   __syncthreads();
 
   const int c = tid % kTW;
@@ -120,36 +63,11 @@ __global__ __launch_bounds__(kThreads) void ssim_fwd_kernel(const float* __restr
 #pragma unroll
   for (int rr = tid / kTW; rr < kTH; rr += kRowsPerPass) {
     const int y = t.y0 + rr;
-    float mu1 = 0.f, mu2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-    for (int k = 0; k < kTaps; ++k) {
-      const float w = win.w[k];
-      mu1 += w * hm[0][rr + k][c];
-      mu2 += w * hm[1][rr + k][c];
-      e11 += w * hm[2][rr + k][c];
-      e22 += w * hm[3][rr + k][c];
-      e12 += w * hm[4][rr + k][c];
-    }
+    float f[5];
+    filter_column(hm, rr, c, win, f);
     if (y < H && x < W) {
-      // One fused multiply-add each, so that the three (co)variances round alike: with x1 == x2 they are equal and
-      // N2 == D2 exactly.  Written as e - mu * mu, the compiler may round one product (mu1 * mu1 is shared with D1)
-      // and fuse another; in a flat region that difference, relative to C2, put S of identical images 6e-6 from 1.
-      const float sg1 = fmaf(-mu1, mu1, e11), sg2 = fmaf(-mu2, mu2, e22), sg12 = fmaf(-mu1, mu2, e12);
-      const float n1 = 2.f * mu1 * mu2 + kC1, n2 = 2.f * sg12 + kC2;
-      const float d1 = mu1 * mu1 + mu2 * mu2 + kC1, d2 = sg1 + sg2 + kC2;
-      const float inv = 1.f / (d1 * d2);
-      const float S = n1 * n2 * inv;
-      acc += (double)S;
-      if (maps) {
-        const float B = -S / d2;
-        const float Cc = 2.f * n1 * inv;
-        const float dmu1 = 2.f * mu2 * n2 * inv - 2.f * mu1 * S / d1;
-        const float A = dmu1 - 2.f * mu1 * B - mu2 * Cc;
-        const int64_t o = base + (int64_t)y * W + x;
-        maps[o] = A;
-        maps[total + o] = B;
-        maps[2 * total + o] = Cc;
-      }
+      const int64_t o = base + (int64_t)y * W + x;
+      acc += (double)ssim_pixel(f, maps ? maps + o : nullptr, total);
     }
   }
   const double s = block_sum(acc, wsum);
@@ -188,31 +106,9 @@ __global__ __launch_bounds__(kThreads) void ssim_bwd_kernel(const float* __restr
   const int64_t base = t.plane * (int64_t)H * W;
   const int tid = threadIdx.x;
 
-  for (int i = tid; i < kIH * kIW; i += kThreads) {
-    const int r = i / kIW, c = i - r * kIW;
-    const int gy = t.y0 - kHalo + r, gx = t.x0 - kHalo + c;
-    const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-    const int64_t o = base + (int64_t)gy * W + gx;
-    sm[0][r][c] = in ? maps[o] : 0.f;
-    sm[1][r][c] = in ? maps[total + o] : 0.f;
-    sm[2][r][c] = in ? maps[2 * total + o] : 0.f;
-  }
+  stage_maps(sm, maps + base, total, t.y0, t.x0, H, W);
   __syncthreads();
-
-  for (int i = tid; i < kIH * kTW; i += kThreads) {
-    const int r = i / kTW, c = i - r * kTW;
-    float m0 = 0.f, m1 = 0.f, m2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < kTaps; ++k) {
-      const float w = win.w[k];
-      m0 += w * sm[0][r][c + k];
-      m1 += w * sm[1][r][c + k];
-      m2 += w * sm[2][r][c + k];
-    }
-    hm[0][r][c] = m0;
-    hm[1][r][c] = m1;
-    hm[2][r][c] = m2;
-  }
+  filter_rows_maps(sm, hm, win);
   __syncthreads();
 
   const int64_t n = t.plane / C;
@@ -223,29 +119,11 @@ __global__ __launch_bounds__(kThreads) void ssim_bwd_kernel(const float* __restr
   for (int rr = tid / kTW; rr < kTH; rr += kRowsPerPass) {
     const int y = t.y0 + rr;
     if (y >= H || x >= W) continue;
-    float fa = 0.f, fb = 0.f, fc = 0.f;
-#pragma unroll
-    for (int k = 0; k < kTaps; ++k) {
-      const float w = win.w[k];
-      fa += w * hm[0][rr + k][c];
-      fb += w * hm[1][rr + k][c];
-      fc += w * hm[2][rr + k][c];
-    }
+    float f[3];
+    filter_column(hm, rr, c, win, f);
     const int64_t o = base + (int64_t)y * W + x;
-    grad[o] = gs * (fa + 2.f * x1[o] * fb + x2[o] * fc);
+    grad[o] = gs * ssim_pixel_grad(f, x1[o], x2[o]);
   }
-}
-
-Window gaussian_window() {
-  double g[kTaps], sum = 0.0;
-  for (int k = 0; k < kTaps; ++k) {
-    const double d = k - kHalo;
-    g[k] = exp(-d * d / (2.0 * 1.5 * 1.5));
-    sum += g[k];
-  }
-  Window w;
-  for (int k = 0; k < kTaps; ++k) w.w[k] = (float)(g[k] / sum);
-  return w;
 }
 
 struct Grid {

@@ -6,13 +6,13 @@
 // the clamp on the freshly updated scaling row while it is in registers).  include/hgs.h states the rule.
 //
 // Nothing comes back to the host: the empty-`relevant` case (scene/OurAdam.py:214 takes the dense path) is decided
-// inside the apply kernel from the word.  The Adam update restates adam.hip's expressions, fmaf for fmaf: selected rows
-// are bit for bit what hgs_adam_step gives on a gradient whose locked rows were zeroed.
+// inside the apply kernel from the word.  The Adam update is adam.hip's (adam_update.h holds it once): selected rows are bit
+// for bit what hgs_adam_step gives on a gradient whose locked rows were zeroed.
 //
 // select: 4 B (opacity gradient) read and 1 B written per model row, + 4 B (radius) per rendered row and, per visible
 // row, 8 B of means2D gradient and three 4 B read-modify-writes.  apply: 16 B read + 12 B written per updated element
 // (adam.hip's 28 B) + the class byte of its row; with the clamp, every scaling row is read.
-#include "common.h"
+#include "adam_update.h"
 
 namespace hgs {
 namespace {
@@ -83,15 +83,6 @@ struct StepLaunch {
   hgs_step_tensor t[kMaxTensors];
   uint32_t first_block[kMaxTensors + 1];   // block range of every tensor
 };
-
-// adam.hip's update, restated
-__device__ __forceinline__ void adam_update(const hgs_adam_tensor& T, float g, float& p, float& m, float& v) {
-  if (T.weight_decay != 0.0f) g = fmaf(T.weight_decay, p, g);
-  m = fmaf(T.one_minus_beta1, g, m * T.beta1);
-  v = fmaf(T.one_minus_beta2 * g, g, v * T.beta2);
-  const float denom = sqrtf(v) / T.bias_correction2_sqrt + T.eps;
-  p = fmaf(-T.step_size, m / denom, p);
-}
 
 template <typename IDX>   // element index type
 __global__ __launch_bounds__(256) void step_apply_kernel(StepLaunch L, int n_tensors, int64_t P, int select_all, int clamp,
