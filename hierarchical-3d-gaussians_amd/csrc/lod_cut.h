@@ -1,8 +1,8 @@
-// The rules of the hierarchy cut, each ONCE, for the three calls that must agree bit for bit: expand_to_size +
-// get_interpolation_weights (lod.hip), the frustum-culled cut (lod_frustum.hip) and the budget-exact cut
-// (lod_budget.hip).  Included by those three files only.  What decides -- the size of a node, the cull, the weight -- is
+// The rules of the hierarchy cut, each ONCE, for the four calls that must agree bit for bit: expand_to_size +
+// get_interpolation_weights (lod.hip), the frustum-culled cut (lod_frustum.hip), the budget-exact cut
+// (lod_budget.hip) and the cut for several views (lod_views.hip).  Included by those four files only.  What decides -- the size of a node, the cull, the weight -- is
 // float32 in a fixed operation order with contraction off (oracle/lod_oracle.py, tests/frustum_spec.py and
-// tests/budget_cut_spec.py restate it); the rest is the shape the three calls share: per-node emission counts,
+// tests/budget_cut_spec.py restate it); the rest is the shape the calls share: per-node emission counts,
 // workgroup sums, the chained scan of common.h, an emit pass in ascending node order.
 #pragma once
 #include "common.h"
@@ -76,6 +76,39 @@ __device__ __forceinline__ float interp_weight(float sp, float sn, float tau) {
 __device__ __forceinline__ uint32_t cut_count(bool reached, bool coarse, const int32_t* __restrict__ nd) {
   if (!reached) return 0u;
   return coarse ? (uint32_t)nd[3] : (uint32_t)(nd[3] + nd[4]);
+}
+
+// ---- the same rules on operands that are already in registers ------------------------------------------------------
+// For the call that loads a node once and judges it for several views (lod_views.hip).  Each is the body of the rule
+// above it, word for word, behind another way in; the rules above stay as they are so that the three single-view calls
+// compile to what they always did.  tests/test_cut_views_gpu.py holds the two texts together bit for bit.
+__device__ __forceinline__ float box_size(float4 mn, float4 mx, Vec3 v) {          // node_size
+#pragma clang fp contract(off)
+  const float dx = fmaxf(fmaxf(mn.x - v.x, v.x - mx.x), 0.0f);
+  const float dy = fmaxf(fmaxf(mn.y - v.y, v.y - mx.y), 0.0f);
+  const float dz = fmaxf(fmaxf(mn.z - v.z, v.z - mx.z), 0.0f);
+  const float d2 = (dx * dx + dy * dy) + dz * dz;
+  const float dist = sqrtf(d2);
+  const float s = mn.w / dist;
+  return d2 > 0.0f ? s : kFltMax;
+}
+// entry_culled in its two halves: bit k = the ball is outside plane k ...
+__device__ __forceinline__ uint32_t planes_outside(float4 b, const Frustum& f) {
+  uint32_t out = 0;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) out |= ball_outside(b, f.p[k], f.rs) ? (1u << k) : 0u;
+  return out;
+}
+// ... and: is the parent's ball outside one of the planes in `out` as well?
+__device__ __forceinline__ bool parent_outside_too(uint32_t out, float4 bp, const Frustum& f) {
+  bool both = false;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) both |= ((out >> k) & 1u) && ball_outside(bp, f.p[k], f.rs);
+  return both;
+}
+__device__ __forceinline__ uint32_t cut_count(bool reached, bool coarse, int32_t leafs, int32_t merged) {
+  if (!reached) return 0u;
+  return coarse ? (uint32_t)leafs : (uint32_t)(leafs + merged);
 }
 
 // ---- workgroup sums, their scan, the emit pass (workgroups of 256 threads = 256 nodes) -------------------------------

@@ -16,6 +16,7 @@ ABI_VERSION = 14
 INST_GRAD_STRIDE = 10          # floats per (tile, Gaussian) record of the backward scratch (HGS_INST_GRAD_STRIDE)
 ERR_CAPACITY = 5
 CUT_COST_ENTRIES, CUT_COST_ROWS = 0, 1
+CUT_MAX_VIEWS = 16              # views of one hgs_lod_cut_views call (HGS_CUT_MAX_VIEWS)
 
 
 class RasterArgs(C.Structure):
@@ -185,6 +186,11 @@ SIGNATURES = {
     "hgs_lod_cut_view": (C.c_int, [_P, _P, _P, C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                    C.c_float, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, _P, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int32), _P, C.c_int]),
+    "hgs_lod_cut_views_tmp_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "hgs_lod_cut_views": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                    C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, _P, _P, C.c_int32, _P,
+                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_int64), _P, C.c_int]),
     "hgs_lod_cut_budget_tmp_bytes": (C.c_size_t, [C.c_int32]),
     "hgs_lod_cut_budget": (C.c_int, [_P, _P, _P, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_float),
                                      C.POINTER(C.c_float), C.c_float, _P, _P, _P, _P, _P, C.c_int32, _P,

@@ -18,7 +18,13 @@ The kept entries are exactly those of the unculled cut, in its order, with its p
 no trial cuts::
 
     bc = cut_to_budget(nodes, boxes, bounds, budget_rows, cam.camera_center, planes, rs, tau_min=tau)
-    # bc.tau is what was rendered, bc.cost <= budget_rows; the other fields are those of cut_view at bc.tau"""
+    # bc.tau is what was rendered, bc.cost <= budget_rows; the other fields are those of cut_view at bc.tau
+
+``cut_views`` (csrc/lod_views.hip, include/hgs.h "Cut for several views") is ``cut_view`` for several views at once --
+a batch of training views with a granularity each, a stereo pair, the current camera and a predicted one: one pass over
+the nodes and one host wait for all of them, every view's result bit for bit what ``cut_view`` gives it::
+
+    cuts = cut_views(nodes, boxes, bounds, taus, centers, planes, radius_scales)     # cuts[v] is a CutView"""
 from __future__ import annotations
 
 import ctypes as C
@@ -244,3 +250,89 @@ def cut_to_budget(nodes, boxes, bounds, budget, viewpoint, planes=None, radius_s
     k = int(n.value)
     return BudgetCut(k, int(n_all.value), bufs.ri[:k], bufs.pi[:k], bufs.ni[:k], bufs.w[:k], bufs.ns[:k],
                      float(tau.value), int(cst.value))
+
+
+def _views_floats(x, V, per, shape, name):
+    """``x`` = a tensor of shape [V, *shape] or a sequence of V items of ``per`` values -> the V * per host floats."""
+    if torch.is_tensor(x):
+        if tuple(x.shape) != (V,) + shape:
+            raise ValueError(f"{name} must be {list((V,) + shape)}, not {list(x.shape)}")
+        return [float(f) for f in x.detach().to("cpu", torch.float32).reshape(-1)]
+    items = list(x)
+    if len(items) != V:
+        raise ValueError(f"{name} must hold one entry per view ({V}), not {len(items)}")
+    out = []
+    for k, it in enumerate(items):
+        if torch.is_tensor(it) and shape and tuple(it.shape) != shape:
+            raise ValueError(f"{name}[{k}] must be {list(shape)}, not {list(it.shape)}")
+        out += list(_host_floats(it, per, f"{name}[{k}]"))
+    return out
+
+
+def cut_views(nodes, boxes, bounds, taus, viewpoints, planes=None, radius_scales=None, out=None) -> list[CutView]:
+    """``cut_view`` for V views in one pass over the nodes: view v is cut at granularity ``taus[v]`` from
+    ``viewpoints[v]`` and culled against ``planes[v]`` with ``radius_scales[v]`` (default 1), and ``result[v]`` is bit
+    for bit what ``cut_view(..., nested=True)`` returns for it.  ``viewpoints``: [V,3]; ``planes``: [V,5,4] or a
+    sequence of [5,4] (``frustum_planes``); all of it is read on the host.  ``bounds`` and ``planes`` are both given or
+    both None: without them nothing is culled and every view gets ``expand_to_size`` + ``get_interpolation_weights``.
+    The boxes must nest (every hierarchy this package builds or merges).  One call of the library takes 16 views; more
+    are processed in groups of 16.  All views share one set of buffers (``out``: a ``CutBuffers``; default: allocated to
+    fit): view v's entries start at the sum of the earlier views' counts, each rounded up to 4 entries (16 bytes), and
+    the ``CutView``s are slices of them.  Views that do not fit ``out`` raise ``_lib.HgsError`` naming the count."""
+    if (bounds is None) != (planes is None):
+        raise ValueError("bounds and planes go together: give both or neither")
+    cull = bounds is not None
+    N, dev, _ = _check_hierarchy(nodes, boxes, bounds, None, cull=False)
+    if cull:
+        _need(bounds, "bounds", torch.float32, lambda t: t.dim() == 2 and tuple(t.shape) == (N, 4), "[N,4]")
+        if bounds.device != dev:
+            raise ValueError("nodes, boxes and bounds must live on one device")
+    tau = [float(x) for x in (taus.detach().cpu().reshape(-1) if torch.is_tensor(taus) else list(taus))]
+    V = len(tau)
+    vps = _views_floats(viewpoints, V, 3, (3,), "viewpoints")
+    pls = _views_floats(planes, V, 20, (5, 4), "planes") if cull else None
+    rss = [1.0] * V if radius_scales is None else _views_floats(radius_scales, V, 1, (), "radius_scales")
+    if V == 0:
+        return []
+    from gaussian_hierarchy._C import _boxes_nested
+    if N > 0 and not _boxes_nested(nodes, boxes):
+        raise ValueError("cut_views needs a hierarchy whose boxes nest (every child's box inside its parent's): "
+                         "these do not -- use cut_view, one view at a time")
+    own = out is None
+    bufs = CutBuffers(max(N, 1), dev) if own else out
+    _check_out(bufs, dev)
+    lib = _lib.lib()
+    G = _lib.CUT_MAX_VIEWS
+    tmp = torch.empty(lib.hgs_lod_cut_views_tmp_bytes(N, min(V, G)), dtype=torch.uint8, device=dev)
+    p = _lib.ptr
+    floats = lambda v: (C.c_float * len(v))(*v)
+    for attempt in range(2):
+        names = (bufs.ri, bufs.pi, bufs.ni, bufs.w, bufs.ns)
+        cap = min(t.numel() for t in names)
+        at, fits, found = 0, True, []                   # `at`: where the next group starts
+        for g0 in range(0, V, G):
+            g = min(G, V - g0)
+            # a group behind one that did not fit is only counted: no room, nothing is written
+            room, base = (cap - at, at) if fits and at < cap else (0, 0)
+            outs = [C.c_void_p(t.data_ptr() + 4 * base) if t.numel() else None for t in names]
+            n, n_all, offs, need = (C.c_int32 * g)(), (C.c_int32 * g)(), (C.c_int32 * g)(), C.c_int64(0)
+            rc = lib.hgs_lod_cut_views(p(nodes), p(boxes), p(bounds), N, g, floats(tau[g0:g0 + g]),
+                                       floats(vps[3 * g0:3 * (g0 + g)]), floats(pls[20 * g0:20 * (g0 + g)]) if cull else None,
+                                       floats(rss[g0:g0 + g]), *outs, room, p(tmp), n, n_all, offs, C.byref(need),
+                                       _stream(dev), dev.index or 0)
+            if rc != 0 and not need.value > room:
+                _lib.check(rc, "hgs_lod_cut_views")
+            fits = fits and rc == 0
+            found += [(at + int(offs[v]), int(n[v]), int(n_all[v])) for v in range(g)]
+            at += sum((int(k) + 3) // 4 * 4 for k in n)
+        if fits:
+            break
+        needed = found[-1][0] + found[-1][1]
+        if needed > 2 ** 31 - 1:
+            raise _lib.HgsError(f"hgs_lod_cut_views failed: {needed} entries are more than the 2^31 - 1 one set of "
+                                f"outputs can index", 1)
+        if not own or attempt == 1:
+            raise _lib.HgsError(f"hgs_lod_cut_views failed: {needed} entries exceed the output capacity {cap}", 1)
+        bufs = CutBuffers(needed, dev)                  # nodes of several rows, or many views: allocate what it takes
+    return [CutView(k, k_all, bufs.ri[o:o + k], bufs.pi[o:o + k], bufs.ni[o:o + k], bufs.w[o:o + k], bufs.ns[o:o + k])
+            for o, k, k_all in found]

@@ -386,6 +386,31 @@ int hgs_lod_cut_budget(const int32_t* nodes, const float* boxes, const float* bo
                        void* tmp, int32_t* count_out_host, int32_t* unculled_out_host, float* tau_out_host,
                        int32_t* cost_out_host, hgs_stream_t stream, int device);
 
+/* ---------------------------------------------------------------------------
+ * Cut for several views (opt-in: the calls above are unchanged).  What
+ * hgs_lod_cut_view gives for each of V <= HGS_CUT_MAX_VIEWS views (granularity sizes[v], viewpoint, five planes and
+ * radius scale of its own) -- entries, order, parents, weights, sibling counts, bit for bit -- from ONE pass over the
+ * nodes and one host wait: a node's record, boxes and ball are loaded once and judged for every view.
+ * Precondition: the boxes NEST (hgs_hier_boxes_nested); only the single-pass route exists.
+ * bounds and planes are both given (planes f32 [V,5,4] HOST values) or both NULL: then nothing is culled and view v gets
+ * hgs_expand_to_size + hgs_interp_weights, unculled_out_host[v] = counts_out_host[v].
+ * The five outputs hold `capacity` entries each and are PACKED: the n_v = counts_out_host[v] entries of view v start at
+ * offsets_out_host[v] = sum over u < v of roundup4(n_u), so every view's slice starts on 16 bytes; the up to 3 entries
+ * between two views are not written.  *needed_out_host = offsets[V - 1] + n_{V - 1}.  needed > capacity: HGS_ERR_INVALID,
+ * the message names the needed count, counts / offsets / needed are set and nothing at or past `capacity` was written
+ * (positions are 64-bit).  needed > 2^31 - 1: refused, the message says so (counts and offsets saturate).
+ * NULL pointers, V outside [1, HGS_CUT_MAX_VIEWS], capacity < 0 and bounds without planes (or the reverse) are refused
+ * before any HIP call.  N <= 0: all counts 0, no GPU work.
+ * ------------------------------------------------------------------------- */
+#define HGS_CUT_MAX_VIEWS 16
+size_t hgs_lod_cut_views_tmp_bytes(int32_t N, int32_t V);
+int hgs_lod_cut_views(const int32_t* nodes, const float* boxes, const float* bounds, int32_t N, int32_t V,
+                      const float* sizes, const float* viewpoints, const float* planes, const float* radius_scales,
+                      int32_t* render_indices, int32_t* parent_indices, int32_t* nodes_for_render_indices,
+                      float* weights, int32_t* num_siblings, int32_t capacity, void* tmp, int32_t* counts_out_host,
+                      int32_t* unculled_out_host, int32_t* offsets_out_host, int64_t* needed_out_host,
+                      hgs_stream_t stream, int device);
+
 /* In-op LOD attribute interpolation: the gather + lerp that render_post does in Python
  * (gaussian_renderer/__init__.py:199-218), for callers that pass GaussianRasterizationSettings.render_indices /
  * parent_indices non-empty.  out_i = w_i * attr[render_indices[i]] + (1 - w_i) * attr[parent_indices[i]]; rotations
