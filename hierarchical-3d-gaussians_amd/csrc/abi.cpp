@@ -161,61 +161,52 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-size_t GeomWs::bytes(int32_t P) {
+// The four raster workspaces: layout() is the one text of each (common.h: carve_from() and bytes() run it).
+GeomWs GeomWs::layout(Carver& c, int32_t P) {
   const size_t p = (size_t)(P > 0 ? P : 1);
   const size_t nblk = (p + kPreBlock - 1) / kPreBlock;
   const size_t jac_rows = (p + 63) / 64 * 64;   // K1's H48 route stores the Jacobians of whole 64-row waves
-  return align_up(p * kRecFloats * 4) + align_up(p * 4) + align_up(p * 8) + 3 * align_up(p * 4) +
-         align_up((nblk + 1) * 4) + align_up((nblk + 1) * kBands * 4) + align_up(jac_rows * kJacStride * 4) +
-         align_up((size_t)(1 + kBands) * scan_chunks(nblk) * 8) + kAlign;
-}
-GeomWs GeomWs::carve_from(void* base, int32_t P) {
-  const size_t p = (size_t)(P > 0 ? P : 1);
-  const size_t nblk = (p + kPreBlock - 1) / kPreBlock;
-  const size_t jac_rows = (p + 63) / 64 * 64;   // (as in bytes())
-  char* c = static_cast<char*>(base);
   GeomWs g;
-  g.records = carve<float>(c, p * kRecFloats);
-  g.depths = carve<float>(c, p);
-  g.rects = carve<uint32_t>(c, p * 2);
-  g.tiles_touched = carve<uint32_t>(c, p);
-  g.offsets = carve<uint32_t>(c, p);
-  g.flags = carve<uint32_t>(c, p);
-  g.block_sums = carve<uint32_t>(c, nblk + 1);
-  g.block_band = carve<uint32_t>(c, (nblk + 1) * kBands);
-  g.shjac = carve<float>(c, jac_rows * kJacStride);
-  g.scan_chain = carve<unsigned long long>(c, (size_t)(1 + kBands) * scan_chunks(nblk));
+  g.records = c.take<float>(p * kRecFloats);
+  g.depths = c.take<float>(p);
+  g.rects = c.take<uint32_t>(p * 2);
+  g.tiles_touched = c.take<uint32_t>(p);
+  g.offsets = c.take<uint32_t>(p);
+  g.flags = c.take<uint32_t>(p);
+  g.block_sums = c.take<uint32_t>(nblk + 1);
+  g.block_band = c.take<uint32_t>((nblk + 1) * kBands);
+  g.shjac = c.take<float>(jac_rows * kJacStride);
+  g.scan_chain = c.take<unsigned long long>((size_t)(1 + kBands) * scan_chunks(nblk));
   return g;
 }
 
-size_t BinWs::bytes(uint32_t L, int32_t T) {
-  const size_t l = L ? L : 1;
-  const size_t tmp_sort = sort_tmp_bytes(L ? L : 1), tmp_bin = tile_bin_tmp_bytes(L, T);
-  return 4 * align_up(l * 4) + align_up((size_t)T * 8) + align_up(((size_t)T * 3 + 3) * 4) + align_up(((size_t)T + 8) * 4) +
-         (tmp_sort > tmp_bin ? tmp_sort : tmp_bin) + kAlign;
-}
-BinWs BinWs::carve_from(void* base, uint32_t L, int32_t T) {
-  const size_t l = L ? L : 1;
-  char* c = static_cast<char*>(base);
+BinWs BinWs::layout(Carver& c, uint32_t L, int32_t T) {
+  const size_t l = L ? L : 1, tmp_sort = sort_tmp_bytes((uint32_t)l), tmp_bin = tile_bin_tmp_bytes(L, T);
   BinWs b;
-  b.keys_in = carve<uint32_t>(c, l);
-  b.vals_in = carve<uint32_t>(c, l);
-  b.keys_out = carve<uint32_t>(c, l);
-  b.vals_out = carve<uint32_t>(c, l);
-  b.ranges = carve<uint32_t>(c, (size_t)T * 2);
-  b.big_tiles = carve<uint32_t>(c, (size_t)T * 3 + 3);
-  b.tile_order = carve<uint32_t>(c, (size_t)T + 8);    // 8 * ceil(T / 8) entries
-  b.sort_tmp = c;
+  b.keys_in = c.take<uint32_t>(l);
+  b.vals_in = c.take<uint32_t>(l);
+  b.keys_out = c.take<uint32_t>(l);
+  b.vals_out = c.take<uint32_t>(l);
+  b.ranges = c.take<uint32_t>((size_t)T * 2);
+  b.big_tiles = c.take<uint32_t>((size_t)T * 3 + 3);
+  b.tile_order = c.take<uint32_t>((size_t)T + 8);    // 8 * ceil(T / 8) entries
+  b.sort_tmp = c.take<char>(tmp_sort > tmp_bin ? tmp_sort : tmp_bin);   // nested: either figure has its own slack
   return b;
 }
 
-size_t ImgWs::bytes(int32_t W, int32_t H) { return 2 * align_up((size_t)W * H * 4) + kAlign; }
-ImgWs ImgWs::carve_from(void* base, int32_t W, int32_t H) {
-  char* c = static_cast<char*>(base);
-  ImgWs im;
-  im.final_T = carve<float>(c, (size_t)W * H);
-  im.n_contrib = carve<uint32_t>(c, (size_t)W * H);
-  return im;
+// (a braced list is evaluated left to right)
+ImgWs ImgWs::layout(Carver& c, int32_t W, int32_t H) { return {c.take<float>((size_t)W * H), c.take<uint32_t>((size_t)W * H)}; }
+
+BwdWs BwdWs::layout(Carver& c, uint32_t L, int32_t P) {
+  const size_t l = L ? L : 1, p = (size_t)(P > 0 ? P : 1);
+  BwdWs w;
+  w.inst_grads = c.take<float>(l * kInstStride);
+  w.drgb = c.take<float>(p * 3);
+  w.dmean_rows = c.take<float>(p * 3);
+  w.lod_flag = c.take<uint32_t>(kAlign / sizeof(uint32_t));   // one block: the flag word and the worklist counter
+  w.work_counter = w.lod_flag ? w.lod_flag + 16 : nullptr;
+  w.work = c.take<uint2>(l / kK8LongRun + 2);
+  return w;
 }
 
 static int validate(const hgs_raster_args* a) {
@@ -273,7 +264,7 @@ int hgs_raster_ws_sizes(int32_t P, int32_t width, int32_t height, uint32_t L, si
   if (geom_bytes) *geom_bytes = GeomWs::bytes(P);
   if (bin_bytes) *bin_bytes = BinWs::bytes(L, T);
   if (img_bytes) *img_bytes = ImgWs::bytes(width, height);
-  if (bwd_bytes) *bwd_bytes = bwd_ws_bytes(L, P);
+  if (bwd_bytes) *bwd_bytes = BwdWs::bytes(L, P);
   return HGS_OK;
 }
 
@@ -434,10 +425,9 @@ int hgs_raster_bwd(const hgs_raster_args* a, const void* geom_ws, const void* bi
   const GeomWs g = GeomWs::carve_from(const_cast<void*>(geom_ws), a->P);
   const BinWs b = BinWs::carve_from(const_cast<void*>(bin_ws), L, T);
   const ImgWs im = ImgWs::carve_from(const_cast<void*>(img_ws), a->width, a->height);
-  float* inst = static_cast<float*>(bwd_ws);
-  float* drgb = bwd_ws_drgb(bwd_ws, L);
+  BwdWs w = BwdWs::carve_from(bwd_ws, L, a->P);
   if (L > 0) {     // (the instance scratch needs no clearing: K7 writes every record, sums or zeros)
-    if ((rc = HGS_TIMED(ST_RENDER_BWD, s, launch_render_bwd(*a, g, b, im, out_color, out_invdepth, dL_dcolor, dL_dinvdepth, inst, s)))) return rc;
+    if ((rc = HGS_TIMED(ST_RENDER_BWD, s, launch_render_bwd(*a, g, b, im, out_color, out_invdepth, dL_dcolor, dL_dinvdepth, w.inst_grads, s)))) return rc;
   }
   hgs_raster_grads gr = *grads;
   if (!a->shs) gr.dL_dshs = nullptr;
@@ -445,14 +435,12 @@ int hgs_raster_bwd(const hgs_raster_args* a, const void* geom_ws, const void* bi
   if (!a->colors_precomp) gr.dL_dcolors = nullptr;
   if (!a->scales) { gr.dL_dscales = nullptr; gr.dL_drotations = nullptr; }
   if (!a->cov3D_precomp) gr.dL_dcov3D = nullptr;
-  uint32_t* lod_flag = nullptr;
-  if (a->lod_render_indices && a->lod_scatter) {
-    lod_flag = bwd_ws_lod_flag(bwd_ws, L, a->P);
-    HGS_HIP(hipMemsetAsync(lod_flag, 0, sizeof(uint32_t), s));
-    if ((rc = launch_lod_monotone(a->lod_parent_indices, a->lod_n, lod_flag, s))) return rc;
+  if (!(a->lod_render_indices && a->lod_scatter)) w.lod_flag = nullptr;
+  if (w.lod_flag) {
+    HGS_HIP(hipMemsetAsync(w.lod_flag, 0, sizeof(uint32_t), s));
+    if ((rc = launch_lod_monotone(a->lod_parent_indices, a->lod_n, w.lod_flag, s))) return rc;
   }
-  return HGS_TIMED(ST_PREPROCESS_BWD, s, launch_preprocess_bwd(*a, g, inst, drgb, bwd_ws_dmean(bwd_ws, L, a->P), lod_flag, gr, L,
-                                                             bwd_ws_work(bwd_ws, L, a->P), bwd_ws_work_counter(bwd_ws, L, a->P), s));
+  return HGS_TIMED(ST_PREPROCESS_BWD, s, launch_preprocess_bwd(*a, g, w, gr, L, s));
 }
 
 int hgs_raster_sh_bwd_batched(const hgs_sh_bwd_view* views, int32_t n_views, int32_t P, int32_t M, int32_t sh_degree,
@@ -470,7 +458,7 @@ int hgs_raster_sh_bwd_batched(const hgs_sh_bwd_view* views, int32_t n_views, int
     const hgs_sh_bwd_view& w = views[i < n_views ? i : 0];
     if (!w.geom_ws || !w.bwd_ws || !w.campos) { set_error("deferred view %d has a null pointer", i); return HGS_ERR_INVALID; }
     v.mask[i] = GeomWs::carve_from(const_cast<void*>(w.geom_ws), P).tiles_touched;
-    v.drgb[i] = bwd_ws_drgb(const_cast<void*>(w.bwd_ws), w.L);
+    v.drgb[i] = BwdWs::carve_from(const_cast<void*>(w.bwd_ws), w.L, P).drgb;
     v.campos[i] = w.campos;
   }
   HGS_HIP(hipSetDevice(device));

@@ -1118,12 +1118,12 @@ int launch_duplicate_tiles(const hgs_raster_args& a, const GeomWs& g, const BinW
   if (super && !(banded && nblk > 0 && L_cap > 0)) { set_error("duplicate_tiles: superblock totals without the banded path"); return HGS_ERR_INVALID; }
   if (nblk > 0 && L_cap > 0) {
     const int T = grid_x(a.width) * grid_y(a.height);
-    if (banded)
+    if (banded) {
+      const TileBinZero z = tile_bin_zero_range(b.sort_tmp, L_cap, T);
       hipLaunchKernelGGL(duplicate_tiles_banded_kernel, dim3(nblk), dim3(kPreBlock), 0, s, a.P, grid_x(a.width), T,
                          band_tiles(T), g, L_cap, b.keys_in, b.vals_in, b.ranges, T * 2, super, total_mirror,
-                         tile_bin_zero_words(b.sort_tmp, L_cap, T), tile_bin_zero_count(T), k3_share_max(),
-                         super ? k3_heavy_threshold(L_cap, a.P) : 0u);
-    else
+                         z.words, z.count, k3_share_max(), super ? k3_heavy_threshold(L_cap, a.P) : 0u);
+    } else
       hipLaunchKernelGGL(duplicate_tiles_kernel, dim3(nblk), dim3(kPreBlock), 0, s, a.P, grid_x(a.width), g, L_cap,
                          b.keys_in, b.vals_in, b.ranges, T * 2);
     HGS_LAUNCH_CHECK("duplicate_tiles", s, a.debug);

@@ -36,12 +36,21 @@ void set_error(const char* fmt, ...);
 constexpr size_t kAlign = 256;
 inline size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
 
-template <typename T>
-inline T* carve(char*& p, size_t count) {
-  T* r = reinterpret_cast<T*>(p);
-  p += align_up(count * sizeof(T));
-  return r;
-}
+// A workspace layout is ONE function that takes its arrays off a Carver in order.  Called on the real base it hands out
+// the pointers; called on a null base it hands out nullptrs and the offset alone sizes the workspace (no arithmetic on a
+// null pointer), so the size query is answered by the code that carves.
+struct Carver {
+  char* base;
+  size_t offset = 0;
+  explicit Carver(void* b) : base(static_cast<char*>(b)) {}
+  template <typename T> T* take(size_t count) {
+    T* r = base ? reinterpret_cast<T*>(base + offset) : nullptr;
+    offset += align_up(count * sizeof(T));
+    return r;
+  }
+  // slack: kAlign for a base that is not aligned (0 where a workspace never had it)
+  size_t bytes(size_t slack) const { return offset + slack; }
+};
 
 constexpr int kTile = HGS_TILE;
 constexpr int kRecFloats = 16;              // per-Gaussian 2D record, 4 x float4 (one 64-byte line)
@@ -68,8 +77,9 @@ struct GeomWs {
                            // instances whose tile lies in band b; [b][nblk] = the band's total
   float* shjac;            // [ceil64(P),kJacStride] d(rgb)/d(view direction): 9 values, rows = direction component (hgs_raster_args.prepare_backward)
   unsigned long long* scan_chain;  // [(1 + kBands) * scan_chunks(nblk)] published chunk totals of the K2 scans (K1 clears it)
-  static size_t bytes(int32_t P);
-  static GeomWs carve_from(void* base, int32_t P);
+  static GeomWs layout(Carver& c, int32_t P);      // abi.cpp; on the real base for the pointers, on a null base for the size
+  static size_t bytes(int32_t P) { Carver c(nullptr); layout(c, P); return c.bytes(kAlign); }
+  static GeomWs carve_from(void* base, int32_t P) { Carver c(base); return layout(c, P); }
 };
 
 struct BinWs {
@@ -80,16 +90,35 @@ struct BinWs {
   uint32_t* ranges;    // [T,2]
   uint32_t* big_tiles; // [3 + 3T] counters + lists of the tiles too crowded for the one-wave register sort
   uint32_t* tile_order; // [8 * ceil(T/8)] tile of workgroup b: XCD bands, heavy tiles first inside a band (binning.hip)
-  void* sort_tmp;
-  static size_t bytes(uint32_t L, int32_t T);
-  static BinWs carve_from(void* base, uint32_t L, int32_t T);
+  void* sort_tmp;      // the larger of the radix-sort scratch and the tile-binning scratch
+  static BinWs layout(Carver& c, uint32_t L, int32_t T);
+  static size_t bytes(uint32_t L, int32_t T) { Carver c(nullptr); layout(c, L, T); return c.bytes(kAlign); }
+  static BinWs carve_from(void* base, uint32_t L, int32_t T) { Carver c(base); return layout(c, L, T); }
 };
 
 struct ImgWs {
   float* final_T;       // [H*W]
   uint32_t* n_contrib;  // [H*W]
-  static size_t bytes(int32_t W, int32_t H);
-  static ImgWs carve_from(void* base, int32_t W, int32_t H);
+  static ImgWs layout(Carver& c, int32_t W, int32_t H);
+  static size_t bytes(int32_t W, int32_t H) { Carver c(nullptr); layout(c, W, H); return c.bytes(kAlign); }
+  static ImgWs carve_from(void* base, int32_t W, int32_t H) { Carver c(base); return layout(c, W, H); }
+};
+
+// Backward scratch.  K8's long runs: the worklist holds one (Gaussian, segment) pair per kK8Seg records of every run of
+// more than kK8LongRun records (preprocess.hip)
+constexpr uint32_t kK8LongRun = 48;
+constexpr uint32_t kK8Seg = 512;
+struct BwdWs {
+  float* inst_grads;       // [L,kInstStride] the ten sums of every (tile, Gaussian) instance
+  float* drgb;             // [P,3] per-Gaussian colour gradients
+  float* dmean_rows;       // [P,3] mean gradients of the rows K8a hands to K8b (in-kernel LOD scatter only)
+  uint32_t* lod_flag;      // "parent indices are not non-decreasing" (set by launch_lod_monotone); the backward call
+                           // nulls it when there is no in-kernel LOD scatter
+  uint32_t* work_counter;  // length of the worklist: 16 words into the flag word's kAlign block
+  uint2* work;             // [L / kK8LongRun + 2]: a run of n > 48 records has <= n / 48 segments
+  static BwdWs layout(Carver& c, uint32_t L, int32_t P);
+  static size_t bytes(uint32_t L, int32_t P) { Carver c(nullptr); layout(c, L, P); return c.bytes(kAlign); }
+  static BwdWs carve_from(void* base, uint32_t L, int32_t P) { Carver c(base); return layout(c, L, P); }
 };
 
 inline int grid_x(int W) { return (W + kTile - 1) / kTile; }
@@ -218,9 +247,10 @@ int launch_scan_block_sums(const GeomWs& g, int32_t P, hipStream_t s, bool debug
 // workgroup then stores the totals and, into *total_mirror (optional, device-visible), the instance count
 int launch_duplicate_tiles(const hgs_raster_args& a, const GeomWs& g, const BinWs& b, uint32_t L_cap, bool banded,
                            hipStream_t s, const uint32_t* super = nullptr, uint32_t* total_mirror = nullptr);
-// the words of the tile-binning scratch that the banded K3 clears for the counting kernels (tile_bin.hip)
-uint32_t* tile_bin_zero_words(void* tmp, uint32_t L_cap, int32_t T);
-int tile_bin_zero_count(int32_t T);
+// the words of the tile-binning scratch that the banded K3 clears for the counting kernels (tile_bin.hip: tb_carve);
+// nullptr / 0 where the grid takes the radix route
+struct TileBinZero { uint32_t* words; int count; };
+TileBinZero tile_bin_zero_range(void* tmp, uint32_t L_cap, int32_t T);
 int launch_tile_ranges(const BinWs& b, uint32_t L_cap, const uint32_t* L_dev, int32_t T, hipStream_t s, bool debug);
 // b.tile_order from the final b.ranges (one small workgroup; counting sort over quantised instance counts)
 int launch_tile_order(const BinWs& b, int32_t T, hipStream_t s, bool debug);
@@ -232,13 +262,10 @@ int launch_render_fwd(const hgs_raster_args& a, const GeomWs& g, const BinWs& b,
 int launch_render_bwd(const hgs_raster_args& a, const GeomWs& g, const BinWs& b, const ImgWs& im,
                       const float* out_color, const float* out_invdepth, const float* dL_dcolor,
                       const float* dL_dinvdepth, float* inst_grads, hipStream_t s);
-// dmean_rows / lod_flag: scratch of the in-kernel LOD scatter (hgs_raster_args.lod_scatter): the per-row mean gradient
-// K8a hands to K8b, and the "parent indices are not non-decreasing" word (set by launch_lod_monotone)
-// L: the frame's instance count (a frame of long runs sums them with kernels of their own in front of K8a; inst_grads is
-// consumed: they leave every segment's sums over the segment's first records); work / work_counter: bwd_ws_work*
-int launch_preprocess_bwd(const hgs_raster_args& a, const GeomWs& g, const float* inst_grads, float* drgb,
-                          float* dmean_rows, const uint32_t* lod_flag, const hgs_raster_grads& out, uint32_t L,
-                          uint2* work, uint32_t* work_counter, hipStream_t s);
+// L: the frame's instance count (a frame of long runs sums them with kernels of their own in front of K8a; w.inst_grads
+// is consumed: they leave every segment's sums over the segment's first records)
+int launch_preprocess_bwd(const hgs_raster_args& a, const GeomWs& g, const BwdWs& w, const hgs_raster_grads& out, uint32_t L,
+                          hipStream_t s);
 int launch_lod_monotone(const int32_t* parent_indices, int32_t n, uint32_t* flag, hipStream_t s);
 // Per-view device pointers of the batched SH kernels.  Kept small (24 pointers): they are kernel arguments and must
 // stay in scalar registers across the view loop.
@@ -260,30 +287,6 @@ int launch_sh_colors_batched(const ShFwdViews& v, int32_t P, int32_t M, int32_t 
                              const float* shs, hipStream_t s);
 int launch_sh_bwd_batched(const ShBwdViews& v, int32_t P, int32_t M, int32_t sh_degree, const float* means3D,
                           const float* shs, float* dL_dshs, float* dL_dmeans3D, bool accumulate, hipStream_t s);
-// the per-Gaussian colour gradients sit behind the instance gradients in the backward scratch
-inline float* bwd_ws_drgb(void* bwd_ws, uint32_t L) {
-  return reinterpret_cast<float*>(static_cast<char*>(bwd_ws) + align_up((size_t)(L ? L : 1) * kInstStride * 4));
-}
-// behind them: [P,3] mean gradients of the rows and one flag word (in-kernel LOD scatter only)
-inline float* bwd_ws_dmean(void* bwd_ws, uint32_t L, int32_t P) {
-  return reinterpret_cast<float*>(reinterpret_cast<char*>(bwd_ws_drgb(bwd_ws, L)) + align_up((size_t)(P > 0 ? P : 1) * 3 * 4));
-}
-inline uint32_t* bwd_ws_lod_flag(void* bwd_ws, uint32_t L, int32_t P) {
-  return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(bwd_ws_dmean(bwd_ws, L, P)) + align_up((size_t)(P > 0 ? P : 1) * 3 * 4));
-}
-// behind the flag word (same 256-byte block): the counter of the long-run worklist of K8, and the worklist itself -- one
-// (Gaussian, segment) pair per kK8Seg records of every run of more than kK8LongRun records (preprocess.hip)
-constexpr uint32_t kK8LongRun = 48;
-constexpr uint32_t kK8Seg = 512;
-inline uint32_t* bwd_ws_work_counter(void* bwd_ws, uint32_t L, int32_t P) { return bwd_ws_lod_flag(bwd_ws, L, P) + 16; }
-inline uint2* bwd_ws_work(void* bwd_ws, uint32_t L, int32_t P) {
-  return reinterpret_cast<uint2*>(reinterpret_cast<char*>(bwd_ws_lod_flag(bwd_ws, L, P)) + kAlign);
-}
-inline size_t bwd_ws_work_items(uint32_t L) { return (size_t)(L ? L : 1) / kK8LongRun + 2; }   // a run of n > 48 records has <= n / 48 segments
-inline size_t bwd_ws_bytes(uint32_t L, int32_t P) {
-  return align_up((size_t)(L ? L : 1) * kInstStride * 4) + 2 * align_up((size_t)(P > 0 ? P : 1) * 3 * 4) + 2 * kAlign +
-         align_up(bwd_ws_work_items(L) * sizeof(uint2));
-}
 // tile binning without a sort (tile_bin.hip); tmp shares BinWs::sort_tmp
 bool tile_bin_supported(int32_t T);
 size_t tile_bin_tmp_bytes(uint32_t L, int32_t T);

@@ -246,14 +246,17 @@ constexpr int64_t kMaxRows = 0x7fffffff;        // 32-bit block sums and one 1-D
 
 using namespace hgs;
 
-extern "C" size_t hgs_densify_tmp_bytes(int64_t P) {
-  if (P < 0 || P > kMaxRows) { set_error("densify: bad sizes (P = %lld outside [0, 2^31 - 1])", (long long)P); return 0; }
-  return align_up((size_t)(P > 0 ? P : 1) * sizeof(uint2)) + 4 * sums_stride(P) * sizeof(uint32_t);
+// tmp: [P] ranks and class bits of every source row, then the four workgroup-sum arrays [4][sums_stride(P)]
+struct DensifyTmp { uint2* rec; uint32_t* sums; };
+static DensifyTmp carve_densify(Carver& c, int64_t P) {     // (a braced list is evaluated left to right)
+  return {c.take<uint2>((size_t)(P > 0 ? P : 1)), c.take<uint32_t>(4 * sums_stride(P))};
 }
 
-static uint2* tmp_rec(void* tmp) { return static_cast<uint2*>(tmp); }
-static uint32_t* tmp_sums(void* tmp, int64_t P) {
-  return reinterpret_cast<uint32_t*>(static_cast<char*>(tmp) + align_up((size_t)(P > 0 ? P : 1) * sizeof(uint2)));
+extern "C" size_t hgs_densify_tmp_bytes(int64_t P) {
+  if (P < 0 || P > kMaxRows) { set_error("densify: bad sizes (P = %lld outside [0, 2^31 - 1])", (long long)P); return 0; }
+  Carver c(nullptr);
+  carve_densify(c, P);
+  return c.bytes(0);   // this workspace never had a slack block
 }
 
 extern "C" int hgs_densify_plan(const float* accum, const float* radii, const float* opacity, const float* scaling,
@@ -267,13 +270,14 @@ extern "C" int hgs_densify_plan(const float* accum, const float* radii, const fl
   HGS_HIP(hipSetDevice(device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint32_t nblk = (uint32_t)plan_blocks(P), stride = (uint32_t)sums_stride(P);
-  uint32_t* sums = tmp_sums(tmp, P);
+  Carver c(tmp);
+  const DensifyTmp t = carve_densify(c, P);
   if (nblk) {
     hipLaunchKernelGGL(densify_plan_kernel, dim3(nblk), dim3(kRows), 0, s, accum, radii, opacity, scaling, P, F, max_grad,
-                       min_opacity, d, tmp_rec(tmp), sums, stride);
+                       min_opacity, d, t.rec, t.sums, stride);
     HGS_LAUNCH_CHECK("densify_plan", s, false);
   }
-  hipLaunchKernelGGL(densify_scan_kernel, dim3(4), dim3(1024), 0, s, sums, stride, nblk, totals);
+  hipLaunchKernelGGL(densify_scan_kernel, dim3(4), dim3(1024), 0, s, t.sums, stride, nblk, totals);
   HGS_LAUNCH_CHECK("densify_scan", s, false);
   if (wait) HGS_HIP(wait_stream(s));
   return HGS_OK;
@@ -334,9 +338,10 @@ extern "C" int hgs_densify_apply(const hgs_densify_tensor* tensors, int32_t n_te
   hipStream_t s = static_cast<hipStream_t>(stream);
   void (*kern)(DensifyLaunch, int, int64_t, DensifyCounts, const uint2*, const uint32_t*, uint32_t, const float*,
                const float*, const float*) = wide ? densify_apply_kernel<int64_t> : densify_apply_kernel<uint32_t>;
-  hipLaunchKernelGGL(kern, dim3((uint32_t)nb), dim3(256), 0, s, L, n_tensors, P, N,
-                     static_cast<const uint2*>(tmp), tmp_sums(const_cast<void*>(tmp), P), (uint32_t)sums_stride(P), scaling,
-                     rotation, noise);
+  Carver c(const_cast<void*>(tmp));
+  const DensifyTmp dt = carve_densify(c, P);
+  hipLaunchKernelGGL(kern, dim3((uint32_t)nb), dim3(256), 0, s, L, n_tensors, P, N, dt.rec, dt.sums,
+                     (uint32_t)sums_stride(P), scaling, rotation, noise);
   HGS_LAUNCH_CHECK("densify_apply", s, false);
   return HGS_OK;
 }

@@ -152,26 +152,28 @@ struct HaTmp {
   void* sort_tmp;
 };
 
-HaTmp carve_ha_tmp(void* tmp, int64_t N) {
-  char* p = static_cast<char*>(tmp);
+HaTmp carve_ha_tmp(Carver& c, int64_t N) {
   HaTmp t;
-  t.res = carve<HaResult>(p, 1);
-  t.keys = carve<uint32_t>(p, (size_t)N);
-  t.keys_sorted = carve<uint32_t>(p, (size_t)N);
-  t.order = carve<uint32_t>(p, (size_t)N);
-  t.sort_tmp = p;
+  t.res = c.take<HaResult>(1);
+  t.keys = c.take<uint32_t>((size_t)N);
+  t.keys_sorted = c.take<uint32_t>((size_t)N);
+  t.order = c.take<uint32_t>((size_t)N);
+  t.sort_tmp = c.take<char>(sort_tmp_bytes((uint32_t)N));   // nested: the sort's own slack included
   return t;
 }
 
 }  // namespace
 
 size_t hier_align_tmp_bytes(int64_t N) {
-  return align_up(sizeof(HaResult)) + 3 * align_up((size_t)N * 4) + sort_tmp_bytes((uint32_t)N);
+  Carver c(nullptr);
+  carve_ha_tmp(c, N);
+  return c.bytes(0);   // this workspace never had a slack block of its own (the nested sort's is its last)
 }
 
 int launch_hier_align(const int32_t* nodes, int64_t N, float* log_scales, float* rots, void* tmp,
                       hgs_hier_align_report* report, hipStream_t s) {
-  const HaTmp t = carve_ha_tmp(tmp, N);
+  Carver c(tmp);
+  const HaTmp t = carve_ha_tmp(c, N);
   // ---- checks, keys and level counts; the level lists
   HGS_HIP(hipMemsetAsync(t.res->counts, 0, sizeof(t.res->counts), s));
   HGS_HIP(hipMemsetAsync(t.res->first_bad, 0xff, sizeof(HaResult) - sizeof(t.res->counts), s));

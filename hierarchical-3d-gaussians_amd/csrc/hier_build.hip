@@ -379,32 +379,32 @@ struct HbTmp {
   void* sort_tmp;
 };
 
-HbTmp carve_hb_tmp(void* tmp, int32_t P) {
-  char* p = static_cast<char*>(tmp);
+HbTmp carve_hb_tmp(Carver& c, int32_t P) {
   const size_t N = 2 * (size_t)P - 1;
   HbTmp t;
-  t.words = carve<uint32_t>(p, 8);
-  t.keys = carve<uint32_t>(p, P);
-  t.keys_sorted = carve<uint32_t>(p, P);
-  t.order = carve<uint32_t>(p, P);
-  t.range = carve<int2>(p, N);
-  t.mom = carve<double>(p, N * kMomDoubles);
-  t.sort_tmp = p;
+  t.words = c.take<uint32_t>(8);
+  t.keys = c.take<uint32_t>(P);
+  t.keys_sorted = c.take<uint32_t>(P);
+  t.order = c.take<uint32_t>(P);
+  t.range = c.take<int2>(N);
+  t.mom = c.take<double>(N * kMomDoubles);
+  t.sort_tmp = c.take<char>(sort_tmp_bytes((uint32_t)P));   // nested: the sort's own slack included
   return t;
 }
 
 }  // namespace
 
 size_t hier_build_tmp_bytes(int32_t P) {
-  const size_t N = 2 * (size_t)P - 1;
-  return align_up(8 * 4) + 3 * align_up((size_t)P * 4) + align_up(N * sizeof(int2)) +
-         align_up(N * kMomDoubles * sizeof(double)) + sort_tmp_bytes((uint32_t)P) + kAlign;
+  Carver c(nullptr);
+  carve_hb_tmp(c, P);
+  return c.bytes(kAlign);
 }
 
 int launch_hier_build(const float* xyz, const float* scales, const float* rots, const float* opacity, const float* shs,
                       int32_t P, int32_t M, float* out_xyz, float* out_shs, float* out_alpha, float* out_log_scales,
                       float* out_rots, int32_t* out_nodes, float* out_boxes, void* tmp, hipStream_t s) {
-  const HbTmp t = carve_hb_tmp(tmp, P);
+  Carver ws(tmp);
+  const HbTmp t = carve_hb_tmp(ws, P);
   // ---- Morton order of the leaves
   HGS_HIP(hipMemsetAsync(t.words, 0xff, 8 * 4, s));
   hipLaunchKernelGGL(hb_bounds_kernel, dim3(min(blocks_for(P), 2048u)), dim3(kHbThreads), 0, s, xyz, P, t.words);

@@ -178,18 +178,17 @@ struct KnnTmp {
   void* sort_tmp;
 };
 
-inline KnnTmp carve_knn(void* tmp, int32_t P) {
+inline KnnTmp carve_knn(Carver& c, int32_t P) {
   const size_t p = (size_t)(P > 0 ? P : 1);
-  char* c = static_cast<char*>(tmp);
   KnnTmp t;
-  t.mm = carve<uint32_t>(c, 8);
-  t.keys_in = carve<uint64_t>(c, p);
-  t.vals_in = carve<uint32_t>(c, p);
-  t.keys_out = carve<uint64_t>(c, p);
-  t.vals_out = carve<uint32_t>(c, p);
-  t.sorted = carve<float4>(c, p);
-  t.boxes = carve<float>(c, ((p + kRun - 1) / kRun) * 6);
-  t.sort_tmp = c;
+  t.mm = c.take<uint32_t>(8);
+  t.keys_in = c.take<uint64_t>(p);
+  t.vals_in = c.take<uint32_t>(p);
+  t.keys_out = c.take<uint64_t>(p);
+  t.vals_out = c.take<uint32_t>(p);
+  t.sorted = c.take<float4>(p);
+  t.boxes = c.take<float>(((p + kRun - 1) / kRun) * 6);
+  t.sort_tmp = c.take<char>(sort_tmp_bytes((uint32_t)p));   // nested: the sort's own slack included
   return t;
 }
 
@@ -201,9 +200,9 @@ using namespace hgs;
 extern "C" {
 
 size_t hgs_knn_tmp_bytes(int32_t P) {
-  const size_t p = (size_t)(P > 0 ? P : 1);
-  return align_up(32) + 2 * align_up(p * 8) + 2 * align_up(p * 4) + align_up(p * 16) +
-         align_up(((p + kRun - 1) / kRun) * 24) + sort_tmp_bytes((uint32_t)p) + kAlign;
+  Carver c(nullptr);
+  carve_knn(c, P);
+  return c.bytes(kAlign);
 }
 
 int hgs_dist2_knn3(const float* xyz, int32_t P, float* out_mean_d2, void* tmp, hgs_stream_t stream, int device) {
@@ -211,7 +210,8 @@ int hgs_dist2_knn3(const float* xyz, int32_t P, float* out_mean_d2, void* tmp, h
   if (!xyz || !out_mean_d2 || !tmp) { set_error("null argument"); return HGS_ERR_INVALID; }
   HGS_HIP(hipSetDevice(device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const KnnTmp t = carve_knn(tmp, P);
+  Carver c(tmp);
+  const KnnTmp t = carve_knn(c, P);
   const int nblk = (P + 255) / 256;
   hipLaunchKernelGGL(knn_init_kernel, dim3(1), dim3(64), 0, s, t.mm);
   HGS_LAUNCH_CHECK("knn_init", s, false);

@@ -176,9 +176,9 @@ using namespace hgs;
 extern "C" {
 
 size_t hgs_expand_tmp_bytes(int32_t N) {
-  char* p = nullptr;
-  carve_levels(p, N, false);
-  return carved_bytes(p);
+  Carver c(nullptr);
+  carve_levels(c, N, false);
+  return c.bytes(kAlign);
 }
 
 static int expand_finish(const int32_t* nodes, const LevelTmp& t, int32_t N, int32_t* render_indices,
@@ -215,8 +215,8 @@ int hgs_expand_to_size(const int32_t* nodes, const float* boxes, int32_t N, floa
   }
   HGS_HIP(hipSetDevice(device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char* p = static_cast<char*>(tmp);
-  const LevelTmp t = carve_levels(p, N, false);
+  Carver c(tmp);
+  const LevelTmp t = carve_levels(c, N, false);
   const Vec3 vp = {viewpoint[0], viewpoint[1], viewpoint[2]};
   const int rc = launch_level_marking(nodes, boxes, N, size, vp, t, s);
   if (rc != HGS_OK) return rc;
@@ -240,8 +240,8 @@ int hgs_expand_to_size_nested(const int32_t* nodes, const float* boxes, int32_t 
   }
   HGS_HIP(hipSetDevice(device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char* p = static_cast<char*>(tmp);
-  const LevelTmp t = carve_levels(p, N, false);
+  Carver c(tmp);
+  const LevelTmp t = carve_levels(c, N, false);
   const Vec3 vp = {viewpoint[0], viewpoint[1], viewpoint[2]};
   hipLaunchKernelGGL(lod_mark_kernel, dim3((N + 255) / 256), dim3(256), 0, s, nodes, boxes, N, size, vp, t.emit_cnt,
                      t.block_sums, t.chain);

@@ -328,15 +328,15 @@ struct BudgetTmp : SumsTmp {
   uint32_t* state;       // [S_WORDS]
 };
 
-inline BudgetTmp carve_budget(char*& p, int32_t N) {
+inline BudgetTmp carve_budget(Carver& c, int32_t N) {
   const size_t n = (size_t)(N > 0 ? N : 1);
   BudgetTmp t;
-  t.sk = carve<uint32_t>(p, n);
-  t.ev = carve<uint32_t>(p, n);
-  t.emit_cnt = carve<uint32_t>(p, n);
-  static_cast<SumsTmp&>(t) = carve_sums(p, n, true);
-  t.hist = carve<uint32_t>(p, kBins);
-  t.state = carve<uint32_t>(p, S_WORDS);
+  t.sk = c.take<uint32_t>(n);
+  t.ev = c.take<uint32_t>(n);
+  t.emit_cnt = c.take<uint32_t>(n);
+  static_cast<SumsTmp&>(t) = carve_sums(c, n, true);
+  t.hist = c.take<uint32_t>(kBins);
+  t.state = c.take<uint32_t>(S_WORDS);
   return t;
 }
 
@@ -348,9 +348,9 @@ using namespace hgs;
 extern "C" {
 
 size_t hgs_lod_cut_budget_tmp_bytes(int32_t N) {
-  char* p = nullptr;
-  carve_budget(p, N);
-  return carved_bytes(p);
+  Carver c(nullptr);
+  carve_budget(c, N);
+  return c.bytes(kAlign);
 }
 
 int hgs_lod_cut_budget(const int32_t* nodes, const float* boxes, const float* bounds, int32_t N, float tau_min,
@@ -389,8 +389,8 @@ int hgs_lod_cut_budget(const int32_t* nodes, const float* boxes, const float* bo
   }
   HGS_HIP(hipSetDevice(device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char* p = static_cast<char*>(tmp);
-  const BudgetTmp t = carve_budget(p, N);
+  Carver c(tmp);
+  const BudgetTmp t = carve_budget(c, N);
   const Vec3 vp = {viewpoint[0], viewpoint[1], viewpoint[2]};
   Frustum f;
   for (int k = 0; k < 5; ++k)

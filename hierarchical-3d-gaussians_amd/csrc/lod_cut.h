@@ -220,12 +220,12 @@ struct SumsTmp {
   uint32_t* block_all;   // [nblk] unculled sums (with a cull)
   unsigned long long* chain;  // [scan_chunks(nblk)] published chunk totals of the scan (cleared by the kernel before it)
 };
-inline SumsTmp carve_sums(char*& p, size_t n, bool cull) {
+inline SumsTmp carve_sums(Carver& c, size_t n, bool cull) {
   const size_t nblk = (n + 255) / 256;
   SumsTmp t;
-  t.block_sums = carve<uint32_t>(p, nblk + (cull ? 2 : 1));
-  t.block_all = cull ? carve<uint32_t>(p, nblk) : nullptr;
-  t.chain = carve<unsigned long long>(p, (size_t)scan_chunks(nblk));
+  t.block_sums = c.take<uint32_t>(nblk + (cull ? 2 : 1));
+  t.block_all = cull ? c.take<uint32_t>(nblk) : nullptr;
+  t.chain = c.take<unsigned long long>((size_t)scan_chunks(nblk));
   return t;
 }
 
@@ -237,19 +237,17 @@ struct LevelTmp : SumsTmp {
   uint32_t* counts;      // [kMaxLevels + 2] frontier sizes of the levels
 };
 constexpr int kCountWords = kMaxLevels + 2;
-inline LevelTmp carve_levels(char*& p, int32_t N, bool cull) {
+// (a *_tmp_bytes call lays the workspace out on a null Carver and answers c.bytes(kAlign): common.h)
+inline LevelTmp carve_levels(Carver& c, int32_t N, bool cull) {
   const size_t n = (size_t)(N > 0 ? N : 1);
   LevelTmp t;
-  t.emit_cnt = carve<uint32_t>(p, n);
-  t.frontier_a = carve<int32_t>(p, n);
-  t.frontier_b = carve<int32_t>(p, n);
-  t.counts = carve<uint32_t>(p, kCountWords);
-  static_cast<SumsTmp&>(t) = carve_sums(p, n, cull);
+  t.emit_cnt = c.take<uint32_t>(n);
+  t.frontier_a = c.take<int32_t>(n);
+  t.frontier_b = c.take<int32_t>(n);
+  t.counts = c.take<uint32_t>(kCountWords);
+  static_cast<SumsTmp&>(t) = carve_sums(c, n, cull);
   return t;
 }
-// What a *_tmp_bytes call answers: where carving from address 0 ends (the same code lays the workspace out), plus the
-// slack for a base that is not aligned.
-inline size_t carved_bytes(const char* end) { return reinterpret_cast<size_t>(end) + kAlign; }
 
 // Level-by-level marking (lod.hip): t.emit_cnt = the count of every node the cut reaches, 0 elsewhere.  One launch per
 // tree level; the host looks at the frontier size every 8 levels; a hierarchy deeper than kMaxLevels is refused.

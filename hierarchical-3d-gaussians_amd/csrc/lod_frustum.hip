@@ -169,9 +169,9 @@ int hgs_hier_cull_bounds(const int32_t* nodes, int32_t N, const float* means, co
 }
 
 size_t hgs_lod_cut_view_tmp_bytes(int32_t N) {
-  char* p = nullptr;
-  carve_levels(p, N, true);
-  return carved_bytes(p);
+  Carver c(nullptr);
+  carve_levels(c, N, true);
+  return c.bytes(kAlign);
 }
 
 int hgs_lod_cut_view(const int32_t* nodes, const float* boxes, const float* bounds, int32_t N, float size,
@@ -191,8 +191,8 @@ int hgs_lod_cut_view(const int32_t* nodes, const float* boxes, const float* boun
   if (capacity < 0) { set_error("lod_cut_view: capacity = %d", capacity); return HGS_ERR_INVALID; }
   HGS_HIP(hipSetDevice(device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char* p = static_cast<char*>(tmp);
-  const LevelTmp t = carve_levels(p, N, true);
+  Carver c(tmp);
+  const LevelTmp t = carve_levels(c, N, true);
   const Vec3 vp = {viewpoint[0], viewpoint[1], viewpoint[2]};
   Frustum f;
   for (int k = 0; k < 5; ++k) f.p[k] = make_float4(planes[4 * k], planes[4 * k + 1], planes[4 * k + 2], planes[4 * k + 3]);

@@ -182,17 +182,17 @@ struct ViewsTmp {
 
 inline int clamp_views(int32_t V) { return V < 1 ? 1 : (V > kMaxViews ? kMaxViews : V); }
 
-inline ViewsTmp carve_views(char*& p, int32_t N, int32_t V) {
+inline ViewsTmp carve_views(Carver& c, int32_t N, int32_t V) {
   const size_t n = (size_t)(N > 0 ? N : 1);
   const int views = clamp_views(V);
   ViewsTmp t;
-  t.emit_cnt = carve<uint32_t>(p, (size_t)views * n);
+  t.emit_cnt = c.take<uint32_t>((size_t)views * n);
   t.cnt_stride = n;
-  const char* before = p;
-  t.sums0 = carve_sums(p, n, true);
-  t.sums_stride = (size_t)(p - before);
-  for (int v = 1; v < views; ++v) (void)carve_sums(p, n, true);
-  t.res = carve<uint32_t>(p, 2 * kMaxViews);
+  const size_t before = c.offset;
+  t.sums0 = carve_sums(c, n, true);
+  t.sums_stride = c.offset - before;
+  for (int v = 1; v < views; ++v) (void)carve_sums(c, n, true);
+  t.res = c.take<uint32_t>(2 * kMaxViews);
   return t;
 }
 
@@ -205,9 +205,9 @@ extern "C" {
 
 // (V outside [1, HGS_CUT_MAX_VIEWS] is answered as the nearest valid V: a size query has no error to return)
 size_t hgs_lod_cut_views_tmp_bytes(int32_t N, int32_t V) {
-  char* p = nullptr;
-  carve_views(p, N, V);
-  return carved_bytes(p);
+  Carver c(nullptr);
+  carve_views(c, N, V);
+  return c.bytes(kAlign);
 }
 
 int hgs_lod_cut_views(const int32_t* nodes, const float* boxes, const float* bounds, int32_t N, int32_t V,
@@ -239,8 +239,8 @@ int hgs_lod_cut_views(const int32_t* nodes, const float* boxes, const float* bou
   if (capacity < 0) { set_error("lod_cut_views: capacity = %d", capacity); return HGS_ERR_INVALID; }
   HGS_HIP(hipSetDevice(device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char* p = static_cast<char*>(tmp);
-  const ViewsTmp t = carve_views(p, N, V);
+  Carver c(tmp);
+  const ViewsTmp t = carve_views(c, N, V);
   const bool cull = bounds != nullptr;
   ViewsArgs va;
   for (int v = 0; v < kMaxViews; ++v) {

@@ -1976,22 +1976,21 @@ int launch_scan_block_sums(const GeomWs& g, int32_t P, hipStream_t s, bool debug
   return HGS_OK;
 }
 
-int launch_preprocess_bwd(const hgs_raster_args& a, const GeomWs& g, const float* inst_grads, float* drgb,
-                          float* dmean_rows, const uint32_t* lod_flag, const hgs_raster_grads& out, uint32_t L,
-                          uint2* work, uint32_t* work_counter, hipStream_t s) {
+int launch_preprocess_bwd(const hgs_raster_args& a, const GeomWs& g, const BwdWs& w, const hgs_raster_grads& out, uint32_t L,
+                          hipStream_t s) {
   const int nblk = (a.P + kPreBlock - 1) / kPreBlock;
   if (nblk > 0) {
     // long runs first, when the frame has them: mean run above 6 records (L > 6 P; HGS_K8_PRESUM=0 / 1 forces)
     static const char* force = getenv("HGS_K8_PRESUM");
     const bool presum = force ? force[0] == '1' : (uint64_t)L > 6ull * (uint64_t)a.P;
     if (presum) {
-      HGS_HIP(hipMemsetAsync(work_counter, 0, sizeof(uint32_t), s));
+      HGS_HIP(hipMemsetAsync(w.work_counter, 0, sizeof(uint32_t), s));
       hipLaunchKernelGGL(k8_worklist_kernel, dim3(nblk < kWorklistGrid ? nblk : kWorklistGrid), dim3(kPreBlock), 0, s, a.P,
-                         g.tiles_touched, work, work_counter);
+                         g.tiles_touched, w.work, w.work_counter);
       HGS_LAUNCH_CHECK("preprocess_bwd_worklist", s, a.debug);
       const int want = (int)(((size_t)L / 64 + 3) / 4);                   // no more workgroups than a pair each could use
       hipLaunchKernelGGL(k8_presum_work_kernel, dim3(want < 1 ? 1 : (want < kPresumGrid ? want : kPresumGrid)), dim3(kPreBlock), 0,
-                         s, work, work_counter, g.tiles_touched, g.offsets, const_cast<float*>(inst_grads));
+                         s, w.work, w.work_counter, g.tiles_touched, g.offsets, w.inst_grads);
       HGS_LAUNCH_CHECK("preprocess_bwd_long_runs", s, a.debug);
     }
     // the drop-in training call: K8a and K8b as one kernel (HGS_K8_FUSE=0 keeps them apart; read on every call)
@@ -2003,13 +2002,13 @@ int launch_preprocess_bwd(const hgs_raster_args& a, const GeomWs& g, const float
       const size_t stage_bytes = (size_t)(kPreBlock / 64) * kK8StageRec * 5 * sizeof(float2);
       const size_t rows_bytes = (size_t)kPreBlock * (a.M * 3 + 4) * sizeof(float);
       hipLaunchKernelGGL(preprocess_bwd_sh_kernel, dim3(nblk), dim3(kPreBlock),
-                         stage_bytes > rows_bytes ? stage_bytes : rows_bytes, s, a, g, inst_grads, out, presum ? 1 : 0);
+                         stage_bytes > rows_bytes ? stage_bytes : rows_bytes, s, a, g, w.inst_grads, out, presum ? 1 : 0);
       HGS_LAUNCH_CHECK("preprocess_bwd_sh", s, a.debug);
       return HGS_OK;
     }
     auto k8a = a.lod_render_indices ? preprocess_bwd_kernel<false, true>      // (accumulation is refused with lod, abi.cpp)
                                     : (a.accumulate_grads ? preprocess_bwd_kernel<true, false> : preprocess_bwd_kernel<false, false>);
-    hipLaunchKernelGGL(k8a, dim3(nblk), dim3(kPreBlock), 0, s, a, g, inst_grads, drgb, dmean_rows, lod_flag, out,
+    hipLaunchKernelGGL(k8a, dim3(nblk), dim3(kPreBlock), 0, s, a, g, w.inst_grads, w.drgb, w.dmean_rows, w.lod_flag, out,
                        presum ? 1 : 0);
     HGS_LAUNCH_CHECK("preprocess_bwd", s, a.debug);
     if (a.shs && out.dL_dshs && !a.defer_sh_bwd) {
@@ -2017,7 +2016,7 @@ int launch_preprocess_bwd(const hgs_raster_args& a, const GeomWs& g, const float
       auto k8b = a.lod_render_indices ? sh_bwd_kernel<false, true, true>
                  : (a.prepare_backward && a.shs) ? (a.accumulate_grads ? sh_bwd_kernel<true, true, false> : sh_bwd_kernel<false, true, false>)
                                                  : (a.accumulate_grads ? sh_bwd_kernel<true, false, false> : sh_bwd_kernel<false, false, false>);
-      hipLaunchKernelGGL(k8b, dim3(nblk), dim3(kPreBlock), lds_bytes, s, a, g, drgb, dmean_rows, lod_flag, out);
+      hipLaunchKernelGGL(k8b, dim3(nblk), dim3(kPreBlock), lds_bytes, s, a, g, w.drgb, w.dmean_rows, w.lod_flag, out);
       HGS_LAUNCH_CHECK("sh_bwd", s, a.debug);
     }
   }

@@ -185,13 +185,12 @@ struct SortTmp {
 inline uint32_t rs_blocks(uint32_t n, int items) { return (n + kRsThreads * items - 1) / (kRsThreads * items); }
 
 template <typename K>
-inline SortTmp<K> carve_sort_tmp(void* tmp, uint32_t n) {
-  char* p = static_cast<char*>(tmp);
+inline SortTmp<K> carve_sort_tmp(Carver& c, uint32_t n) {
   SortTmp<K> t;
-  t.keys_alt = carve<K>(p, n);
-  t.vals_alt = carve<uint32_t>(p, n);
-  t.counts = carve<uint32_t>(p, (size_t)kRadix * rs_blocks(n, rs_items(n)));
-  t.totals = carve<uint32_t>(p, kRadix);
+  t.keys_alt = c.take<K>(n);
+  t.vals_alt = c.take<uint32_t>(n);
+  t.counts = c.take<uint32_t>((size_t)kRadix * rs_blocks(n, rs_items(n)));
+  t.totals = c.take<uint32_t>(kRadix);
   return t;
 }
 
@@ -203,7 +202,8 @@ int sort_pairs_t(const K* keys_in, const uint32_t* vals_in, K* keys_out, uint32_
   if (end_bit < 1) end_bit = 1;
   if (end_bit > maxbit) end_bit = maxbit;
   const int passes = (end_bit + 7) / 8;
-  const SortTmp<K> t = carve_sort_tmp<K>(tmp, n);
+  Carver c(tmp);
+  const SortTmp<K> t = carve_sort_tmp<K>(c, n);
   const uint32_t nblk = rs_blocks(n, ITEMS);
   // ping-pong between (out) and (alt) such that the LAST pass writes (out); pass 0 reads (in).
   const K* src_k = keys_in;
@@ -232,8 +232,9 @@ int sort_pairs_t(const K* keys_in, const uint32_t* vals_in, K* keys_out, uint32_
 }  // namespace
 
 size_t sort_tmp_bytes(uint32_t n) {   // sized for 64-bit keys (covers the 32-bit sorts too)
-  return align_up((size_t)n * 8) + align_up((size_t)n * 4) +
-         align_up((size_t)kRadix * rs_blocks(n, rs_items(n)) * 4) + align_up(kRadix * 4) + kAlign;
+  Carver c(nullptr);
+  carve_sort_tmp<uint64_t>(c, n);
+  return c.bytes(kAlign);
 }
 
 int sort_pairs(const uint64_t* keys_in, const uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out,

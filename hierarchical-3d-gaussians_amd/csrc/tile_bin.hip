@@ -47,19 +47,20 @@ __device__ __forceinline__ BandStream band_stream(const uint32_t* __restrict__ b
 }
 
 // The binning scratch (BinWs::sort_tmp): the count table, the group sums, then -- adjacent, cleared together by K3
-// (binning.hip: zero_words) -- the tile totals and the arrival counters of the chunk groups.
+// (binning.hip: zero_words; zero_count words from totals on) -- the tile totals and the arrival counters of the chunk groups.
 struct TbScratch {
   uint32_t *table, *gsum, *totals, *arrive;
+  int zero_count;
 };
-__host__ inline TbScratch tb_carve(void* tmp, uint32_t L_cap, int32_t T, uint32_t chunk) {
+__host__ inline TbScratch tb_carve(Carver& c, uint32_t L_cap, int32_t T, uint32_t chunk) {
   const size_t max_chunks = ((size_t)(L_cap ? L_cap : 1) + chunk - 1) / chunk;
   const size_t per = band_tiles(T), Tp = per * kBands;
-  char* c = static_cast<char*>(tmp);
   TbScratch t;
-  t.table = carve<uint32_t>(c, (size_t)kBands * max_chunks * per);
-  t.gsum = carve<uint32_t>(c, (size_t)kGroups * Tp);
-  t.totals = carve<uint32_t>(c, Tp + (size_t)kBands * kGroups);
-  t.arrive = t.totals + Tp;
+  t.table = c.take<uint32_t>((size_t)kBands * max_chunks * per);
+  t.gsum = c.take<uint32_t>((size_t)kGroups * Tp);
+  t.zero_count = (int)(Tp + (size_t)kBands * kGroups);
+  t.totals = c.take<uint32_t>((size_t)t.zero_count);
+  t.arrive = t.totals ? t.totals + Tp : nullptr;
   return t;
 }
 
@@ -398,17 +399,17 @@ bool tile_bin_supported(int32_t T) { return T <= kMaxTiles; }
 
 size_t tile_bin_tmp_bytes(uint32_t L, int32_t T) {
   if (!tile_bin_supported(T)) return 0;
-  const uint32_t chunk = tb_chunk(T);
-  const size_t max_chunks = ((size_t)(L ? L : 1) + chunk - 1) / chunk;
-  const size_t per = band_tiles(T), Tp = per * kBands;
-  return align_up(kBands * max_chunks * per * 4) + align_up((size_t)kGroups * Tp * 4) +
-         align_up((Tp + (size_t)kBands * kGroups) * 4) + kAlign;
+  Carver c(nullptr);
+  tb_carve(c, L, T, tb_chunk(T));
+  return c.bytes(kAlign);
 }
 
-uint32_t* tile_bin_zero_words(void* tmp, uint32_t L_cap, int32_t T) {
-  return tile_bin_supported(T) ? tb_carve(tmp, L_cap, T, tb_chunk(T)).totals : nullptr;
+TileBinZero tile_bin_zero_range(void* tmp, uint32_t L_cap, int32_t T) {
+  if (!tile_bin_supported(T)) return {nullptr, 0};
+  Carver c(tmp);
+  const TbScratch t = tb_carve(c, L_cap, T, tb_chunk(T));
+  return {t.totals, t.zero_count};
 }
-int tile_bin_zero_count(int32_t T) { return tile_bin_supported(T) ? band_tiles(T) * kBands + kBands * kGroups : 0; }
 
 // keys / vals: the banded instance streams (band-local tile id, Gaussian id); vals_out: ids grouped by tile (unordered
 // inside a tile); ranges [T,2], the depth-sort class counters (big[0..2]) and the compositing kernels' launch order
@@ -420,7 +421,8 @@ int launch_tile_bin(const uint32_t* keys, const uint32_t* vals, uint32_t* vals_o
   const uint32_t chunk = tb_chunk(T);
   const int max_chunks = (int)(((size_t)L_cap + chunk - 1) / chunk);
   const int per = band_tiles(T), Tp = per * kBands, col = nblk + 1;
-  const TbScratch t = tb_carve(tmp, L_cap, T, chunk);
+  Carver c(tmp);
+  const TbScratch t = tb_carve(c, L_cap, T, chunk);
   const size_t lds = (size_t)per * 4;          // <= 16 KiB (T <= 32768)
   hipLaunchKernelGGL(tb_count_kernel, dim3(kBands * max_chunks), dim3(kTbThreads), lds, s, keys, L_cap, band_totals, col, per,
                      chunk, max_chunks, t.table, t.gsum, t.totals, t.arrive, Tp, super,

@@ -23,8 +23,10 @@ constexpr int64_t kMaxRows = 0x7fffffff;
 constexpr int kPerThread = 4;      // elements per apply thread, 256 apart: four rounds of loads in flight
 
 // tmp: [the word, one kAlign block][P class bytes]
-__host__ __device__ inline uint32_t* tmp_word(void* tmp) { return static_cast<uint32_t*>(tmp); }
-__host__ __device__ inline uint8_t* tmp_cls(void* tmp) { return static_cast<uint8_t*>(tmp) + kAlign; }
+struct StepTmp { uint32_t* word; uint8_t* cls; };
+inline StepTmp carve_step(Carver& c, int64_t P) {     // (a braced list is evaluated left to right)
+  return {c.take<uint32_t>(1), c.take<uint8_t>((size_t)(P > 0 ? P : 1))};
+}
 
 // torch.maximum: a NaN operand gives NaN
 __device__ __forceinline__ float nan_max(float a, float b) { return (a != a) ? a : ((b != b) ? b : fmaxf(a, b)); }
@@ -204,7 +206,9 @@ using namespace hgs;
 
 extern "C" size_t hgs_step_tmp_bytes(int64_t P) {
   if (P < 0 || P > kMaxRows) { set_error("step: bad sizes (P = %lld outside [0, 2^31 - 1])", (long long)P); return 0; }
-  return kAlign + align_up((size_t)(P > 0 ? P : 1));
+  Carver c(nullptr);
+  carve_step(c, P);
+  return c.bytes(0);   // this workspace never had a slack block
 }
 
 extern "C" int hgs_step_select(const hgs_step_args* a, void* tmp, hgs_stream_t stream, int device) {
@@ -226,9 +230,10 @@ extern "C" int hgs_step_select(const hgs_step_args* a, void* tmp, hgs_stream_t s
   const int64_t threads = A.n > A.P ? A.n : A.P;
   HGS_HIP(hipSetDevice(device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  HGS_HIP(hipMemsetAsync(tmp_word(tmp), 0, sizeof(uint32_t), s));
-  hipLaunchKernelGGL(step_select_kernel, dim3((uint32_t)((threads + 256 * kSelectRounds - 1) / (256 * kSelectRounds))), dim3(256), 0, s, A, tmp_word(tmp),
-                     tmp_cls(tmp));
+  Carver c(tmp);
+  const StepTmp t = carve_step(c, A.P);
+  HGS_HIP(hipMemsetAsync(t.word, 0, sizeof(uint32_t), s));
+  hipLaunchKernelGGL(step_select_kernel, dim3((uint32_t)((threads + 256 * kSelectRounds - 1) / (256 * kSelectRounds))), dim3(256), 0, s, A, t.word, t.cls);
   HGS_LAUNCH_CHECK("step_select", s, false);
   return HGS_OK;
 }
@@ -275,10 +280,12 @@ extern "C" int hgs_step_apply(const hgs_step_args* a, const hgs_step_tensor* ten
   for (int k = n_tensors; k <= kMaxTensors; ++k) L.first_block[k] = (uint32_t)nb;
   HGS_HIP(hipSetDevice(device));
   hipStream_t s = static_cast<hipStream_t>(stream);
+  Carver c(const_cast<void*>(tmp));
+  const StepTmp st = carve_step(c, P);
   void (*kern)(StepLaunch, int, int64_t, int, int, float, const uint32_t*, const uint8_t*) =
       wide ? step_apply_kernel<int64_t> : step_apply_kernel<uint32_t>;
   hipLaunchKernelGGL(kern, dim3((uint32_t)nb), dim3(256), 0, s, L, n_tensors, P, a->select_all, a->clamp,
-                     a->clamp_threshold, tmp_word(const_cast<void*>(tmp)), tmp_cls(const_cast<void*>(tmp)));
+                     a->clamp_threshold, st.word, st.cls);
   HGS_LAUNCH_CHECK("step_apply", s, false);
   return HGS_OK;
 }
