@@ -7,6 +7,9 @@
 // node's hemisphere first (:212-216).  Used when GaussianRasterizationSettings.render_indices /
 // parent_indices are passed NON-empty (the reference's settings fields exist for exactly this; its own
 // glue always passes them empty, so this path is reached only by callers that opt in).
+// The gather follows the torch expression to the letter: both rows are read whatever the weight, and with w_i = 1 a
+// non-finite parent attribute makes the row non-finite (0 * NaN).  Only the in-kernel interpolation of the per-Gaussian
+// kernels (gaussian_math.h: lod_row_gather) leaves the parent of a weight-1 row unread.
 //
 // Backward: node rows are unique in an LOD cut (plain stores); a parent row collects up to k sibling
 // contributions.  Siblings are adjacent in expand_to_size's output (ascending node index, children

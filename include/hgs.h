@@ -414,7 +414,11 @@ int hgs_lod_cut_views(const int32_t* nodes, const float* boxes, const float* bou
 /* In-op LOD attribute interpolation: the gather + lerp that render_post does in Python
  * (gaussian_renderer/__init__.py:199-218), for callers that pass GaussianRasterizationSettings.render_indices /
  * parent_indices non-empty.  out_i = w_i * attr[render_indices[i]] + (1 - w_i) * attr[parent_indices[i]]; rotations
- * with the parent quaternion flipped into the node's hemisphere.  Any attribute pointer may be NULL (skipped). */
+ * with the parent quaternion flipped into the node's hemisphere.  Any attribute pointer may be NULL (skipped).
+ * Every product and the sum are rounded separately and BOTH rows are always read, exactly as the torch expression: a
+ * weight of exactly 1 still multiplies the parent row by 0, so a non-finite parent attribute gives a non-finite row
+ * (0 * NaN is NaN).  The weight-1 rule of the in-kernel interpolation (hgs_raster_args.lod_render_indices; stated at
+ * lod_row_gather in csrc/gaussian_math.h: the parent of a weight-1 row is not read) does NOT hold for this call. */
 int hgs_lod_gather(const int32_t* render_indices, const int32_t* parent_indices, const float* weights, int32_t n,
                    int32_t M, const float* means3D, const float* scales, const float* rotations, const float* shs,
                    const float* opacities, float* o_means3D, float* o_scales, float* o_rotations, float* o_shs,
