@@ -214,6 +214,13 @@ static int validate(const hgs_raster_args* a) {
   if (a->P < 0 || a->width <= 0 || a->height <= 0) { set_error("bad sizes P=%d W=%d H=%d", a->P, a->width, a->height); return HGS_ERR_INVALID; }
   if (grid_x(a->width) > 1023 || grid_y(a->height) > 1023) { set_error("image larger than 16368 px per side is not supported"); return HGS_ERR_INVALID; }
   if (!a->bg || !a->viewmatrix || !a->projmatrix || !a->campos) { set_error("bg/viewmatrix/projmatrix/campos must be device pointers"); return HGS_ERR_INVALID; }
+  // half-precision attribute rows (lod_half_rows): one forward-only instantiation of K1's in-kernel LOD route reads them
+  if (a->lod_half_rows != 0 && a->lod_half_rows != 1) { set_error("lod_half_rows = %d: 0 (float32 rows) or 1 (half rows)", a->lod_half_rows); return HGS_ERR_INVALID; }
+  if (a->lod_half_rows) {
+    if (!a->lod_render_indices) { set_error("lod_half_rows needs lod_render_indices: half rows are read by the in-kernel LOD interpolation only"); return HGS_ERR_INVALID; }
+    if (a->prepare_backward) { set_error("lod_half_rows is forward only: prepare_backward must be 0"); return HGS_ERR_INVALID; }
+    if (a->shs_rest || a->activations || a->colors_precomp || a->cov3D_precomp) { set_error("lod_half_rows takes shs, scales and rotations as halves: no shs_rest, activations, colors_precomp or cov3D_precomp"); return HGS_ERR_INVALID; }
+  }
   if (a->P > 0) {
     if (!a->means3D || !a->opacities) { set_error("means3D/opacities missing"); return HGS_ERR_INVALID; }
     if ((a->shs != nullptr) == (a->colors_precomp != nullptr)) { set_error("provide exactly one of shs / colors_precomp"); return HGS_ERR_INVALID; }
@@ -405,6 +412,7 @@ int hgs_raster_bwd(const hgs_raster_args* a, const void* geom_ws, const void* bi
                    void* bwd_ws, uint32_t L, const float* out_color, const float* out_invdepth,
                    const float* dL_dcolor, const float* dL_dinvdepth, const hgs_raster_grads* grads,
                    hgs_stream_t stream, int device) {
+  if (a && a->lod_half_rows != 0) { set_error("hgs_raster_bwd: lod_half_rows is forward only (there is no backward through half rows)"); return HGS_ERR_INVALID; }
   int rc = validate(a);
   if (rc) return rc;
   if (!geom_ws || !bin_ws || !img_ws || !bwd_ws || !out_color || !dL_dcolor || !grads) { set_error("null workspace/input"); return HGS_ERR_INVALID; }

@@ -275,7 +275,9 @@ __device__ __forceinline__ LodRow lod_row(const hgs_raster_args& a, int idx) {
 // 236 bytes.  Differences to the Python expression t * x[r] + (1 - t) * x[p]: a -0.0 attribute stays -0.0 (the
 // expression gives +0.0 next to a positive parent value) and a non-finite parent attribute does not reach rows it has
 // no weight in.  The gradient scatter keeps using lod_row: the parent of a weight-1 row still belongs to its siblings'
-// run.
+// run.  (The loaders below read float32 arrays.  Their forms for arrays of IEEE half -- hgs_raster_args.lod_half_rows --
+// sit beside coop_gather_sh in preprocess.hip, K1 being their only user: this header is also compiled for the host on
+// its own and must not pull in half_widen.h.  They share lod_row_gather and lod_lerp with the loaders here.)
 template <bool LOD>
 __device__ __forceinline__ LodRow lod_row_gather(const hgs_raster_args& a, int idx) {
   LodRow l = lod_row<LOD>(a, idx);

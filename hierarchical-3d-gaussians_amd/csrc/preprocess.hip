@@ -5,6 +5,7 @@
 // SURVEY.md App. A 1-6, 9-10).  HBM-bound streaming kernels: 236 B in per Gaussian
 // at SH degree 3 (fwd), 236 B in + 248 B out (bwd).
 #include "gaussian_math.h"
+#include "half_widen.h"
 
 #include <stdlib.h>
 
@@ -266,6 +267,64 @@ __device__ __forceinline__ void load_sh_lod(const hgs_raster_args& a, int idx, f
 #pragma unroll
   for (int i = 0; i < 48; ++i)
     if (i < n) sh[i] = lod_lerp(x[i], y[i], l.w, l.u);
+}
+
+// ---- half-precision attribute rows (hgs_raster_args.lod_half_rows: the half SLOTS of the budgeted residency) ----------------
+// The forms of the LOD loaders above (gaussian_math.h: load_scale_rot / load_opacity; coop_gather_sh, load_sh_lod) for
+// arrays of IEEE half: every value is widened as it is loaded (half_widen.h: exact) and then takes the float32 path -- the
+// same lod_row_gather (weight 1: p = r, the loads stay unconditional), the same separately rounded lod_lerp, the same
+// hemisphere flip -- so the row is bit for bit the one float32 arrays holding the widened values give.  The mean stays
+// float32 (load_mean).  A gathered row is 6 M + 28 bytes instead of 4 (3 M + 11).
+//
+// The cooperative SH gather, one lane per 16-byte chunk = eight halves, which become two float4 of the row's LDS slot
+// (the layout coop_gather_sh writes; at M = 16 a row is six chunks).  Needs n % 8 == 0 (6 M % 16 == 0: rows start on
+// 16-byte boundaries, and so do the LDS slots at a stride of n + 4 floats).
+__device__ __forceinline__ void coop_gather_sh_half(const void* __restrict__ shs, int block_first, int P, int n, float* lds) {
+  const int count = min(kPreBlock, P - block_first);
+  const int cpr = n / 8;                                        // 16-byte chunks per row
+  const int stride = sh_row_stride(n);
+  const uint4* src = static_cast<const uint4*>(shs);
+  for (int v = threadIdx.x; v < count * cpr; v += kPreBlock) {
+    const int row = v / cpr, c = v - row * cpr;
+    const float* pad = lds + row * stride + n;
+    const size_t r = (size_t)__float_as_uint(pad[0]), p = (size_t)__float_as_uint(pad[1]);
+    const float w = pad[2], u = 1.0f - w;
+    const uint4 xb = src[r * cpr + c], yb = src[p * cpr + c];   // (weight 1: p = r, see lod_row_gather)
+    float x[8], y[8];
+    widen8(xb, x);
+    widen8(yb, y);
+    float4* dst = reinterpret_cast<float4*>(lds + row * stride + c * 8);
+    dst[0] = make_float4(lod_lerp(x[0], y[0], w, u), lod_lerp(x[1], y[1], w, u), lod_lerp(x[2], y[2], w, u), lod_lerp(x[3], y[3], w, u));
+    dst[1] = make_float4(lod_lerp(x[4], y[4], w, u), lod_lerp(x[5], y[5], w, u), lod_lerp(x[6], y[6], w, u), lod_lerp(x[7], y[7], w, u));
+  }
+}
+// per lane, 2-byte loads: the route of every other M (a row of 6 M bytes then starts off a 16-byte boundary)
+__device__ __forceinline__ void load_sh_lod_half(const hgs_raster_args& a, int idx, float sh[48]) {
+  const LodRow l = lod_row_gather<true>(a, idx);
+  const int n = a.M * 3;
+  const uint16_t* x = reinterpret_cast<const uint16_t*>(a.shs) + l.r * n;
+  const uint16_t* y = reinterpret_cast<const uint16_t*>(a.shs) + l.p * n;
+#pragma unroll
+  for (int i = 0; i < 48; ++i)
+    if (i < n) sh[i] = lod_lerp(widen_half(x[i]), widen_half(y[i]), l.w, l.u);
+}
+// scales: three 2-byte loads (rows are 6 bytes apart); rotation: one 8-byte load
+__device__ __forceinline__ void load_scale_rot_half(const hgs_raster_args& a, int idx, float sc[3], float q[4]) {
+  const LodRow l = lod_row_gather<true>(a, idx);
+  const uint16_t* s16 = reinterpret_cast<const uint16_t*>(a.scales);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) sc[k] = lod_lerp(widen_half(s16[l.r * 3 + k]), widen_half(s16[l.p * 3 + k]), l.w, l.u);
+  const uint2 ra = reinterpret_cast<const uint2*>(a.rotations)[l.r], rb = reinterpret_cast<const uint2*>(a.rotations)[l.p];
+  const float4 qa = make_float4(widen_half(ra.x & 0xffffu), widen_half(ra.x >> 16), widen_half(ra.y & 0xffffu), widen_half(ra.y >> 16));
+  const float4 qb = make_float4(widen_half(rb.x & 0xffffu), widen_half(rb.x >> 16), widen_half(rb.y & 0xffffu), widen_half(rb.y >> 16));
+  const float sgn = (qa.x * qb.x + qa.y * qb.y + qa.z * qb.z + qa.w * qb.w) < 0.0f ? -1.0f : 1.0f;
+  q[0] = lod_lerp(qa.x, sgn * qb.x, l.w, l.u); q[1] = lod_lerp(qa.y, sgn * qb.y, l.w, l.u);
+  q[2] = lod_lerp(qa.z, sgn * qb.z, l.w, l.u); q[3] = lod_lerp(qa.w, sgn * qb.w, l.w, l.u);
+}
+__device__ __forceinline__ float load_opacity_half(const hgs_raster_args& a, int idx) {
+  const LodRow l = lod_row_gather<true>(a, idx);
+  const uint16_t* o16 = reinterpret_cast<const uint16_t*>(a.opacities);
+  return lod_lerp(widen_half(o16[l.r]), widen_half(o16[l.p]), l.w, l.u);
 }
 
 
@@ -536,15 +595,18 @@ __device__ __forceinline__ void wave_store_jac(float* __restrict__ dst, size_t r
   __builtin_amdgcn_wave_barrier();               // (the next use of wave_lds overwrites it)
 }
 
-template <bool JAC, bool LOD, bool DEFER, bool H48>
+template <bool JAC, bool LOD, bool DEFER, bool H48, bool HALF = false>
                                 // JAC: also store d(rgb)/d(direction) for the backward; LOD: in-kernel LOD
                                 // interpolation; DEFER: the plain [P, M, 3] coefficient block is loaded into registers
                                 // ahead of the double-precision chain (their own instantiations: the extra state
                                 // would cost every other caller of K1 its occupancy); H48: plain [P, 16, 3] block
-                                // straight into LDS by DMA (above; DEFER and LOD do not apply)
+                                // straight into LDS by DMA (above; DEFER and LOD do not apply); HALF: the LOD route
+                                // on arrays of IEEE half (lod_half_rows), widened on load -- forward only
 __device__ __forceinline__ void preprocess_fwd_body(const hgs_raster_args& a, const GeomWs& g,
                                                     int32_t* __restrict__ radii, uint32_t* __restrict__ super, uint32_t heavy_thr) {
   static_assert(!(H48 && (LOD || DEFER)), "the DMA route is the plain layout's");
+  static_assert(!HALF || (LOD && !JAC && !DEFER), "half rows: the in-kernel LOD route, forward only");
+  constexpr int kShMask = HALF ? 7 : 3;          // the cooperative SH route moves 16-byte chunks: four floats, eight halves
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   float* lds_sh = reinterpret_cast<float*>(smem_raw);
   __shared__ uint32_t wave_tot[kPreBlock / 64];
@@ -570,7 +632,7 @@ __device__ __forceinline__ void preprocess_fwd_body(const hgs_raster_args& a, co
   if (idx < a.P) {
     const LodRow lr = lod_row_gather<LOD>(a, idx);     // (its node / parent / weight also steer the cooperative SH gather)
     load_mean<LOD>(a, lr, p);
-    if (lod && a.shs && (shn & 3) == 0) {
+    if (lod && a.shs && (shn & kShMask) == 0) {
       // the cooperative SH gather below needs every row's (node row, parent row, weight): they ride in the four pad
       // floats at the end of the row's LDS slot
       float* pad = lds_sh + threadIdx.x * sh_row_stride(shn) + shn;
@@ -587,7 +649,8 @@ __device__ __forceinline__ void preprocess_fwd_body(const hgs_raster_args& a, co
 #pragma unroll
       for (int i = 0; i < 6; ++i) pr.c3[i] = a.cov3D_precomp[(size_t)idx * 6 + i];
     } else {
-      load_scale_rot<LOD>(a, idx, sc_act, q_act, nullptr);
+      if constexpr (HALF) load_scale_rot_half(a, idx, sc_act, q_act);
+      else load_scale_rot<LOD>(a, idx, sc_act, q_act, nullptr);
       float R[9], s[3];
       cov3d_from_scale_rot(sc_act, a.scale_modifier, q_act, pr.c3, R, s);
     }
@@ -605,7 +668,7 @@ __device__ __forceinline__ void preprocess_fwd_body(const hgs_raster_args& a, co
   // SH coefficients: stream the workgroup's block through LDS when most of it is visible (coalesced),
   // fall back to per-lane loads (visible lanes only) when most of the block is culled.
   bool coop = false, deferred = false;
-  const bool sh_lds = a.shs && (shn & 3) == 0;
+  const bool sh_lds = a.shs && (shn & kShMask) == 0;
   const int nvis = __syncthreads_count(pr.visible);        // (also orders wave_tot / band_cnt)
   if (threadIdx.x < 64) {                                  // (wave 0) raw sums; with `super` also into the superblock totals
     uint32_t mine = 0;
@@ -638,7 +701,8 @@ __device__ __forceinline__ void preprocess_fwd_body(const hgs_raster_args& a, co
       if constexpr (H48) {
         sh48_issue_rows(a.shs, blockIdx.x * kPreBlock, a.P, ((a.sh_degree + 1) * (a.sh_degree + 1) * 3 + 3) / 4, lds_sh);
       } else if (lod) {
-        coop_gather_sh(a.shs, blockIdx.x * kPreBlock, a.P, shn, lds_sh);
+        if constexpr (HALF) coop_gather_sh_half(a.shs, blockIdx.x * kPreBlock, a.P, shn, lds_sh);
+        else coop_gather_sh(a.shs, blockIdx.x * kPreBlock, a.P, shn, lds_sh);
       } else if (a.shs_rest) {
         coop_load_seg(a.shs, blockIdx.x * kPreBlock, a.P, 3, 0, sh_row_stride(shn), lds_sh);
         coop_load_seg(a.shs_rest, blockIdx.x * kPreBlock, a.P, shn - 3, 3, sh_row_stride(shn), lds_sh);
@@ -661,7 +725,8 @@ __device__ __forceinline__ void preprocess_fwd_body(const hgs_raster_args& a, co
     if (pr.clampx) flags |= 8u;
     if (pr.clampy) flags |= 16u;
     if constexpr (!H48) {
-      opac = load_opacity<LOD>(a, idx, nullptr);
+      if constexpr (HALF) opac = load_opacity_half(a, idx);
+      else opac = load_opacity<LOD>(a, idx, nullptr);
       if (a.interpolation_weights && a.num_node_kids && !a.lod_per_pixel)     // (per pixel: the compositing kernels remap alpha)
         opac = lod_opacity(opac, a.interpolation_weights[idx], a.num_node_kids[idx], nullptr);
     }
@@ -705,6 +770,7 @@ __device__ __forceinline__ void preprocess_fwd_body(const hgs_raster_args& a, co
     } else {
       float sh[48];
       if (coop) lds_row_read(lds_sh, shn, sh);
+      else if (lod && HALF) load_sh_lod_half(a, idx, sh);
       else if (lod) load_sh_lod(a, idx, sh);
       else if (a.shs_rest) load_sh_split(a.shs, a.shs_rest, idx, a.M, sh);
       else load_sh(a.shs, idx, a.M, sh);
@@ -778,6 +844,12 @@ template <bool JAC, bool LOD, bool DEFER>
 __global__ __launch_bounds__(kPreBlock) void preprocess_fwd_kernel(hgs_raster_args a, GeomWs g,
                                                                    int32_t* __restrict__ radii, uint32_t* __restrict__ super, uint32_t heavy_thr) {
   preprocess_fwd_body<JAC, LOD, DEFER, false>(a, g, radii, super, heavy_thr);
+}
+// In-kernel LOD interpolation on half-precision rows (hgs_raster_args.lod_half_rows): forward only, no Jacobian.
+__global__ __launch_bounds__(kPreBlock) void preprocess_fwd_lod_half_kernel(hgs_raster_args a, GeomWs g,
+                                                                            int32_t* __restrict__ radii,
+                                                                            uint32_t* __restrict__ super, uint32_t heavy_thr) {
+  preprocess_fwd_body<false, true, false, false, true>(a, g, radii, super, heavy_thr);
 }
 // The M = 16 DMA route: 48 KB of LDS per workgroup (three workgroups per compute unit), the registers held to what four
 // waves per SIMD leave (128).
@@ -1943,7 +2015,8 @@ int launch_preprocess_fwd(const hgs_raster_args& a, const GeomWs& g, int32_t* ra
     const bool h48 = plain && a.M == 16;
     const bool defer = plain && !h48;
     const size_t lds_bytes = !a.shs ? 0 : h48 ? (size_t)kK1ImageBytes : (size_t)kPreBlock * (a.M * 3 + 4) * sizeof(float);
-    auto k1 = a.lod_render_indices ? (jac ? preprocess_fwd_kernel<true, true, false> : preprocess_fwd_kernel<false, true, false>)
+    auto k1 = a.lod_half_rows      ? preprocess_fwd_lod_half_kernel     // (only with lod_render_indices, never jac: abi.cpp)
+              : a.lod_render_indices ? (jac ? preprocess_fwd_kernel<true, true, false> : preprocess_fwd_kernel<false, true, false>)
               : h48   ? (jac ? preprocess_fwd_h48_kernel<true> : preprocess_fwd_h48_kernel<false>)
               : defer ? (jac ? preprocess_fwd_kernel<true, false, true> : preprocess_fwd_kernel<false, false, true>)
                       : (jac ? preprocess_fwd_kernel<true, false, false> : preprocess_fwd_kernel<false, false, false>);

@@ -7,6 +7,7 @@
 // resid_fetch_kernel below) -- PCIe carries exactly the rows that are needed, there is no host-side gather and no
 // staging copy.  Slots are recycled by age (frames since the last use) when the free list runs out.
 #include "common.h"
+#include "half_widen.h"
 
 namespace hgs {
 namespace {
@@ -131,22 +132,7 @@ __global__ __launch_bounds__(256) void resid_fetch_kernel(const int32_t* __restr
 // A row is eight 16-byte chunks: chunks 0..5 hold 48 halves of SH, chunk 6 rotation (4 halves), scale (3) and opacity
 // (1), chunk 7 the mean as three float32 and four bytes of padding.
 
-// IEEE half (bits) -> float: exact (v_cvt_f32_f16; subnormal halves become normal floats)
-__device__ __forceinline__ float widen_half(uint32_t h) {
-  const uint16_t b = (uint16_t)h;
-  _Float16 x;
-  __builtin_memcpy(&x, &b, 2);
-  return (float)x;
-}
-
-__device__ __forceinline__ void widen8(const uint4 v, float* f) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    f[2 * t] = widen_half(w[t] & 0xffffu);
-    f[2 * t + 1] = widen_half(w[t] >> 16);
-  }
-}
+// (widen_half / widen8, IEEE half bits -> float, exact: half_widen.h -- one text with K1's half-row LOD route)
 
 // float -> IEEE half (bits), the narrowing rule of include/hgs.h: round to nearest even with subnormal halves kept, a
 // finite value beyond +-65504 becomes +-65504 (narrowing never makes an infinity), NaN stays NaN (0x7e00 under its sign),
@@ -200,6 +186,52 @@ __global__ __launch_bounds__(256) void resid_fetch_half_kernel(const int32_t* __
     dst.means3D[s * 3 + 0] = __uint_as_float(v.x);
     dst.means3D[s * 3 + 1] = __uint_as_float(v.y);
     dst.means3D[s * 3 + 2] = __uint_as_float(v.z);
+    slot_of[id] = (int32_t)s;
+    id_of_slot[s] = (int32_t)id;
+    stamp[s] = frame;
+  }
+}
+
+// Half SLOTS (hgs_resid_fetch_half_slots): the slot arrays hold the rows as they arrive -- SH, rotation, scale and opacity
+// as IEEE half, the mean as float32 -- so a slot costs 6 M + 28 bytes instead of 4 (3 M + 11).  The read is that of
+// resid_fetch_half_kernel (eight lanes per row, one 16-byte chunk each); the BITS are copied, nothing is converted:
+// lanes 0..5 store the first 6 M bytes of the SH block (kVec: 6 M % 16 == 0 and the array 16-byte aligned -- whole
+// chunks; else 2-byte stores, since a slot's row then starts off a 16-byte boundary), lane 6 the rotation (8 bytes),
+// the scale (rows are 6 bytes apart: three 2-byte stores) and the opacity (2 bytes), lane 7 the mean and the bookkeeping.
+// No store is wider than what it writes: the last slot of a [B] half array may end 2 bytes past a 4-byte boundary.
+template <bool kVec>
+__global__ __launch_bounds__(256) void resid_fetch_half_slots_kernel(const int32_t* __restrict__ miss_ids, uint32_t m,
+                                                                     const int32_t* __restrict__ free_list, uint32_t free_top,
+                                                                     int32_t* __restrict__ slot_of, int32_t* __restrict__ id_of_slot,
+                                                                     uint32_t* __restrict__ stamp, uint32_t frame,
+                                                                     const uint4* __restrict__ src, hgs_resid_rows_half dst,
+                                                                     int nsh) {
+  const uint32_t j = blockIdx.x * 32u + (threadIdx.x >> 3);
+  const int sub = threadIdx.x & 7;
+  if (j >= m) return;
+  const size_t id = (size_t)miss_ids[j];
+  const size_t s = (size_t)free_list[free_top - 1u - j];
+  const uint4 v = src[id * (HGS_RESID_HOST_ROW_BYTES_HALF / 16) + sub];
+  if (sub < 6) {
+    uint16_t* row = static_cast<uint16_t*>(dst.shs) + s * nsh;
+    if (kVec) {
+      if (sub * 8 < nsh) reinterpret_cast<uint4*>(row)[sub] = v;
+    } else {
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int t = 0; t < 8; ++t)
+        if (sub * 8 + t < nsh) row[sub * 8 + t] = (uint16_t)(w[t >> 1] >> ((t & 1) * 16));
+    }
+  } else if (sub == 6) {                           // halves 48..55: rotation, scale, opacity
+    static_cast<uint2*>(dst.rotations)[s] = make_uint2(v.x, v.y);
+    uint16_t* sc = static_cast<uint16_t*>(dst.scales) + s * 3;
+    sc[0] = (uint16_t)v.z; sc[1] = (uint16_t)(v.z >> 16); sc[2] = (uint16_t)v.w;
+    static_cast<uint16_t*>(dst.opacities)[s] = (uint16_t)(v.w >> 16);
+  } else {                                         // bytes 112..127: mean (float32), padding
+    float* mean = static_cast<float*>(dst.means3D) + s * 3;
+    mean[0] = __uint_as_float(v.x);
+    mean[1] = __uint_as_float(v.y);
+    mean[2] = __uint_as_float(v.z);
     slot_of[id] = (int32_t)s;
     id_of_slot[s] = (int32_t)id;
     stamp[s] = frame;
@@ -343,11 +375,10 @@ int hgs_resid_evict(uint32_t* stamp, int32_t* id_of_slot, int32_t* slot_of, int3
   return HGS_OK;
 }
 
-// the two fetch calls: the checks, the device-side address of the host rows, one launch
-static int resid_fetch(bool half, const int32_t* miss_ids, uint32_t m, const int32_t* free_list, uint32_t free_top,
-                       int32_t* slot_of, int32_t* id_of_slot, uint32_t* stamp, uint32_t frame, const void* host_rows_packed,
-                       const hgs_resid_rows* slot_rows, int32_t M, hgs_stream_t stream, int device) {
-  if (m == 0) return HGS_OK;
+// what every fetch call checks before its launch (m > 0); *d receives the device-side address of the packed host rows
+static int resid_fetch_checks(const int32_t* miss_ids, uint32_t m, const int32_t* free_list, uint32_t free_top,
+                              const int32_t* slot_of, const int32_t* id_of_slot, const uint32_t* stamp,
+                              const void* host_rows_packed, const void* slot_rows, int32_t M, int device, void** d) {
   if (!miss_ids || !free_list || !slot_of || !id_of_slot || !stamp || !host_rows_packed || !slot_rows) {
     set_error("null argument");
     return HGS_ERR_INVALID;
@@ -355,14 +386,26 @@ static int resid_fetch(bool half, const int32_t* miss_ids, uint32_t m, const int
   if (M < 1 || M > 16) { set_error("M = %d SH coefficients per channel: 1..16", M); return HGS_ERR_INVALID; }
   if (free_top < m) { set_error("%u free slots for %u missing rows", free_top, m); return HGS_ERR_CAPACITY; }
   HGS_HIP(hipSetDevice(device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
   // the packed host rows by their device-side address
-  void* d = nullptr;
-  if (hipHostGetDevicePointer(&d, const_cast<void*>(host_rows_packed), 0) != hipSuccess) {
+  *d = nullptr;
+  if (hipHostGetDevicePointer(d, const_cast<void*>(host_rows_packed), 0) != hipSuccess) {
     (void)hipGetLastError();
     set_error("the packed host rows must come from hgs_host_alloc (pinned, device-mapped)");
     return HGS_ERR_INVALID;
   }
+  return HGS_OK;
+}
+
+// the two fetch calls into float slots: the checks, one launch
+static int resid_fetch(bool half, const int32_t* miss_ids, uint32_t m, const int32_t* free_list, uint32_t free_top,
+                       int32_t* slot_of, int32_t* id_of_slot, uint32_t* stamp, uint32_t frame, const void* host_rows_packed,
+                       const hgs_resid_rows* slot_rows, int32_t M, hgs_stream_t stream, int device) {
+  if (m == 0) return HGS_OK;
+  void* d = nullptr;
+  const int rc = resid_fetch_checks(miss_ids, m, free_list, free_top, slot_of, id_of_slot, stamp, host_rows_packed, slot_rows,
+                                    M, device, &d);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
   if (((uintptr_t)d | (uintptr_t)slot_rows->rotations) & 15u) {
     set_error("packed host rows / slot rotations must be 16-byte aligned");
     return HGS_ERR_INVALID;
@@ -402,6 +445,38 @@ int hgs_resid_fetch_half(const int32_t* miss_ids, uint32_t m, const int32_t* fre
                          const hgs_resid_rows* slot_rows, int32_t M, hgs_stream_t stream, int device) {
   return resid_fetch(true, miss_ids, m, free_list, free_top, slot_of, id_of_slot, stamp, frame, host_rows_packed, slot_rows,
                      M, stream, device);
+}
+
+int hgs_resid_fetch_half_slots(const int32_t* miss_ids, uint32_t m, const int32_t* free_list, uint32_t free_top,
+                               int32_t* slot_of, int32_t* id_of_slot, uint32_t* stamp, uint32_t frame,
+                               const void* host_rows_packed, const hgs_resid_rows_half* slot_rows, int32_t M,
+                               hgs_stream_t stream, int device) {
+  if (m == 0) return HGS_OK;
+  void* d = nullptr;
+  const int rc = resid_fetch_checks(miss_ids, m, free_list, free_top, slot_of, id_of_slot, stamp, host_rows_packed, slot_rows,
+                                    M, device, &d);
+  if (rc) return rc;
+  if (!slot_rows->means3D || !slot_rows->shs || !slot_rows->opacities || !slot_rows->scales || !slot_rows->rotations) {
+    set_error("null argument");
+    return HGS_ERR_INVALID;
+  }
+  // the rotation of a slot is stored with one 8-byte access, the mean as floats, everything else as halves
+  if (((uintptr_t)d & 15u) || ((uintptr_t)slot_rows->rotations & 7u) || ((uintptr_t)slot_rows->means3D & 3u) ||
+      (((uintptr_t)slot_rows->shs | (uintptr_t)slot_rows->scales | (uintptr_t)slot_rows->opacities) & 1u)) {
+    set_error("packed host rows must be 16-byte aligned, half slot rotations 8-byte aligned (means 4, the other arrays 2)");
+    return HGS_ERR_INVALID;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const uint4* src = static_cast<const uint4*>(d);
+  const bool vec = ((M * 3) & 7) == 0 && (((uintptr_t)slot_rows->shs & 15u) == 0);      // 6 M % 16 == 0
+  if (vec)
+    hipLaunchKernelGGL(resid_fetch_half_slots_kernel<true>, dim3((m + 31) / 32), dim3(256), 0, s, miss_ids, m, free_list,
+                       free_top, slot_of, id_of_slot, stamp, frame, src, *slot_rows, M * 3);
+  else
+    hipLaunchKernelGGL(resid_fetch_half_slots_kernel<false>, dim3((m + 31) / 32), dim3(256), 0, s, miss_ids, m, free_list,
+                       free_top, slot_of, id_of_slot, stamp, frame, src, *slot_rows, M * 3);
+  HGS_LAUNCH_CHECK("resid_fetch_half_slots", s, false);
+  return HGS_OK;
 }
 
 int hgs_resid_pack_rows(const hgs_resid_rows* src, int64_t G, int32_t M, int32_t half, void* host_rows_packed,

@@ -12,21 +12,49 @@ import torch
 from hgs import _lib
 
 
-def _require_gpu(t: torch.Tensor, name: str):
+HALF_ROWS_USE = ("float16 tensors are supported in ONE use: the in-op LOD interpolation (non-empty render_indices) with "
+                 "shs, opacities, scales and rotations ALL float16, means3D float32, no precomputed colours / covariances, "
+                 "no raw-parameter path and no input that requires a gradient (hgs_raster_args.lod_half_rows; the half "
+                 "slots of hgs.residency.BudgetedHierarchy)")
+
+
+def _require_gpu(t: torch.Tensor, name: str, dtype=torch.float32):
     """Device / dtype checks; returns the tensor made contiguous (a sliced or expanded input, e.g. an override_color
     broadcast, is copied once -- the upstream extension calls .contiguous() on its inputs in the same way)."""
     if not t.is_cuda:
         raise RuntimeError(f"{name} must be a CUDA/HIP tensor (got {t.device}); this op has no CPU path")
-    if t.dtype != torch.float32:
+    if t.dtype != dtype:
+        if torch.float16 in (t.dtype, dtype):
+            raise RuntimeError(f"{name} is {t.dtype} where {dtype} is expected: {HALF_ROWS_USE}")
         raise RuntimeError(f"{name} must be float32 (got {t.dtype})")
     return t.contiguous()
 
 
-def _opt(t, name, P, inner):
+def _half_rows(means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, sh_rest, activations, lod):
+    """True when the call is the one supported use of float16 tensors (HALF_ROWS_USE); False when no tensor is float16;
+    every other use of a float16 tensor raises."""
+    present = lambda t: t is not None and torch.is_tensor(t) and t.numel() > 0
+    is_half = lambda t: present(t) and t.dtype == torch.float16
+    att = (sh, opacity, scales, rotations)
+    if not any(is_half(t) for t in att + (means3D, colors, cov3D_precomp, sh_rest)):
+        return False
+    if lod is None or not all(is_half(t) for t in att) or means3D.dtype != torch.float32 or present(colors) or \
+            present(cov3D_precomp) or present(sh_rest) or activations:
+        raise RuntimeError(HALF_ROWS_USE)
+    return True
+
+
+def _require_att(t, name, dtype):
+    """_require_gpu for shs / opacities / scales / rotations, whose dtype the call decides (float16: HALF_ROWS_USE).  The
+    float32 call keeps the two-argument form every other input uses."""
+    return _require_gpu(t, name) if dtype is torch.float32 else _require_gpu(t, name, dtype)
+
+
+def _opt(t, name, P, inner, dtype=torch.float32):
     """None for an absent/empty optional input, else the validated (contiguous) tensor."""
     if t is None or t.numel() == 0:
         return None
-    t = _require_gpu(t, name)
+    t = _require_att(t, name, dtype)
     if t.shape[0] != P or t.numel() != P * inner:
         raise RuntimeError(f"{name} has shape {tuple(t.shape)}, expected [{P}, ...] with {inner} values per Gaussian")
     return t
@@ -157,6 +185,8 @@ def _build_args(background, means3D, colors, opacity, scales, rotations, scale_m
                 debug, interpolation_weights, num_node_kids, do_depth, sh_rest=None, activations=0, lod=None):
     """``lod`` = (render_indices, parent_indices, skybox_points): in-kernel LOD interpolation -- the attribute tensors
     hold all hierarchy Gaussians (G rows), the op renders P = len(render_indices) + skybox_points rows."""
+    half = _half_rows(means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, sh_rest, activations, lod)
+    att = torch.float16 if half else torch.float32      # dtype of shs / opacities / scales / rotations: passed as they are
     means3D = _require_gpu(means3D, "means3D")
     if means3D.dim() != 2 or means3D.shape[1] != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
@@ -176,15 +206,15 @@ def _build_args(background, means3D, colors, opacity, scales, rotations, scale_m
     if sh is not None and sh.numel() == 0:
         sh = None
     if sh is not None:
-        sh = _require_gpu(sh, "shs")
+        sh = _require_att(sh, "shs", att)
         if sh.dim() != 3 or sh.shape[0] != rows or sh.shape[2] != 3:
             raise RuntimeError("shs must have dimensions (num_points, num_coeffs, 3)")
     colors = _opt(colors, "colors_precomp", rows, 3)
-    scales = _opt(scales, "scales", rows, 3)
-    rotations = _opt(rotations, "rotations", rows, 4)
+    scales = _opt(scales, "scales", rows, 3, att)
+    rotations = _opt(rotations, "rotations", rows, 4, att)
     cov3D_precomp = _opt(cov3D_precomp, "cov3D_precomp", rows, 6)
     if rows > 0:
-        opacity = _require_gpu(opacity, "opacities")
+        opacity = _require_att(opacity, "opacities", att)
         if opacity.numel() != rows:
             raise RuntimeError(f"opacities must hold {rows} values")
         if (sh is None) == (colors is None):
@@ -223,6 +253,7 @@ def _build_args(background, means3D, colors, opacity, scales, rotations, scale_m
         raise RuntimeError(f"LOD_REMAP must be 'opacity' or 'alpha', not {LOD_REMAP!r}")
     a.lod_per_pixel = int(LOD_REMAP == "alpha" and w is not None)
     a.shs_rest, a.activations = p(sh_rest), int(activations)
+    a.lod_half_rows = int(half)
     if lod is not None:
         a.lod_render_indices, a.lod_parent_indices = p(ri), p(pi)
         a.lod_n, a.lod_rows = int(ri.numel()), rows
@@ -250,6 +281,8 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
                                 cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, image_height,
                                 image_width, sh, degree, campos, debug, interpolation_weights, num_node_kids,
                                 do_depth, sh_rest, activations, lod)
+    if a.lod_half_rows and prepare_backward:
+        raise RuntimeError("an input requires a gradient: " + HALF_ROWS_USE)
     a.prepare_backward = int(bool(prepare_backward))
     dev = means3D.device
     H, W = int(image_height), int(image_width)

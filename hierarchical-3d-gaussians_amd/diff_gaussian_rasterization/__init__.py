@@ -289,7 +289,10 @@ class _RasterizeGaussiansLod(torch.autograd.Function):
     kernels, forward and backward (hgs_raster_args.lod_*) -- what gaussian_renderer/__init__.py:199-234 does with ~25
     torch kernels and three materialised copies of the rows.  The backward's per-Gaussian kernels scatter the
     gradients to node and parent rows themselves (hgs_raster_args.lod_scatter; with 3M % 4 != 0 the row gradients go
-    through memory and hgs_lod_gather_bwd)."""
+    through memory and hgs_lod_gather_bwd).  Forward only, it also takes the half-precision slot arrays of
+    ``hgs.residency.BudgetedHierarchy(..., slots="half")`` as they are: shs, opacities, scales and rotations all float16,
+    means3D float32, nothing requiring a gradient (hgs_raster_args.lod_half_rows: K1 widens the halves in registers and
+    renders the bits of the widened float32 arrays); every other use of a float16 tensor raises (_C.HALF_ROWS_USE)."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, opacities, scales, rotations, raster_settings, render_indices,

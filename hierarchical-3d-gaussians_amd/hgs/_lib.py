@@ -29,7 +29,7 @@ class RasterArgs(C.Structure):
         ("means3D", C.c_void_p), ("shs", C.c_void_p), ("colors_precomp", C.c_void_p),
         ("opacities", C.c_void_p), ("scales", C.c_void_p), ("rotations", C.c_void_p),
         ("cov3D_precomp", C.c_void_p), ("interpolation_weights", C.c_void_p), ("num_node_kids", C.c_void_p),
-        ("shs_rest", C.c_void_p), ("activations", C.c_int32), ("defer_sh_bwd", C.c_int32), ("lod_per_pixel", C.c_int32), ("reserved1", C.c_int32),
+        ("shs_rest", C.c_void_p), ("activations", C.c_int32), ("defer_sh_bwd", C.c_int32), ("lod_per_pixel", C.c_int32), ("lod_half_rows", C.c_int32),
         ("prepare_backward", C.c_int32), ("lod_n", C.c_int32),
         ("lod_render_indices", C.c_void_p), ("lod_parent_indices", C.c_void_p),
         ("lod_rows", C.c_int32), ("lod_scatter", C.c_int32),
@@ -78,6 +78,11 @@ class HierAlignReport(C.Structure):
 
 class ResidRows(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("means3D", "shs", "opacities", "scales", "rotations")]
+
+
+class ResidRowsHalf(C.Structure):
+    """hgs_resid_rows_half: the half SLOT arrays (means3D float32; shs, opacities, scales, rotations IEEE half)."""
+    _fields_ = ResidRows._fields_
 
 
 class ShBwdView(C.Structure):
@@ -237,6 +242,8 @@ SIGNATURES = {
     "hgs_resid_remap": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int]),
     "hgs_resid_fetch_half": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P,
                                        C.POINTER(ResidRows), C.c_int32, _P, C.c_int]),
+    "hgs_resid_fetch_half_slots": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P,
+                                             C.POINTER(ResidRowsHalf), C.c_int32, _P, C.c_int]),
     "hgs_resid_pack_rows": (C.c_int, [C.POINTER(ResidRows), C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int]),
 }
 P2P_MAX_WORLD, P2P_HANDLE_BYTES, P2P_FLAG_BYTES = 8, 64, 256

@@ -42,7 +42,16 @@ hierarchy whose boxes nest; the default ``fit="regulate"`` is the path described
 of include/hgs.h (HGS_RESID_HOST_ROW_BYTES_HALF: SH, rotation, scale and opacity as IEEE half, the mean as float32): half
 the pinned memory and two 64-byte PCIe reads per row instead of four.  The fetch kernel widens the rows into the same
 float32 slot arrays, so everything behind the slots -- and the number of rows a budget buys -- is unchanged; what the
-viewer sees is ``round_rows_to_half`` of the attributes.  ``pack_rows_half`` is the layout's specification in numpy."""
+viewer sees is ``round_rows_to_half`` of the attributes.  ``pack_rows_half`` is the layout's specification in numpy.
+
+``slots="half"`` (same three places; needs ``rows="half"``) keeps the SLOT arrays in half precision too: the fetch kernel
+copies the bits of the host row (hgs_resid_fetch_half_slots) -- SH, rotation, scale and opacity stay IEEE half
+(``bh.shs`` ... are ``torch.float16``), the mean float32 -- and the rasterizer's in-op LOD path widens them in registers
+(hgs_raster_args.lod_half_rows).  A slot then costs ``6 M + 28`` bytes instead of ``4 (3 M + 11)`` -- 124 against 236 at
+M = 16 -- so the same ``budget_mb`` buys 1.90 times the rows, which ``fit="budget"`` and the regulator turn into a finer
+cut.  Nothing is lost against ``rows="half"`` with float slots: widening a half is exact and the interpolation stays in
+float32, so at an equal ROW budget the two render the same image bit for bit.  Forward only (a viewer's path): the
+tensors are handed to ``GaussianRasterizer`` as they are, without gradients."""
 from __future__ import annotations
 
 import ctypes as C
@@ -129,6 +138,14 @@ def _check_rows(rows):
         raise ValueError(f"rows must be 'float' or 'half', not {rows!r}")
 
 
+def _check_slots(slots, rows):
+    if slots not in ("float", "half"):
+        raise ValueError(f"slots must be 'float' or 'half', not {slots!r}")
+    if slots == "half" and rows != "half":
+        raise ValueError("slots='half' needs rows='half': the fetch copies the half host row's bits into the slot, and "
+                         "narrowing float host rows on fetch is not part of it")
+
+
 def _check_arrays(means3D, shs, opacities, scales, rotations, on_gpu):
     """ValueError unless the five arrays are float32, agree on G, have the rasterizer's shapes and live where the
     constructor expects them (``on_gpu``); nothing here touches the device.  -> (G, M)"""
@@ -183,15 +200,18 @@ class Selection:
 
 class BudgetedHierarchy:
     def __init__(self, means3D, shs, opacities, scales, rotations, device, budget_mb: Optional[float] = None,
-                 budget_rows: Optional[int] = None, index_capacity: Optional[int] = None, rows: str = "float"):
+                 budget_rows: Optional[int] = None, index_capacity: Optional[int] = None, rows: str = "float",
+                 slots: str = "float"):
         """The five attribute arrays as CPU tensors ([G,3], [G,M,3], [G] or [G,1], [G,3], [G,4], float32, already in the
         form the rasterizer takes: activated).  They are COPIED into pinned host memory.  ``budget_mb``: megabytes of
         GPU memory for the attribute rows (the reference's ``--budget``); or ``budget_rows`` directly.  ``rows``:
-        ``"float"`` -- 256-byte host rows -- or ``"half"`` -- 128-byte host rows (module docstring); the slots, and so the
-        rows a budget buys, are float32 either way."""
+        ``"float"`` -- 256-byte host rows -- or ``"half"`` -- 128-byte host rows (module docstring).  ``slots``:
+        ``"float"`` -- float32 slot arrays, 4 (3 M + 11) bytes a row -- or, with ``rows="half"``, ``"half"`` -- the slots
+        keep the halves, 6 M + 28 bytes a row: the same budget buys 1.90 times the rows at M = 16."""
         _check_rows(rows)
+        _check_slots(slots, rows)
         G, M = _check_arrays(means3D, shs, opacities, scales, rotations, on_gpu=False)
-        self._setup(G, M, device, budget_mb, budget_rows, index_capacity, rows)
+        self._setup(G, M, device, budget_mb, budget_rows, index_capacity, rows, slots)
         if rows == "half":
             step = 1 << 20              # narrowed block by block: no second copy of the whole hierarchy
             for a in range(0, G, step):
@@ -207,13 +227,14 @@ class BudgetedHierarchy:
         r[:, 58] = f(opacities, (G,))
         r[:, 59:] = 0.0
 
-    def _setup(self, G, M, device, budget_mb, budget_rows, index_capacity, rows):
+    def _setup(self, G, M, device, budget_mb, budget_rows, index_capacity, rows, slots="float"):
         """Everything but the contents of the host rows: the pinned rows, the slot arrays, the bookkeeping."""
         self.dev = torch.device(device)
         self.lib = _lib.lib()
         self.G, self.M = G, M
-        self.rows_format = rows
-        self.row_bytes = 4 * (3 * M + 11)                   # bytes of a row in the SLOT arrays: what a budget is counted in
+        self.rows_format, self.slots_format = rows, slots
+        # bytes of a row in the SLOT arrays -- what a budget is counted in: five float32 arrays, or halves beside a float32 mean
+        self.row_bytes = 6 * M + 28 if slots == "half" else 4 * (3 * M + 11)
         self.host_row_bytes = HOST_ROW_BYTES[rows]          # bytes of a row in pinned host memory, and over PCIe
         if budget_rows is None:
             if budget_mb is None:
@@ -225,15 +246,18 @@ class BudgetedHierarchy:
         if rows == "half":
             self._rows, self._rows_ptr = _host_array((G, self.host_row_bytes), np.uint8)
             self._fetch, self._fetch_name = self.lib.hgs_resid_fetch_half, "hgs_resid_fetch_half"
+            if slots == "half":
+                self._fetch, self._fetch_name = self.lib.hgs_resid_fetch_half_slots, "hgs_resid_fetch_half_slots"
         else:
             self._rows, self._rows_ptr = _host_array((G, _lib.RESID_HOST_ROW_FLOATS))
             self._fetch, self._fetch_name = self.lib.hgs_resid_fetch, "hgs_resid_fetch"
         f32 = dict(dtype=torch.float32, device=self.dev)
+        att = dict(dtype=torch.float16 if slots == "half" else torch.float32, device=self.dev)
         self.means3D = torch.zeros(B, 3, **f32)
-        self.shs = torch.zeros(B, M, 3, **f32)
-        self.opacities = torch.zeros(B, 1, **f32)
-        self.scales = torch.ones(B, 3, **f32)
-        self.rotations = torch.zeros(B, 4, **f32)
+        self.shs = torch.zeros(B, M, 3, **att)
+        self.opacities = torch.zeros(B, 1, **att)
+        self.scales = torch.ones(B, 3, **att)
+        self.rotations = torch.zeros(B, 4, **att)
         self.rotations[:, 0] = 1.0
         i32 = dict(dtype=torch.int32, device=self.dev)
         self.slot_of = torch.full((G,), -1, **i32)
@@ -259,24 +283,25 @@ class BudgetedHierarchy:
         self._bounds = None             # (key of the node list, float32 [N,4] culling balls): built on first frustum use
         self.profile_fetch = False      # True: (rows, start event, end event) of every fetch launch -> self.fetch_events
         self.fetch_events = []
-        self._slot_rows = _lib.ResidRows(*[C.c_void_p(t.data_ptr()) for t in
-                                           (self.means3D, self.shs, self.opacities, self.scales, self.rotations)])
+        self._slot_rows = (_lib.ResidRowsHalf if slots == "half" else _lib.ResidRows)(
+            *[C.c_void_p(t.data_ptr()) for t in (self.means3D, self.shs, self.opacities, self.scales, self.rotations)])
 
     @classmethod
     def from_device_arrays(cls, means3D, shs, opacities, scales, rotations, *, rows: str = "float",
-                           budget_mb: Optional[float] = None, budget_rows: Optional[int] = None,
+                           slots: str = "float", budget_mb: Optional[float] = None, budget_rows: Optional[int] = None,
                            index_capacity: Optional[int] = None):
         """The constructor for attributes that are already on the GPU (a hierarchy built or merged there): float32 GPU
         tensors of the constructor's shapes, on one device.  The host rows are written by a kernel through the mapped
         pointer (hgs_resid_pack_rows) in either format -- the same bytes the constructor writes -- and no float copy of
-        the attributes is made on the host."""
+        the attributes is made on the host.  ``slots``: as in the constructor."""
         _check_rows(rows)
+        _check_slots(slots, rows)
         G, M = _check_arrays(means3D, shs, opacities, scales, rotations, on_gpu=True)
         dev = means3D.device
         if any(t.device != dev for t in (shs, opacities, scales, rotations)):
             raise ValueError("from_device_arrays: the five tensors must live on one device")
         self = cls.__new__(cls)
-        self._setup(G, M, dev, budget_mb, budget_rows, index_capacity, rows)
+        self._setup(G, M, dev, budget_mb, budget_rows, index_capacity, rows, slots)
         src = [t.detach().contiguous() for t in (means3D, shs, opacities, scales, rotations)]
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
@@ -288,18 +313,19 @@ class BudgetedHierarchy:
 
     @classmethod
     def from_hier_file(cls, path: str, device, budget_mb: Optional[float] = None, budget_rows: Optional[int] = None,
-                       rows: str = "float"):
+                       rows: str = "float", slots: str = "float"):
         """A ``.hier`` file (gaussian_hierarchy._C.load_hierarchy, scene/gaussian_model.py:329) straight into the
         budgeted form, with the activations the reference applies to a loaded hierarchy: opacity = |alpha|
         (scene/gaussian_model.py:393), scales = exp(log-scales), rotations normalised (scene/gaussian_model.py:108-116).
         Returns (BudgetedHierarchy, nodes, boxes) with nodes / boxes on ``device`` (they stay resident: 60 B per node).
         ``rows="half"``: 128-byte host rows, narrowed from the ACTIVATED values (a file written with ``half=True`` stores
-        log-scales as halves; its activated scales are narrowed once more here)."""
+        log-scales as halves; its activated scales are narrowed once more here).  ``slots``: as in the constructor."""
         from gaussian_hierarchy._C import load_hierarchy
         _check_rows(rows)
+        _check_slots(slots, rows)
         xyz, shs, alpha, log_scales, rots, nodes, boxes = load_hierarchy(path)
         bh = cls(xyz, shs, alpha.abs(), torch.exp(log_scales), torch.nn.functional.normalize(rots), device,
-                 budget_mb=budget_mb, budget_rows=budget_rows, rows=rows)
+                 budget_mb=budget_mb, budget_rows=budget_rows, rows=rows, slots=slots)
         return bh, nodes.to(device), boxes.to(device)
 
     def __del__(self):

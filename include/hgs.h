@@ -103,7 +103,17 @@ typedef struct hgs_raster_args {
    * reference's kernel implements is not recoverable from its checkout: gaussian_renderer/__init__.py:258-265 only
    * passes the tensors on).  Must hold the same value in the forward and the backward call. */
   int32_t lod_per_pixel;
-  int32_t reserved1;
+  /* Half-precision attribute rows for the in-kernel LOD interpolation (the word that was `reserved1`; 0 = today's
+   * behaviour, ABI unchanged).  1, valid only together with lod_render_indices and FORWARD ONLY: shs, opacities, scales
+   * and rotations point at arrays of IEEE half ([lod_rows, M, 3], [lod_rows], [lod_rows, 3], [lod_rows, 4] -- the slot
+   * arrays hgs_resid_fetch_half_slots fills; shs and rotations 16-byte aligned, as for float32 arrays), means3D
+   * stays float32, and the skybox tail rows are read the same way.  The per-Gaussian kernel widens every half exactly
+   * as it loads it and then takes the float32 path unchanged -- the weight-1 rule, the separately rounded lerp, the
+   * hemisphere flip, the opacity remap -- so the call renders bit for bit what it renders on float32 arrays holding the
+   * widened values.  Refused with HGS_ERR_INVALID before any HIP call: by the three forward calls without
+   * lod_render_indices, with prepare_backward, with shs_rest / activations / colors_precomp / cov3D_precomp, or with a
+   * value other than 0 or 1; by hgs_raster_bwd with any value other than 0. */
+  int32_t lod_half_rows;
   /* The caller will run hgs_raster_bwd on the workspaces of this forward (must hold the SAME value in the forward and
    * in the backward call).  The forward's per-Gaussian kernel then also stores, next to the colour, the 3x3 Jacobian
    * d(rgb)/d(view direction) (36 bytes per Gaussian, in geom_ws): it has the SH coefficients in registers anyway, and
@@ -848,7 +858,8 @@ int hgs_resid_remap(const int32_t* render_indices, const int32_t* parent_indices
                     const int32_t* slot_of, int32_t* ro, int32_t* po, hgs_stream_t stream, int device);
 
 /* Half-precision host rows (opt-in): 128 bytes per Gaussian = two 64-byte PCIe reads and half the pinned memory.  The
- * slot arrays on the device stay float32; only the host side and the bus carry halves.  Eight 16-byte chunks:
+ * slot arrays on the device stay float32 (hgs_resid_fetch_half) or hold the halves as they arrive
+ * (hgs_resid_fetch_half_slots); the host side and the bus carry halves.  Eight 16-byte chunks:
  *   bytes   0 ..  95   48 halves: SH coefficients [0, 3 M) in the slot array's order, the rest padding
  *   bytes  96 .. 103   rotation, 4 halves
  *   bytes 104 .. 109   scale, 3 halves (activated, as the float rows hold it)
@@ -861,6 +872,14 @@ int hgs_resid_remap(const int32_t* render_indices, const int32_t* parent_indices
  * pixels); NaN stays NaN (the quiet NaN 0x7e00 under its sign) and an infinity stays an infinity.  Widening is exact.
  *   hgs_resid_fetch_half  hgs_resid_fetch on rows of this layout: same arguments, refusals and slot assignment; the
  *                         kernel reads the half rows over PCIe and widens them into the float slot arrays.
+ *   hgs_resid_fetch_half_slots  the same call for half SLOTS (hgs_resid_rows_half): arguments, refusals and slot
+ *                         assignment are those of hgs_resid_fetch_half, but the slot arrays hold SH, rotation, scale and
+ *                         opacity as IEEE half and the mean as float32 -- the BITS of the host row are copied, nothing
+ *                         is converted.  A slot costs 6 M + 28 bytes instead of 4 (3 M + 11): 124 against 236 at M = 16,
+ *                         so a budget buys 1.90 times the rows.  No store touches a byte outside the assigned slot of
+ *                         any array (16-byte stores into the SH rows only when 6 M % 16 == 0 and the array is 16-byte
+ *                         aligned).  Alignment asked of the slot arrays: rotations 8 bytes, means3D 4, the others 2.
+ *                         The rasterizer reads such slots with hgs_raster_args.lod_half_rows = 1.
  *   hgs_resid_pack_rows   device attribute arrays (`src`, G rows, activated) -> packed host rows, written by the kernel
  *                         through the mapped pointer: `half` = 1 this layout, 0 the float layout of
  *                         HGS_RESID_HOST_ROW_FLOATS; padding is written as zeros in both.  host_rows_packed: G rows
@@ -870,6 +889,17 @@ int hgs_resid_remap(const int32_t* render_indices, const int32_t* parent_indices
 int hgs_resid_fetch_half(const int32_t* miss_ids, uint32_t m, const int32_t* free_list, uint32_t free_top, int32_t* slot_of,
                          int32_t* id_of_slot, uint32_t* stamp, uint32_t frame, const void* host_rows_packed,
                          const hgs_resid_rows* slot_rows, int32_t M, hgs_stream_t stream, int device);
+typedef struct hgs_resid_rows_half {   /* the order of hgs_resid_rows */
+  void* means3D;    /* float32 [rows, 3]    */
+  void* shs;        /* half    [rows, M, 3] */
+  void* opacities;  /* half    [rows]       */
+  void* scales;     /* half    [rows, 3]    */
+  void* rotations;  /* half    [rows, 4]    */
+} hgs_resid_rows_half;
+int hgs_resid_fetch_half_slots(const int32_t* miss_ids, uint32_t m, const int32_t* free_list, uint32_t free_top,
+                               int32_t* slot_of, int32_t* id_of_slot, uint32_t* stamp, uint32_t frame,
+                               const void* host_rows_packed, const hgs_resid_rows_half* slot_rows, int32_t M,
+                               hgs_stream_t stream, int device);
 int hgs_resid_pack_rows(const hgs_resid_rows* src, int64_t G, int32_t M, int32_t half, void* host_rows_packed,
                         hgs_stream_t stream, int device);
 

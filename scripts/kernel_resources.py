@@ -129,6 +129,7 @@ def occupancy(vgprs, agprs, lds_static, wg_threads, lds_dynamic=0):
 
 # dynamic LDS of the kernels that take it at launch (bytes per workgroup at the metric configuration: M = 16, 256 lanes)
 DYNAMIC_LDS = {"preprocess_fwd_kernel": 256 * (16 * 3 + 4) * 4, "preprocess_fwd_h48_kernel": 256 * 192,
+               "preprocess_fwd_lod_half_kernel": 256 * (16 * 3 + 4) * 4,
                "sh_bwd_kernel": 256 * (16 * 3 + 4) * 4,
                "preprocess_bwd_sh_kernel": 256 * (16 * 3 + 4) * 4,       # the output stage; the run stages (40 KB) lie inside it
                # 1080p: two arrays over a band's 1 020 tiles + 8 bytes per instance of a 4 096-instance chunk (staged scatter)
