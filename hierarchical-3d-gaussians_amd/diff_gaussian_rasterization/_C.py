@@ -411,6 +411,10 @@ def rasterize_gaussians_backward(call, color, invdepth, dL_dcolor, dL_dinvdepth,
         if t is not None:
             if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != int(torch.Size(shape).numel()):
                 raise RuntimeError(f"gradient buffer for {name} must be a contiguous float32 GPU tensor of shape {tuple(shape)}")
+            # the SH blocks and the quaternions are moved with 16-byte accesses, gradients as well as inputs (validate() in
+            # csrc/abi.cpp refuses such inputs; a slice of a flat bucket is where a gradient buffer gets off the boundary)
+            if name in ("shs", "shs_rest", "rotations") and t.data_ptr() % 16:
+                raise RuntimeError(f"gradient buffer for {name} must be 16-byte aligned")
             return t.view(*shape)
         return _rows_empty(shape[0], shape[1:], dev)
 

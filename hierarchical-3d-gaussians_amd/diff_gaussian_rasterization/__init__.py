@@ -53,6 +53,8 @@ class RasterContext:
                        writes those gradients straight into the buffers and hands autograd ``None`` for them, so
                        ``.grad`` is never touched (no double counting under ``loss.backward()``) and no autograd node
                        consumes them.  Meant for LEAF inputs: nothing upstream of a buffered input receives a gradient.
+                       The shs, shs_rest and rotations buffers must start on a 16-byte boundary, like those inputs (the
+                       kernels move them in 16-byte pieces); the views of a ``GradBucket`` do.
     grad_accumulate    add to the buffers (later views of one optimizer step) instead of overwriting; ``means2D`` and
                        ``colors_precomp`` gradients are per-view quantities and always overwritten.
     defer_sh_backward  leave the SH part of every backward (dL_dshs, 81 % of the gradient bytes, and the

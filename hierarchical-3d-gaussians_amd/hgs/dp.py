@@ -45,14 +45,16 @@ class GradBucket:
 
     def __init__(self, shapes: Dict[str, Sequence[int]], device, direct: Optional[bool] = None):
         """``direct``: exchange through DirectAllReduce (peer pointers) instead of torch.distributed's all-reduce;
-        default from the environment (HGS_DP_ALLREDUCE=direct).  The bucket then lives in exportable memory and every
-        tensor starts on a multiple of 4 floats (the direct kernels move 16 bytes per lane)."""
+        default from the environment (HGS_DP_ALLREDUCE=direct).  The bucket then lives in exportable memory.  On either
+        route every tensor starts on a multiple of 4 floats: the direct kernels move 16 bytes per lane, and so does the
+        rasterizer's backward when it writes SH and rotation gradients straight into the views (it refuses a buffer off
+        a 16-byte boundary) -- a row count that is no multiple of 4 leaves up to 3 unused floats behind a tensor."""
         self.names: List[str] = [n for n in GRAD_ORDER if n in shapes]
         sizes = [int(torch.Size(shapes[n]).numel()) for n in self.names]
         if direct is None:
             direct = os.environ.get("HGS_DP_ALLREDUCE", "") == "direct"
         direct = bool(direct) and dist.is_initialized() and dist.get_world_size() > 1
-        pad = (lambda x: (x + 3) // 4 * 4) if direct else (lambda x: x)
+        pad = lambda x: (x + 3) // 4 * 4
         total = sum(pad(sz) for sz in sizes)
         self.direct = None
         if direct:

@@ -731,7 +731,10 @@ def activate_raw(scaling_raw, rotation_raw, opacity_raw, opacity_activation="sig
         return t + (t.detach().float().double() - t.detach())
     s = rounded(torch.exp(scaling_raw.double()))
     q = rotation_raw.double()
-    n = torch.sqrt(((q[:, 0] ** 2 + q[:, 1] ** 2) + q[:, 2] ** 2) + q[:, 3] ** 2).clamp_min(1e-12)
+    ss = ((q[:, 0] ** 2 + q[:, 1] ** 2) + q[:, 2] ** 2) + q[:, 3] ** 2
+    # (an all-zero quaternion: the same values as sqrt(ss).clamp_min(1e-12), but autograd must not see d sqrt / d ss at 0 --
+    # behind the clamp the norm is the constant 1e-12, 0 x inf would make that row's gradient NaN)
+    n = torch.where(ss > 0, torch.sqrt(torch.where(ss > 0, ss, torch.ones_like(ss))), torch.zeros_like(ss)).clamp_min(1e-12)
     r = rounded(q / n[:, None])
     x = opacity_raw.double()
     if opacity_activation == "sigmoid":

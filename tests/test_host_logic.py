@@ -168,6 +168,24 @@ def test_training_loop_extras_live_on_a_context_object():
     assert dgr.GaussianRasterizer(rs).context is None and dgr.GaussianRasterizer(rs, context=b).context is b
 
 
+def test_grad_bucket_views_start_on_16_byte_boundaries():
+    """The rasterizer's backward moves SH and rotation gradients in 16-byte pieces and refuses a buffer off the boundary:
+    a bucket over a row count that is no multiple of 4 pads between its tensors instead of handing out such a view."""
+    from hgs import dp
+    for P in (1, 257, 400):
+        shapes = dict(means3D=(P, 3), shs=(P, 16, 3), opacities=(P, 1), scales=(P, 3), rotations=(P, 4))
+        b = dp.GradBucket(shapes, "cpu")
+        assert b.flat.data_ptr() % 16 == 0
+        end = 0
+        for n in b.names:
+            v = b.views[n]
+            assert tuple(v.shape) == shapes[n] and v.data_ptr() % 16 == 0, (P, n)
+            assert v.storage_offset() >= end, (P, n)                   # no overlap
+            end = v.storage_offset() + v.numel()
+        assert end <= b.flat.numel() <= 59 * P + 3 * len(b.names)
+        assert b.span(b.names).numel() == end                          # the padding travels with a span
+
+
 def test_bench_byte_model_is_consistent():
     """bench.py's algorithmic byte model: every stage positive, the batched-SH variants move strictly fewer bytes
     per view than the per-view model, and the headline figure is reproduced (1.25 GB-scale per frame at 1 M / 1080p)."""

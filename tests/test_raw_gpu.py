@@ -7,68 +7,9 @@ import torch
 
 import parity as pa
 from hgs import synth
-from oracle import raster_oracle as ro
+from raw_cases import _compare, _oracle_raw, _raw_from_scene, _run_hip_raw
 
 pytestmark = pytest.mark.gpu
-
-
-def _raw_from_scene(scene, seed, logit=True):
-    g = torch.Generator().manual_seed(seed)
-    op = scene.opacities.clamp(1e-4, 1 - 1e-4)
-    return dict(
-        xyz=scene.means3D.clone(),
-        f_dc=scene.shs[:, :1].contiguous().clone(),
-        f_rest=scene.shs[:, 1:].contiguous().clone(),
-        opacity=(torch.log(op / (1 - op)) if logit else op * torch.where(torch.rand(op.shape, generator=g) < 0.5, -1.0, 1.0)),
-        scaling=torch.log(scene.scales),
-        rotation=scene.rotations * (0.5 + torch.rand(scene.P, 1, generator=g) * 2.0),   # un-normalised
-    )
-
-
-def _oracle_raw(raw, cam, bg, sh_degree, act):
-    """The oracle of the raw entrance: float64 leaves, the activations of ``ro.activate_raw`` in front of the blend."""
-    leaves = {k: v.clone().double().requires_grad_(True) for k, v in raw.items()}
-    leaves["means2D"] = torch.zeros(raw["xyz"].shape[0], 3, dtype=torch.float64, requires_grad=True)
-
-    def call(lv, **extra):
-        s, r, o = ro.activate_raw(lv["scaling"], lv["rotation"], lv["opacity"], act)
-        shs = torch.cat([lv["f_dc"], lv["f_rest"]], 1)
-        return ro.rasterize(lv["xyz"], lv["means2D"], shs, None, o, s, r, None, image_height=cam.image_height,
-                            image_width=cam.image_width, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, bg=bg,
-                            scale_modifier=1.0, viewmatrix=cam.world_view_transform,
-                            projmatrix=cam.full_proj_transform, sh_degree=sh_degree, campos=cam.camera_center, **extra)
-    return pa.OracleRun(leaves, call)
-
-
-def _run_hip_raw(raw, cam, bg, gc, gd, sh_degree, act, device, debug=True):
-    import diff_gaussian_rasterization as dgr
-    leaves = {k: v.clone().to(device).requires_grad_(True) for k, v in raw.items()}
-    m2 = torch.zeros(raw["xyz"].shape[0], 3, device=device, requires_grad=True)
-    rs = dgr.GaussianRasterizationSettings(**pa.settings_kwargs(cam, bg, sh_degree, do_depth=True, debug=debug,
-                                                                device=device))
-    color, radii, invd = dgr.GaussianRasterizer(rs).forward_raw(
-        leaves["xyz"], m2, leaves["f_dc"], leaves["f_rest"], leaves["opacity"], leaves["scaling"],
-        leaves["rotation"], opacity_activation=act)
-    call = color.grad_fn.call
-    views = {k: v.cpu().clone() for k, v in dgr._C.raster_views(call).items()}
-    ((color * gc.to(device)).sum() + (invd * gd.to(device)).sum()).backward()
-    torch.cuda.synchronize()
-    grads = {k: v.grad.detach().cpu() for k, v in leaves.items()}
-    grads["means2D"] = m2.grad.detach().cpu()
-    return dict(color=color.detach().cpu(), radii=radii.cpu(), invdepth=invd.detach().cpu(), views=views, L=call.L,
-                grads=grads)
-
-
-def _compare(hip, res):
-    idx = pa.check_indices(hip, res["oracle"])
-    assert all(v == 0 for v in idx.values()), idx
-    st = res["stats"]
-    assert st["fragile_frac"] <= pa.FRAGILE_FRAC
-    assert st["fragile_unmatched"] == 0 and st["fragile_unenumerated"] == 0, st
-    assert st["n_contrib_mismatch"] == 0, st["n_contrib_mismatch"]
-    for k, v in st.items():
-        if isinstance(v, dict):
-            assert v["maxrel"] <= pa.REL_TOL and v["l2"] <= pa.REL_TOL, (k, v)
 
 
 @pytest.mark.parametrize("P,size,deg,act", [(1000, 128, 3, "sigmoid"), (1000, 128, 3, "abs"), (777, 96, 1, "sigmoid"),
