@@ -666,6 +666,63 @@ int hgs_hier_align(const int32_t* nodes, int64_t N, float* log_scales, float* ro
   return launch_hier_align(nodes, N, log_scales, rots, tmp, report, static_cast<hipStream_t>(stream));
 }
 
+size_t hgs_hier_trim_tmp_bytes(int64_t N) {
+  if (N < 1 || N > kHierMergeMaxN) return 0;
+  return hier_trim_tmp_bytes(N);
+}
+
+// Sizes, pointers and alignment of one side of a trim call.
+static int check_trim_view(const hgs_hier_view* v, const char* side) {
+  if (v->N < 1 || v->N > kHierMergeMaxN) { set_error("bad sizes: %s N=%lld not in [1, 2^31 - 1]", side, (long long)v->N); return HGS_ERR_INVALID; }
+  if (v->G < v->N) { set_error("bad sizes: %s G=%lld < N=%lld", side, (long long)v->G, (long long)v->N); return HGS_ERR_INVALID; }
+  if (v->M < 1 || v->M > 64) { set_error("bad sizes: %s M=%d not in [1, 64]", side, v->M); return HGS_ERR_INVALID; }
+  if (null_view(v)) { set_error("null argument"); return HGS_ERR_INVALID; }
+  if (((uintptr_t)v->rots | (uintptr_t)v->boxes) & 15u) { set_error("%s rots / boxes must be 16-byte aligned", side); return HGS_ERR_INVALID; }
+  if (((uintptr_t)v->xyz | (uintptr_t)v->shs | (uintptr_t)v->alpha | (uintptr_t)v->log_scales | (uintptr_t)v->nodes) & 3u) {
+    set_error("%s xyz / shs / alpha / log_scales / nodes must be 4-byte aligned", side);
+    return HGS_ERR_INVALID;
+  }
+  return HGS_OK;
+}
+
+int hgs_hier_trim_plan(const hgs_hier_view* in, const hgs_hier_trim_args* args, void* tmp, hgs_hier_trim_report* report,
+                       hgs_stream_t stream, int device) {
+  if (!in || !args || !report) { set_error("null argument"); return HGS_ERR_INVALID; }
+  int rc = check_trim_view(in, "input");
+  if (rc) return rc;
+  bool nan = std::isnan(args->min_extent);
+  for (int a = 0; a < 3 && args->use_roi; ++a) nan = nan || std::isnan(args->roi_lo[a]) || std::isnan(args->roi_hi[a]);
+  if (nan) { set_error("min_extent or a region bound is NaN"); return HGS_ERR_INVALID; }
+  if (!tmp) { set_error("null argument"); return HGS_ERR_INVALID; }
+  if ((uintptr_t)tmp & (kAlign - 1)) { set_error("tmp must be %d-byte aligned", (int)kAlign); return HGS_ERR_INVALID; }
+  for (int k = 0; k < 4; ++k) report->first_bad[k] = -1;
+  report->kept = report->stubs = 0;
+  HGS_HIP(hipSetDevice(device));
+  return launch_hier_trim_plan(*in, *args, tmp, report, static_cast<hipStream_t>(stream), device);
+}
+
+int hgs_hier_trim_apply(const hgs_hier_view* in, const hgs_hier_view* out, const void* tmp, int32_t* old_of_new,
+                        int32_t* new_of_old, hgs_stream_t stream, int device) {
+  if (!in || !out) { set_error("null argument"); return HGS_ERR_INVALID; }
+  int rc = check_trim_view(in, "input");
+  if (!rc) rc = check_trim_view(out, "output");
+  if (rc) return rc;
+  if (in->M != out->M) { set_error("bad sizes: input M=%d != output M=%d", in->M, out->M); return HGS_ERR_INVALID; }
+  if (!tmp || !old_of_new || !new_of_old) { set_error("null argument"); return HGS_ERR_INVALID; }
+  if ((uintptr_t)tmp & (kAlign - 1)) { set_error("tmp must be %d-byte aligned", (int)kAlign); return HGS_ERR_INVALID; }
+  if (((uintptr_t)old_of_new | (uintptr_t)new_of_old) & 3u) { set_error("old_of_new / new_of_old must be 4-byte aligned"); return HGS_ERR_INVALID; }
+  int64_t planned_N = 0, kept = 0;
+  if (!hier_trim_planned(device, tmp, &planned_N, &kept)) {
+    set_error("no successful hgs_hier_trim_plan on this device and tmp");
+    return HGS_ERR_INVALID;
+  }
+  if (in->N != planned_N) { set_error("bad sizes: input N=%lld, the plan was made for N=%lld", (long long)in->N, (long long)planned_N); return HGS_ERR_INVALID; }
+  if (out->N != kept) { set_error("bad sizes: output N=%lld != the plan's kept count %lld", (long long)out->N, (long long)kept); return HGS_ERR_INVALID; }
+  const bool shs16 = (3 * in->M) % 4 == 0 && (((uintptr_t)in->shs | (uintptr_t)out->shs) & 15u) == 0;
+  HGS_HIP(hipSetDevice(device));
+  return launch_hier_trim_apply(*in, *out, tmp, old_of_new, new_of_old, shs16, static_cast<hipStream_t>(stream));
+}
+
 size_t hgs_ssim_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W) {
   if (!ssim_sizes_ok(N, C, H, W)) return 0;
   return ssim_tmp_bytes(N, C, H, W);

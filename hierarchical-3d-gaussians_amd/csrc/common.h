@@ -315,6 +315,15 @@ int launch_hier_merge_root(const hgs_hier_view& merged, int32_t k, hipStream_t s
 size_t hier_align_tmp_bytes(int64_t N);
 int launch_hier_align(const int32_t* nodes, int64_t N, float* log_scales, float* rots, void* tmp,
                       hgs_hier_align_report* report, hipStream_t s);
+// trimming (hier_trim.hip): sizes, pointers and alignment checked by the caller (1 <= N <= 2^31 - 1).  hier_trim_planned:
+// what the last successful plan on (device, tmp) found (host memory: the apply call's size checks need no HIP call);
+// shs16: copy shs in 16-byte pieces (12 M a multiple of 16, both bases aligned)
+size_t hier_trim_tmp_bytes(int64_t N);
+bool hier_trim_planned(int device, const void* tmp, int64_t* N, int64_t* kept);
+int launch_hier_trim_plan(const hgs_hier_view& in, const hgs_hier_trim_args& args, void* tmp,
+                          hgs_hier_trim_report* report, hipStream_t s, int device);
+int launch_hier_trim_apply(const hgs_hier_view& in, const hgs_hier_view& out, const void* tmp, int32_t* old_of_new,
+                           int32_t* new_of_old, bool shs16, hipStream_t s);
 // fused SSIM loss (ssim.hip): ssim_sizes_ok sets the error message; the launches expect sizes it accepted
 bool ssim_sizes_ok(int32_t N, int32_t C, int32_t H, int32_t W);
 size_t ssim_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W);

@@ -1,0 +1,282 @@
+// Trimming a hierarchy: the rule of hgs.hierarchy.trim_hierarchy (the spec) on the device, in two calls.
+//
+//   rule       test(p) = extent(p) >= min_extent, and with a region: box(p) meets the closed box [lo, hi] (float32
+//              comparisons only).  Node 0 is kept; node n > 0 is kept iff test(parent(n)): siblings stay or go together.
+//              A kept node with children whose own test fails becomes a STUB: it takes a leaf's record.  Rows and boxes of
+//              the kept nodes are copied in ascending old order, node records renumbered.
+//   plan       ht_plan_kernel: one thread per node reads its record, its own box and its parent's (the grandparent's only
+//              for the closure check of a kept node), evaluates test, the keep flag, the three layout checks of the merger
+//              (restated here: hier_merge.hip stays as it is) and the closure check (first offending node per check),
+//              and writes the workgroup's keep sum and stub sum; ht_scan_kernel: the chained scan of common.h over the
+//              keep sums, the stub sums added up beside it (one atomic per scan chunk: one per stub wave on a single
+//              word cost 4 ms at 4.2 M stubs); ONE host wait reads back the kept count, the stub count and the checks.
+//              Nothing has been written to any output at that point.
+//   apply      asynchronous.  ht_maps_kernel: new_of_old and old_of_new from the flags and the scanned sums;
+//              ht_gather_kernel: one workgroup per kHtRows OUTPUT rows stages their source rows in LDS, then copies tensor
+//              by tensor, one thread per 16-byte piece (shs where 12 M is a multiple of 16 and both bases are aligned,
+//              rots, boxes) or 4-byte piece (xyz, alpha, log_scales, the rewritten node records, shs otherwise): stores
+//              are contiguous over the workgroup's rows, reads contiguous within a row, and across rows wherever the kept
+//              set is a run of the old order (under an extent floor it is nearly a prefix of the BFS order).
+//
+// Rows at index >= N of the input (a skybox tail) are not read; rows at index >= N' of the output are not written.
+#include "lod_cut.h"   // the workgroup sums and the launcher of the chained scan (the cut rules in it are not used here)
+
+#include <mutex>
+#include <vector>
+
+namespace hgs {
+namespace {
+
+constexpr int kHtThreads = 256;
+constexpr int kHtRows = 128;            // output rows per workgroup of the gather
+constexpr uint32_t kNone = 0xffffffffu;
+constexpr uint32_t kKeep = 1u, kTest = 2u;   // bits of a node's flag byte
+
+// Device half of the report (the kept and stub counts are the two words behind the scanned workgroup sums).
+struct HtResult {
+  uint32_t first_bad[4];   // unsigned minima, kNone = none
+};
+
+__device__ __forceinline__ bool ht_test(const float* __restrict__ boxes, int64_t n, const hgs_hier_trim_args& a) {
+  const float4 mn = reinterpret_cast<const float4*>(boxes)[n * 2 + 0];
+  bool ok = mn.w >= a.min_extent;                 // (a NaN extent never passes)
+  if (a.use_roi) {
+    const float4 mx = reinterpret_cast<const float4*>(boxes)[n * 2 + 1];
+    ok = ok && mn.x <= a.roi_hi[0] && mx.x >= a.roi_lo[0] && mn.y <= a.roi_hi[1] && mx.y >= a.roi_lo[1] &&
+         mn.z <= a.roi_hi[2] && mx.z >= a.roi_lo[2];
+  }
+  return ok;
+}
+
+// One thread per node: the checks of the row, its flags, the workgroup's keep sum and stub sum.
+__global__ __launch_bounds__(kHtThreads) void ht_plan_kernel(const int32_t* __restrict__ nodes,
+                                                             const float* __restrict__ boxes, int32_t N,
+                                                             hgs_hier_trim_args a, uint8_t* __restrict__ flags,
+                                                             uint32_t* __restrict__ block_sums,
+                                                             uint32_t* __restrict__ block_stubs,
+                                                             unsigned long long* __restrict__ chain,
+                                                             HtResult* __restrict__ res) {
+  clear_scan_chain(chain, block_sums);
+  const int64_t i = (int64_t)blockIdx.x * kHtThreads + threadIdx.x;
+  uint32_t keep = 0, stub = 0;
+  if (i < N) {
+    const int32_t* nd = nodes + i * kNodeInts;
+    const int32_t parent = nd[1], start = nd[2], leafs = nd[3], merged = nd[4], sc = nd[5];
+    const int64_t cc = nd[6];
+    // ---- the merger's three checks
+    const bool bad_row = start != i || (int64_t)leafs + merged != 1;
+    const bool parent_in_range = i > 0 && parent >= 0 && parent < N;
+    bool bad_parent;
+    if (i == 0) {
+      bad_parent = parent != -1;
+    } else if (!parent_in_range) {
+      bad_parent = true;
+    } else {
+      const int32_t* pn = nodes + (int64_t)parent * kNodeInts;
+      const int64_t ps = pn[5], pc = pn[6];
+      bad_parent = !(i >= ps && i < ps + pc);
+    }
+    const bool bad_children = cc < 0 || (cc > 0 && (sc < 1 || (int64_t)sc + cc > N));
+    if (bad_row) atomicMin(&res->first_bad[0], (uint32_t)i);
+    if (bad_children) atomicMin(&res->first_bad[1], (uint32_t)i);
+    if (bad_parent) atomicMin(&res->first_bad[2], (uint32_t)i);
+    // ---- the rule
+    const bool test_self = ht_test(boxes, i, a);
+    bool k = i == 0;
+    if (parent_in_range) {
+      k = ht_test(boxes, parent, a);
+      if (k && parent != 0) {          // closure: a kept node's parent is kept (a bad grandparent index is check [2]'s)
+        const int32_t pp = nodes[(int64_t)parent * kNodeInts + 1];
+        if (pp >= 0 && pp < N && !ht_test(boxes, pp, a)) atomicMin(&res->first_bad[3], (uint32_t)i);
+      }
+    }
+    keep = k ? 1u : 0u;
+    stub = (k && cc > 0 && !test_self) ? 1u : 0u;
+    flags[i] = (uint8_t)((k ? kKeep : 0u) | (test_self ? kTest : 0u));
+  }
+  const uint32_t cnt[2] = {keep, stub};
+  uint32_t* const out[2] = {block_sums, block_stubs};
+  block_totals<2>(cnt, out);
+}
+
+// sums[0 .. n) scanned in place, sums[n] = the kept count, sums[n + 1] = the stub count
+__global__ __launch_bounds__(1024) void ht_scan_kernel(uint32_t* __restrict__ sums,
+                                                       const uint32_t* __restrict__ block_stubs, int n,
+                                                       unsigned long long* __restrict__ chain, int c_off, int chunks) {
+  scan_sums_and_unculled_total(sums, block_stubs, n, chain, c_off, chunks);
+}
+
+// One thread per old node: its new index from the scanned workgroup sums, both maps.
+__global__ __launch_bounds__(kHtThreads) void ht_maps_kernel(const uint8_t* __restrict__ flags,
+                                                             const uint32_t* __restrict__ block_sums, int32_t N,
+                                                             int32_t kept, int32_t* __restrict__ old_of_new,
+                                                             int32_t* __restrict__ new_of_old) {
+  const int64_t i = (int64_t)blockIdx.x * kHtThreads + threadIdx.x;
+  const bool keep = i < N && (flags[i] & kKeep) != 0u;
+  const uint32_t pos = block_sums[blockIdx.x] + block_exclusive_offset(keep ? 1u : 0u);
+  if (i < N) {
+    new_of_old[i] = keep ? (int32_t)pos : -1;
+    if (keep && pos < (uint32_t)kept) old_of_new[pos] = (int32_t)i;
+  }
+}
+
+struct HtIn {
+  const float* xyz; const float* shs; const float* alpha; const float* log_scales; const float* rots;
+  const int32_t* nodes; const float* boxes;
+};
+struct HtOut {
+  float* xyz; float* shs; float* alpha; float* log_scales; float* rots; int32_t* nodes; float* boxes;
+};
+
+// rows [r0, r0 + rows) of a tensor of `ppr` pieces of type T per row <- the rows src[0 .. rows) of `in`
+template <typename T>
+__device__ __forceinline__ void ht_copy_rows(T* __restrict__ out, const T* __restrict__ in, const int32_t* src,
+                                             int64_t r0, uint32_t rows, uint32_t ppr) {
+  T* o = out + r0 * ppr;
+  const uint32_t L = rows * ppr;
+#pragma unroll 4
+  for (uint32_t u = threadIdx.x; u < L; u += kHtThreads) {
+    const uint32_t jl = u / ppr, k = u - jl * ppr;
+    o[u] = in[(int64_t)src[jl] * ppr + k];
+  }
+}
+
+// One workgroup per kHtRows output rows.  S: 16-byte pieces of an shs row (0: shs goes in W 4-byte pieces).
+__global__ __launch_bounds__(kHtThreads) void ht_gather_kernel(HtIn in, HtOut out, const int32_t* __restrict__ old_of_new,
+                                                               const int32_t* __restrict__ new_of_old,
+                                                               const uint8_t* __restrict__ flags, int32_t kept,
+                                                               uint32_t S, uint32_t W) {
+  __shared__ int32_t src[kHtRows];
+  const int64_t r0 = (int64_t)blockIdx.x * kHtRows;
+  const uint32_t rows = (uint32_t)min((int64_t)kHtRows, (int64_t)kept - r0);
+  if (threadIdx.x < rows) src[threadIdx.x] = old_of_new[r0 + threadIdx.x];
+  __syncthreads();
+  if (S) ht_copy_rows(reinterpret_cast<float4*>(out.shs), reinterpret_cast<const float4*>(in.shs), src, r0, rows, S);
+  else ht_copy_rows(out.shs, in.shs, src, r0, rows, W);
+  ht_copy_rows(reinterpret_cast<float4*>(out.boxes), reinterpret_cast<const float4*>(in.boxes), src, r0, rows, 2u);
+  ht_copy_rows(reinterpret_cast<float4*>(out.rots), reinterpret_cast<const float4*>(in.rots), src, r0, rows, 1u);
+  ht_copy_rows(out.xyz, in.xyz, src, r0, rows, 3u);
+  ht_copy_rows(out.log_scales, in.log_scales, src, r0, rows, 3u);
+  ht_copy_rows(out.alpha, in.alpha, src, r0, rows, 1u);
+  // the node records, one thread per int: depth kept, parent / start / start_children renumbered, a stub takes a
+  // leaf's record, a leaf keeps its own
+  int32_t* o = out.nodes + r0 * kNodeInts;
+  const uint32_t L = rows * kNodeInts;
+  for (uint32_t u = threadIdx.x; u < L; u += kHtThreads) {
+    const uint32_t jl = u / kNodeInts, k = u - jl * kNodeInts;
+    const int64_t i = src[jl];
+    const int32_t* nd = in.nodes + i * kNodeInts;
+    const int32_t cc = nd[6];
+    const bool stub = cc > 0 && (flags[i] & kTest) == 0u;
+    int32_t v;
+    switch (k) {
+      case 0: v = nd[0]; break;
+      case 1: v = i == 0 ? -1 : new_of_old[nd[1]]; break;
+      case 2: v = (int32_t)(r0 + jl); break;
+      case 3: v = stub ? 1 : nd[3]; break;
+      case 4: v = stub ? 0 : nd[4]; break;
+      case 5: v = stub ? 0 : (cc > 0 ? new_of_old[nd[5]] : nd[5]); break;
+      default: v = stub ? 0 : cc; break;
+    }
+    o[u] = v;
+  }
+}
+
+struct HtTmp : SumsTmp {
+  HtResult* res;
+  uint8_t* flags;   // [N]
+};
+
+HtTmp carve_ht_tmp(Carver& c, int64_t N) {
+  HtTmp t;
+  t.res = c.take<HtResult>(1);
+  t.flags = c.take<uint8_t>((size_t)N);
+  static_cast<SumsTmp&>(t) = carve_sums(c, (size_t)N, true);   // block_all: the workgroups' stub sums
+  return t;
+}
+
+// What the last successful plan on (device, tmp) found: the apply call checks its sizes against it on the host.
+struct HtPlan { int device; const void* tmp; int64_t N; int64_t kept; };
+constexpr size_t kHtMaxPlans = 64;
+std::mutex g_ht_mutex;
+std::vector<HtPlan> g_ht_plans;   // oldest first
+
+void forget_plan(int device, const void* tmp) {
+  std::lock_guard<std::mutex> lock(g_ht_mutex);
+  for (size_t k = 0; k < g_ht_plans.size(); ++k)
+    if (g_ht_plans[k].device == device && g_ht_plans[k].tmp == tmp) { g_ht_plans.erase(g_ht_plans.begin() + k); break; }
+}
+
+}  // namespace
+
+size_t hier_trim_tmp_bytes(int64_t N) {
+  Carver c(nullptr);
+  carve_ht_tmp(c, N);
+  return c.bytes(0);   // tmp is required to be kAlign-aligned: no slack
+}
+
+bool hier_trim_planned(int device, const void* tmp, int64_t* N, int64_t* kept) {
+  std::lock_guard<std::mutex> lock(g_ht_mutex);
+  for (const HtPlan& p : g_ht_plans)
+    if (p.device == device && p.tmp == tmp) { *N = p.N; *kept = p.kept; return true; }
+  return false;
+}
+
+int launch_hier_trim_plan(const hgs_hier_view& in, const hgs_hier_trim_args& args, void* tmp,
+                          hgs_hier_trim_report* report, hipStream_t s, int device) {
+  forget_plan(device, tmp);
+  const int64_t N = in.N;
+  Carver c(tmp);
+  const HtTmp t = carve_ht_tmp(c, N);
+  HGS_HIP(hipMemsetAsync(t.res, 0xff, sizeof(HtResult), s));
+  const int nblk = (int)((N + kHtThreads - 1) / kHtThreads);
+  hipLaunchKernelGGL(ht_plan_kernel, dim3((unsigned)nblk), dim3(kHtThreads), 0, s, in.nodes, in.boxes, (int32_t)N, args,
+                     t.flags, t.block_sums, t.block_all, t.chain, t.res);
+  HGS_LAUNCH_CHECK("ht_plan", s, false);
+  const int rc = launch_scan_chunks(ht_scan_kernel, "ht_scan", nblk, s, t.block_sums, t.block_all, nblk, t.chain);
+  if (rc) return rc;
+  // ---- the one host wait
+  HtResult host;
+  uint32_t totals[2];      // kept, stubs
+  HGS_HIP(hipMemcpyAsync(&host, t.res, sizeof(host), hipMemcpyDeviceToHost, s));
+  HGS_HIP(hipMemcpyAsync(totals, t.block_sums + nblk, sizeof(totals), hipMemcpyDeviceToHost, s));
+  HGS_HIP(wait_stream(s));
+  for (int k = 0; k < 4; ++k) report->first_bad[k] = host.first_bad[k] == kNone ? -1 : (int32_t)host.first_bad[k];
+  report->kept = (int64_t)totals[0];
+  report->stubs = (int64_t)totals[1];
+  static const char* const what[4] = {
+      "start != node index or count_leafs + count_merged != 1", "children range outside [1, N)",
+      "parent outside [0, N) or not claiming the node (node 0: parent != -1)",
+      "a kept node under a dropped parent (the boxes do not nest, or the extents grow downwards)"};
+  for (int k = 0; k < 4; ++k) {
+    if (report->first_bad[k] >= 0) {
+      set_error("not a hierarchy that can be trimmed: %s (first offending node %d); nothing was written", what[k],
+                report->first_bad[k]);
+      return HGS_ERR_INVALID;
+    }
+  }
+  std::lock_guard<std::mutex> lock(g_ht_mutex);
+  if (g_ht_plans.size() >= kHtMaxPlans) g_ht_plans.erase(g_ht_plans.begin());
+  g_ht_plans.push_back(HtPlan{device, tmp, N, (int64_t)totals[0]});
+  return HGS_OK;
+}
+
+int launch_hier_trim_apply(const hgs_hier_view& in, const hgs_hier_view& out, const void* tmp, int32_t* old_of_new,
+                           int32_t* new_of_old, bool shs16, hipStream_t s) {
+  const int64_t N = in.N, kept = out.N;
+  Carver c(const_cast<void*>(tmp));
+  const HtTmp t = carve_ht_tmp(c, N);
+  const unsigned nblk = (unsigned)((N + kHtThreads - 1) / kHtThreads);
+  hipLaunchKernelGGL(ht_maps_kernel, dim3(nblk), dim3(kHtThreads), 0, s, t.flags, t.block_sums, (int32_t)N, (int32_t)kept,
+                     old_of_new, new_of_old);
+  HGS_LAUNCH_CHECK("ht_maps", s, false);
+  const HtIn i{in.xyz, in.shs, in.alpha, in.log_scales, in.rots, in.nodes, in.boxes};
+  const HtOut o{out.xyz, out.shs, out.alpha, out.log_scales, out.rots, out.nodes, out.boxes};
+  const uint32_t W = 3u * (uint32_t)in.M, S = shs16 ? W / 4u : 0u;
+  hipLaunchKernelGGL(ht_gather_kernel, dim3((unsigned)((kept + kHtRows - 1) / kHtRows)), dim3(kHtThreads), 0, s, i, o,
+                     old_of_new, new_of_old, t.flags, (int32_t)kept, S, W);
+  HGS_LAUNCH_CHECK("ht_gather", s, false);
+  return HGS_OK;
+}
+
+}  // namespace hgs

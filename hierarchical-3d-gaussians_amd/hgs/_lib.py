@@ -76,6 +76,14 @@ class HierAlignReport(C.Structure):
     _fields_ = [("first_bad", C.c_int32 * 4), ("roots", C.c_int32), ("levels", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class HierTrimArgs(C.Structure):
+    _fields_ = [("min_extent", C.c_float), ("use_roi", C.c_int32), ("roi_lo", C.c_float * 3), ("roi_hi", C.c_float * 3)]
+
+
+class HierTrimReport(C.Structure):
+    _fields_ = [("first_bad", C.c_int32 * 4), ("kept", C.c_int64), ("stubs", C.c_int64)]
+
+
 class ResidRows(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("means3D", "shs", "opacities", "scales", "rotations")]
 
@@ -167,6 +175,10 @@ SIGNATURES = {
     "hgs_hier_merge_root": (C.c_int, [C.POINTER(HierView), C.c_int32, _P, C.c_int]),
     "hgs_hier_align_tmp_bytes": (C.c_size_t, [C.c_int64]),
     "hgs_hier_align": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.POINTER(HierAlignReport), _P, C.c_int]),
+    "hgs_hier_trim_tmp_bytes": (C.c_size_t, [C.c_int64]),
+    "hgs_hier_trim_plan": (C.c_int, [C.POINTER(HierView), C.POINTER(HierTrimArgs), _P, C.POINTER(HierTrimReport), _P,
+                                     C.c_int]),
+    "hgs_hier_trim_apply": (C.c_int, [C.POINTER(HierView), C.POINTER(HierView), _P, _P, _P, _P, C.c_int]),
     "hgs_ssim_tmp_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "hgs_ssim_fwd": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int]),
     "hgs_ssim_bwd": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,

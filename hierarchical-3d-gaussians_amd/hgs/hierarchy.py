@@ -8,7 +8,9 @@ Morton-sorted leaves, interior nodes holding a moment-matched merge of their chi
 under one root by ``merge_hierarchies`` (the torch spec) and ``merge_hierarchies_gpu`` (the same rule on the device, one
 chunk at a time, behind ``python -m hgs.merge_hierarchies``).  ``align_hierarchy`` (the numpy spec) and ``align_hierarchy_gpu``
 (the same rule on the device, behind ``--align`` and ``python -m hgs.align_hierarchy``) re-express every node's rotation
-and scales in the frame closest to its parent's, opt-in.
+and scales in the frame closest to its parent's, opt-in.  ``trim_hierarchy`` (the numpy spec) and ``trim_hierarchy_gpu``
+(the same rule on the device, behind ``python -m hgs.trim_hierarchy``) make a smaller copy: a detail floor, a region, a
+node budget.
 Layout = DESIGN.md '.hier layout':
 
   one Gaussian per node, Gaussian index == node index (``start`` = node id)
@@ -717,3 +719,244 @@ def align_hierarchy_gpu(h: Hierarchy, stats=None) -> Hierarchy:
         ev[1].synchronize()
         stats["align_ms"] = ev[0].elapsed_time(ev[1])
     return h
+
+
+# ---- trimming: a detail floor, a region, a node budget ------------------------------------------------------------------
+# hgs_hier_trim_report.first_bad, in the order they are reported: the merger's three layout checks, then closure
+TRIM_CHECKS = MERGE_CHECKS + ("a kept node under a dropped parent (the boxes do not nest, or the extents grow downwards)",)
+TRIM_MAX_NODES = (1 << 31) - 1
+_FLT_MAX = 3.4028234663852886e38
+
+
+class HierarchyTrimError(ValueError):
+    """A hierarchy ``trim_hierarchy`` / ``trim_hierarchy_gpu`` rejected (nothing was written): ``check`` (what failed,
+    one of TRIM_CHECKS) and ``node`` (the first offending node)."""
+
+    def __init__(self, check, node, message):
+        super().__init__(message)
+        self.check, self.node = check, node
+
+
+@dataclass
+class TrimResult:
+    hierarchy: Hierarchy        # the N' kept nodes, in ascending old order
+    old_of_new: torch.Tensor    # int32 [N']
+    new_of_old: torch.Tensor    # int32 [N], -1 at dropped nodes
+    min_extent: float           # the floor that was used (the larger of the given one and the budget's)
+    stubs: int                  # kept nodes with children that became leaves
+    stub_ids: torch.Tensor      # int32 [stubs]: their NEW indices, ascending
+
+    def exact_for(self, viewpoint, tau) -> bool:
+        """Is the cut of ``hierarchy`` from ``viewpoint`` at granularity ``tau`` the original's cut mapped through
+        ``new_of_old``, bit for bit?  True iff every stub s has node_size(s, viewpoint) < tau (float32, the operation
+        order of csrc/lod_cut.h node_size): the original's cut then stops at s as well."""
+        if self.stub_ids.numel() == 0:
+            return True
+        b = self.hierarchy.boxes.reshape(-1, 2, 4)[self.stub_ids.long()]
+        v = torch.as_tensor(viewpoint, dtype=torch.float32).reshape(3).to(b.device)
+        mn, mx, ext = b[:, 0, :3], b[:, 1, :3], b[:, 0, 3]
+        d = torch.maximum(torch.maximum(mn - v, v - mx), torch.zeros((), dtype=torch.float32, device=b.device))
+        d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        size = torch.where(d2 > 0, ext / d2.sqrt(), torch.full_like(d2, _FLT_MAX))
+        return bool((size < torch.tensor(float(np.float32(tau)), dtype=torch.float32, device=b.device)).all())
+
+
+def _trim_params(min_extent, roi, max_nodes):
+    """-> (float32 floor, None or (lo float32 [3], hi float32 [3]), None or int K); NaN and K < 1 refused."""
+    e = np.float32(min_extent)
+    if np.isnan(e):
+        raise ValueError("min_extent is NaN")
+    if roi is not None:
+        lo, hi = (np.asarray(torch.as_tensor(r).detach().cpu().numpy() if torch.is_tensor(r) else r,
+                             dtype=np.float32).reshape(-1) for r in roi)
+        if lo.shape != (3,) or hi.shape != (3,) or np.isnan(lo).any() or np.isnan(hi).any():
+            raise ValueError("roi is a pair (lo[3], hi[3]) of numbers")
+        roi = (lo, hi)
+    if max_nodes is not None:
+        max_nodes = int(max_nodes)
+        if max_nodes < 1:
+            raise ValueError(f"max_nodes = {max_nodes}; at least 1 (the root) expected")
+    return e, roi, max_nodes
+
+
+def _trim_test(boxes, e, roi):
+    """test(p) at every node (numpy bool [N]): float32 comparisons only."""
+    t = boxes[:, 0, 3] >= e
+    if roi is not None:
+        lo, hi = roi
+        t = t & (boxes[:, 0, :3] <= hi[None, :]).all(1) & (boxes[:, 1, :3] >= lo[None, :]).all(1)
+    return t
+
+
+def trim_layout_checks(nodes):
+    """The merger's three layout checks on int32 nodes [N,7] (numpy) -> [first offending node or -1] x 3."""
+    nd = np.asarray(nodes).astype(np.int64)
+    N = nd.shape[0]
+    i = np.arange(N)
+    parent, start, leafs, merged, sc, cc = nd[:, 1], nd[:, 2], nd[:, 3], nd[:, 4], nd[:, 5], nd[:, 6]
+    bad_row = (start != i) | (leafs + merged != 1)
+    bad_children = (cc < 0) | ((cc > 0) & ((sc < 1) | (sc + cc > N)))
+    in_range = (parent >= 0) & (parent < N)
+    ps, pc = sc[np.where(in_range, parent, 0)], cc[np.where(in_range, parent, 0)]
+    bad_parent = ~in_range | ~((i >= ps) & (i < ps + pc))
+    bad_parent[0] = parent[0] != -1
+    first = lambda m: int(np.nonzero(m)[0][0]) if m.any() else -1
+    return [first(bad_row), first(bad_children), first(bad_parent)]
+
+
+def trim_budget_extent(nodes, boxes, max_nodes, roi=None):
+    """The floor a node budget resolves to (numpy float32): the smallest extent value e among the nodes with children
+    (with a region: those meeting it) such that 1 + sum of count_children over {p: test_e(p)} <= max_nodes; nodes of
+    equal extent go in together or not at all; +inf if even the root's children do not fit."""
+    boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 2, 4)
+    cc = np.asarray(nodes)[:, 6].astype(np.int64)
+    cand = (cc > 0) & _trim_test(boxes, np.float32(-np.inf), roi)      # (a NaN extent never passes a test)
+    e, c = boxes[cand, 0, 3], cc[cand]
+    if e.size == 0:
+        return np.float32(np.inf)
+    order = np.argsort(-e, kind="stable")
+    e, total = e[order], 1 + np.cumsum(c[order])
+    last = np.ones(e.size, dtype=bool)                               # the last node of every run of equal extents
+    last[:-1] = e[:-1] != e[1:]
+    ok = np.nonzero(last & (total <= int(max_nodes)))[0]
+    return np.float32(e[ok[-1]]) if ok.size else np.float32(np.inf)
+
+
+def trim_hierarchy(h: Hierarchy, min_extent=0.0, roi=None, max_nodes=None) -> TrimResult:
+    """Trim a hierarchy to a detail floor, a region and/or a node budget (the numpy spec; ``trim_hierarchy_gpu`` is the
+    same rule on the device).  test(p) = extent(p) >= min_extent and, with ``roi`` = (lo[3], hi[3]), box(p) meets the
+    closed box: boxes[p,0,a] <= hi[a] and boxes[p,1,a] >= lo[a] on every axis, all in float32.  Node 0 is kept; node
+    n > 0 is kept iff test(parent(n)): siblings stay or go together.  ``max_nodes`` = K resolves to a floor first
+    (``trim_budget_extent``); the larger of it and ``min_extent`` is used.  The kept nodes are written in ascending old
+    order: rows and boxes bit for bit; node records with parent / start / start_children renumbered, depth kept; a kept
+    node with children whose own test fails becomes a stub with a leaf's record (1, 0, 0, 0).  Rows at index >= N (a
+    skybox tail) are not the function's business: the result has G = N' rows.
+    Refused with ``HierarchyTrimError`` (check, first offending node): the merger's three layout checks, and closure --
+    a kept node n > 0 whose parent p != 0 is dropped.  -> TrimResult (host tensors)."""
+    e, roi, K = _trim_params(min_extent, roi, max_nodes)
+    nodes = h.nodes.detach().cpu().numpy().astype(np.int32)
+    N = nodes.shape[0]
+    G = int(h.xyz.shape[0])
+    if N < 1 or G < N or N > TRIM_MAX_NODES:
+        raise ValueError(f"G = {G} rows, N = {N} nodes; 1 <= N <= G, N <= 2^31 - 1 expected")
+    boxes = h.boxes.detach().cpu().numpy().astype(np.float32).reshape(-1, 2, 4)
+    assert boxes.shape[0] == N
+    for check, node in zip(TRIM_CHECKS, trim_layout_checks(nodes)):
+        if node >= 0:
+            raise HierarchyTrimError(check, node, f"not a hierarchy that can be trimmed: {check} (first offending node "
+                                                  f"{node}); nothing was written")
+    if K is not None:
+        e = max(e, trim_budget_extent(nodes, boxes, K, roi))
+    test = _trim_test(boxes, e, roi)
+    parent = nodes[:, 1].astype(np.int64)
+    keep = np.ones(N, dtype=bool)
+    keep[1:] = test[parent[1:]]
+    grand = parent[np.maximum(parent, 0)]
+    open_ = keep & (parent > 0) & ~test[np.maximum(grand, 0)]
+    if open_.any():
+        node = int(np.nonzero(open_)[0][0])
+        raise HierarchyTrimError(TRIM_CHECKS[3], node, f"not a hierarchy that can be trimmed: {TRIM_CHECKS[3]} (first "
+                                                       f"offending node {node}); nothing was written")
+    old = np.nonzero(keep)[0]
+    new_of_old = np.full(N, -1, dtype=np.int32)
+    new_of_old[old] = np.arange(old.size, dtype=np.int32)
+    cc = nodes[:, 6]
+    stub = keep & (cc > 0) & ~test
+    out = nodes[old].copy()
+    out[:, 1] = np.where(old == 0, -1, new_of_old[np.maximum(parent[old], 0)])
+    out[:, 2] = np.arange(old.size, dtype=np.int32)
+    inner = (cc[old] > 0) & test[old]
+    out[inner, 5] = new_of_old[nodes[old[inner], 5]]
+    out[stub[old], 3:7] = np.array([1, 0, 0, 0], dtype=np.int32)
+    idx = torch.from_numpy(old)
+    rows = lambda t: t.detach().cpu()[:N].index_select(0, idx).clone()
+    th = Hierarchy(xyz=rows(h.xyz), shs=rows(h.shs), alpha=rows(h.alpha), log_scales=rows(h.log_scales),
+                   rots=rows(h.rots), nodes=torch.from_numpy(out), boxes=rows(h.boxes.reshape(-1, 2, 4)))
+    return TrimResult(th, torch.from_numpy(old.astype(np.int32)), torch.from_numpy(new_of_old), float(e),
+                      int(stub.sum()), torch.from_numpy(np.nonzero(stub[old])[0].astype(np.int32)))
+
+
+def _trim_budget_extent_torch(nodes, boxes, K, roi):
+    """``trim_budget_extent`` in torch on the tensors' device (a sort and a cumulative sum) -> numpy float32."""
+    cc = nodes[:, 6].long()
+    ext = boxes[:, 0, 3]
+    cand = (cc > 0) & (ext >= float("-inf"))
+    if roi is not None:
+        lo, hi = (torch.from_numpy(r).to(boxes.device) for r in roi)
+        cand &= (boxes[:, 0, :3] <= hi).all(1) & (boxes[:, 1, :3] >= lo).all(1)
+    e, c = ext[cand], cc[cand]
+    if e.numel() == 0:
+        return np.float32(np.inf)
+    e, order = torch.sort(e, descending=True)
+    total = 1 + torch.cumsum(c[order], 0)
+    last = torch.ones_like(e, dtype=torch.bool)
+    last[:-1] = e[:-1] != e[1:]
+    ok = (last & (total <= K)).nonzero().flatten()
+    return np.float32(e[ok[-1]].item()) if ok.numel() else np.float32(np.inf)
+
+
+def trim_hierarchy_gpu(h: Hierarchy, min_extent=0.0, roi=None, max_nodes=None, stats=None) -> TrimResult:
+    """``trim_hierarchy`` on the GPU (csrc/hier_trim.hip: hgs_hier_trim_plan, then N' rows are allocated, then
+    hgs_hier_trim_apply).  ``h``: contiguous device tensors (float32 rows of G >= N, int32 nodes [N,7], boxes [N,2,4]);
+    it is not modified, and rows behind the N nodes are not read.  Every output tensor, both maps, N' and the stub
+    count equal the spec's bit for bit.  A node budget is resolved with torch on the device first.  A hierarchy that
+    fails a check raises ``HierarchyTrimError`` naming the check and the first offending node; nothing has been
+    allocated or written then.  ``stats`` (a dict, optional) receives ``trim_ms`` (device events around plan, the
+    allocation and apply) and its two parts ``plan_ms`` (plan, its host wait and the allocation) and ``apply_ms``.
+    No CPU fallback: raises without libhgs.so or a GPU."""
+    import ctypes as C
+    from . import _lib
+    lib = _lib.lib()
+    if not torch.cuda.is_available():
+        raise RuntimeError("trim_hierarchy_gpu needs a GPU (there is no CPU fallback; trim_hierarchy is the numpy spec)")
+    e, roi, K = _trim_params(min_extent, roi, max_nodes)
+    G, N, M = _tensor_sizes(h)
+    if N < 1 or G < N or N > TRIM_MAX_NODES:
+        raise ValueError(f"G = {G} rows, N = {N} nodes; 1 <= N <= G, N <= 2^31 - 1 expected")
+    dev = h.nodes.device
+    for name in ("xyz", "shs", "alpha", "log_scales", "rots", "nodes", "boxes"):
+        t = getattr(h, name)
+        want = torch.int32 if name == "nodes" else torch.float32
+        if not (t.is_cuda and t.device == dev and t.dtype == want and t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {want} tensor on {dev}")
+    boxes = h.boxes.reshape(-1, 2, 4)
+    if K is not None:
+        e = max(e, _trim_budget_extent_torch(h.nodes, boxes, K, roi))
+    args = _lib.HierTrimArgs(float(e), 0 if roi is None else 1)
+    if roi is not None:
+        args.roi_lo[:], args.roi_hi[:] = [float(x) for x in roi[0]], [float(x) for x in roi[1]]
+    p = lambda t: t.data_ptr()
+    view = lambda g, n, x: _lib.HierView(g, n, M, 0, p(x.xyz), p(x.shs), p(x.alpha), p(x.log_scales), p(x.rots),
+                                         p(x.nodes), p(x.boxes))
+    tmp = torch.empty(lib.hgs_hier_trim_tmp_bytes(N), dtype=torch.uint8, device=dev)
+    rep = _lib.HierTrimReport()
+    rep.first_bad[:] = [-1] * 4              # (a call that fails its size checks does not fill the report)
+    vin = view(G, N, h)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        rc = lib.hgs_hier_trim_plan(C.byref(vin), C.byref(args), p(tmp), C.byref(rep), stream, dev.index or 0)
+        if rc != 0:
+            msg = lib.hgs_last_error()
+            msg = msg.decode() if msg else "?"
+            for check, node in zip(TRIM_CHECKS, rep.first_bad):
+                if node >= 0:
+                    raise HierarchyTrimError(check, int(node), f"hgs_hier_trim_plan: {msg}")
+            raise _lib.HgsError(f"hgs_hier_trim_plan failed (code {rc}): {msg}", rc)
+        n = int(rep.kept)
+        em = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
+        out = Hierarchy(xyz=em(n, 3), shs=em(n, *h.shs.shape[1:]), alpha=em(n, *h.alpha.shape[1:]), log_scales=em(n, 3),
+                        rots=em(n, 4), nodes=em(n, 7, dtype=torch.int32), boxes=em(n, 2, 4))
+        old_of_new, new_of_old = em(n, dtype=torch.int32), em(N, dtype=torch.int32)
+        mid = torch.cuda.Event(enable_timing=True)
+        mid.record()
+        _lib.check(lib.hgs_hier_trim_apply(C.byref(vin), C.byref(view(n, n, out)), p(tmp), p(old_of_new), p(new_of_old),
+                                           stream, dev.index or 0), "hgs_hier_trim_apply")
+        ev[1].record()
+    if stats is not None:
+        ev[1].synchronize()
+        stats["trim_ms"] = ev[0].elapsed_time(ev[1])
+        stats["plan_ms"], stats["apply_ms"] = ev[0].elapsed_time(mid), mid.elapsed_time(ev[1])
+    stub_ids = ((h.nodes[:, 6][old_of_new.long()] > 0) & (out.nodes[:, 6] == 0)).nonzero().flatten().to(torch.int32)
+    return TrimResult(out, old_of_new, new_of_old, float(e), int(rep.stubs), stub_ids)

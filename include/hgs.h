@@ -597,6 +597,52 @@ int hgs_hier_align(const int32_t* nodes, int64_t N, float* log_scales, float* ro
                    hgs_hier_align_report* report, hgs_stream_t stream, int device);
 
 /* ---------------------------------------------------------------------------
+ * Trimming a hierarchy on the device: the rule of hgs.hierarchy.trim_hierarchy (DESIGN.md section 4 and section 7
+ * f-17).  Input: a hierarchy in this project's layout (one row per node, start == node index, count_leafs +
+ * count_merged == 1, contiguous children, every node claimed by its parent), G >= N; rows at index >= N are not read.
+ * test(p) = boxes[p,0,3] >= min_extent and, with use_roi != 0, box(p) meets the closed box [roi_lo, roi_hi]: on every
+ * axis a, boxes[p,0,a] <= roi_hi[a] and boxes[p,1,a] >= roi_lo[a] (float32 comparisons only: nothing rounds).  Node 0
+ * is kept; node n > 0 is kept iff test(parent(n)), so siblings stay or go together.  The N' kept nodes are written in
+ * ascending old order: rows (xyz, shs, alpha, log_scales, rots) and boxes copied bit for bit; node records rewritten:
+ * depth kept, parent = new_of_old[parent] (-1 at node 0), start = the new index; a node with children whose own test
+ * holds keeps its counts and gets start_children = new_of_old[start_children]; a node with children whose own test
+ * fails becomes a STUB with a leaf's record (count_leafs 1, count_merged 0, start_children 0, count_children 0); a node
+ * without children keeps its record.  old_of_new int32 [N'], new_of_old int32 [N] (-1 at dropped nodes).
+ * hgs_hier_trim_tmp_bytes: host only (no GPU needed); 0 for an N outside [1, 2^31 - 1].
+ * hgs_hier_trim_plan: one pass over the nodes and a scan; ONE host wait, which reads `report` back.  Four checks, each
+ * with its first offending node: the three of hgs_hier_merge_report, and [3] closure -- a kept node n > 0 whose parent
+ * p != 0 is dropped (test(parent(p)) fails: the boxes do not nest, or the extents grow downwards).  A failed check
+ * returns HGS_ERR_INVALID with the check and the node in the message and in `report`; no output exists yet, so none is
+ * touched.  tmp: hgs_hier_trim_tmp_bytes(N) of device memory, 256-byte aligned; it carries the plan to the apply call.
+ * hgs_hier_trim_apply: asynchronous on `stream` (the stream of the plan call, or one ordered behind it).  in: the view
+ * and tmp of a plan call that returned HGS_OK; out: N = report.kept, G >= N (rows behind N' are not written), the same
+ * M, memory that does not overlap the input's.
+ * Both check sizes, pointers and alignment before any HIP call: 1 <= N <= 2^31 - 1, N <= G, M in [1, 64]; every array
+ * 4-byte aligned, rots and boxes 16-byte aligned (shs is copied in 16-byte pieces where 12 M is a multiple of 16 and
+ * both shs bases are 16-byte aligned, in 4-byte pieces otherwise); a min_extent or region bound that is NaN is refused;
+ * apply refuses a (device, tmp) pair without a successful plan, an in->N other than the plan's and an out->N other than
+ * its kept count. */
+typedef struct hgs_hier_trim_args {
+  float min_extent;   /* the detail floor (0: none; +inf: the root alone) */
+  int32_t use_roi;    /* != 0: also test the node's box against [roi_lo, roi_hi] */
+  float roi_lo[3];
+  float roi_hi[3];
+} hgs_hier_trim_args;
+typedef struct hgs_hier_trim_report {
+  int32_t first_bad[4]; /* first offending node per check, -1 if none: [0] start != i or count_leafs + count_merged
+                         * != 1; [1] a children range outside [1, N) or a negative children count; [2] node 0's parent
+                         * != -1, or another node's parent outside [0, N) or not claiming it; [3] a kept node under a
+                         * dropped parent */
+  int64_t kept;         /* N': nodes of the trimmed hierarchy */
+  int64_t stubs;        /* kept nodes with children whose own test fails */
+} hgs_hier_trim_report;
+size_t hgs_hier_trim_tmp_bytes(int64_t N);
+int hgs_hier_trim_plan(const hgs_hier_view* in, const hgs_hier_trim_args* args, void* tmp, hgs_hier_trim_report* report,
+                       hgs_stream_t stream, int device);
+int hgs_hier_trim_apply(const hgs_hier_view* in, const hgs_hier_view* out, const void* tmp, int32_t* old_of_new,
+                        int32_t* new_of_old, hgs_stream_t stream, int device);
+
+/* ---------------------------------------------------------------------------
  * Fused SSIM loss (hgs.loss.ssim): the standard SSIM of the reference's loss -- an 11-tap
  * Gaussian window (sigma 1.5, normalised to sum 1) applied separably, zero padding, C1 = 0.01^2, C2 = 0.03^2 -- of
  * img1 against img2, both float32 [N,C,H,W] contiguous on the device, and its gradient with respect to img1.
