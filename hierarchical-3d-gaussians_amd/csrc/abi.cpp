@@ -723,6 +723,106 @@ int hgs_hier_trim_apply(const hgs_hier_view* in, const hgs_hier_view* out, const
   return launch_hier_trim_apply(*in, *out, tmp, old_of_new, new_of_old, shs16, static_cast<hipStream_t>(stream));
 }
 
+// The renderer's SH basis of bands 1..3 at a unit direction (hgs.hierarchy.sh_band_basis), b[0..3), b[3..8), b[8..15).
+static void sh_band_basis(const double d[3], double b[15]) {
+  const double x = d[0], y = d[1], z = d[2];
+  const double xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+  const double C1 = 0.4886025119029199;
+  b[0] = -C1 * y; b[1] = C1 * z; b[2] = -C1 * x;
+  b[3] = 1.0925484305920792 * xy; b[4] = -1.0925484305920792 * yz; b[5] = 0.31539156525252005 * (2.0 * zz - xx - yy);
+  b[6] = -1.0925484305920792 * xz; b[7] = 0.5462742152960396 * (xx - yy);
+  b[8] = -0.5900435899266435 * y * (3 * xx - yy); b[9] = 2.890611442640554 * xy * z;
+  b[10] = -0.4570457994644658 * y * (4 * zz - xx - yy); b[11] = 0.3731763325901154 * z * (2 * zz - 3 * xx - 3 * yy);
+  b[12] = -0.4570457994644658 * x * (4 * zz - xx - yy); b[13] = 1.445305721320277 * z * (xx - yy);
+  b[14] = -0.5900435899266435 * x * (xx - 3 * yy);
+}
+
+// The parameter block of a similarity transform: everything hgs.h lists, on the host.
+static int check_transform_args(const hgs_hier_transform_args* a) {
+  bool finite = std::isfinite(a->s) && std::isfinite(a->log_s);
+  for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(a->t[k]);
+  if (!finite || !(a->s > 0.0)) { set_error("bad transform: s and t must be finite and s > 0"); return HGS_ERR_INVALID; }
+  if (!(std::fabs(a->log_s - std::log(a->s)) <= 1e-12)) { set_error("bad transform: log_s is not log(s)"); return HGS_ERR_INVALID; }
+  const double* R = a->R;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double dot = R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1] + R[3 * i + 2] * R[3 * j + 2];
+      if (!(std::fabs(dot - (i == j ? 1.0 : 0.0)) <= 1e-9)) { set_error("bad transform: R is not orthonormal (|R R^T - I| > 1e-9)"); return HGS_ERR_INVALID; }
+    }
+  const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+  if (!(det > 0.0)) { set_error("bad transform: det R < 0 (a mirror)"); return HGS_ERR_INVALID; }
+  const double w = a->q[0], x = a->q[1], y = a->q[2], z = a->q[3];
+  const double Rq[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                        2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                        2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)};
+  for (int k = 0; k < 9; ++k)
+    if (!(std::fabs(Rq[k] - R[k]) <= 1e-9)) { set_error("bad transform: q does not reproduce R"); return HGS_ERR_INVALID; }
+  const double* D[3] = {a->D1, a->D2, a->D3};
+  for (int l = 1; l <= 3; ++l) {
+    const int n = 2 * l + 1;
+    const double* Dl = D[l - 1];
+    for (int i = 0; i < n; ++i)
+      for (int j = 0; j < n; ++j) {
+        double dot = 0.0;
+        for (int k = 0; k < n; ++k) dot += Dl[i * n + k] * Dl[j * n + k];
+        if (!(std::fabs(dot - (i == j ? 1.0 : 0.0)) <= 1e-9)) { set_error("bad transform: D%d is not orthogonal", l); return HGS_ERR_INVALID; }
+      }
+  }
+  // consistency with R at 16 fixed directions (a Fibonacci sphere): D_l^T b_l(d) = b_l(R^T d)
+  for (int i = 0; i < 16; ++i) {
+    const double zc = 1.0 - (2.0 * i + 1.0) / 16.0, r = std::sqrt(1.0 - zc * zc), phi = i * 2.399963229728653;
+    const double d[3] = {r * std::cos(phi), r * std::sin(phi), zc};
+    const double dr[3] = {R[0] * d[0] + R[3] * d[1] + R[6] * d[2], R[1] * d[0] + R[4] * d[1] + R[7] * d[2],
+                          R[2] * d[0] + R[5] * d[1] + R[8] * d[2]};
+    double b[15], br[15];
+    sh_band_basis(d, b);
+    sh_band_basis(dr, br);
+    for (int l = 1; l <= 3; ++l) {
+      const int n = 2 * l + 1, o = l * l - 1;
+      const double* Dl = D[l - 1];
+      for (int j = 0; j < n; ++j) {
+        double v = 0.0;
+        for (int k = 0; k < n; ++k) v += Dl[k * n + j] * b[o + k];
+        if (!(std::fabs(v - br[o + j]) <= 1e-9)) { set_error("bad transform: D%d is not the SH block of R", l); return HGS_ERR_INVALID; }
+      }
+    }
+  }
+  return HGS_OK;
+}
+
+int hgs_hier_transform(const hgs_hier_view* in, const hgs_hier_view* out, const hgs_hier_transform_args* args,
+                       hgs_stream_t stream, int device) {
+  if (!in || !out || !args) { set_error("null argument"); return HGS_ERR_INVALID; }
+  int rc = check_trim_view(in, "input");
+  if (!rc) rc = check_trim_view(out, "output");
+  if (rc) return rc;
+  if (in->G > kHierMergeMaxN) { set_error("bad sizes: G=%lld > 2^31 - 1", (long long)in->G); return HGS_ERR_INVALID; }
+  if (in->G != out->G || in->N != out->N || in->M != out->M) {
+    set_error("bad sizes: input (G=%lld, N=%lld, M=%d) != output (G=%lld, N=%lld, M=%d)", (long long)in->G, (long long)in->N,
+              in->M, (long long)out->G, (long long)out->N, out->M);
+    return HGS_ERR_INVALID;
+  }
+  if (in->M != 1 && in->M != 4 && in->M != 9 && in->M != 16) { set_error("bad sizes: M=%d not in {1, 4, 9, 16} (whole SH bands only)", in->M); return HGS_ERR_INVALID; }
+  // every output array is its input array (in place) or does not overlap it
+  const size_t G = (size_t)in->G, N = (size_t)in->N;
+  const struct { const void* a; const void* b; size_t bytes; const char* name; } pairs[7] = {
+      {in->xyz, out->xyz, G * 12, "xyz"}, {in->shs, out->shs, G * 12 * (size_t)in->M, "shs"}, {in->alpha, out->alpha, G * 4, "alpha"},
+      {in->log_scales, out->log_scales, G * 12, "log_scales"}, {in->rots, out->rots, G * 16, "rots"},
+      {in->nodes, out->nodes, N * 28, "nodes"}, {in->boxes, out->boxes, N * 32, "boxes"}};
+  for (const auto& pr : pairs) {
+    const uintptr_t a = (uintptr_t)pr.a, b = (uintptr_t)pr.b;
+    if (a != b && a < b + pr.bytes && b < a + pr.bytes) {
+      set_error("output %s overlaps input %s without being the same array", pr.name, pr.name);
+      return HGS_ERR_INVALID;
+    }
+  }
+  rc = check_transform_args(args);
+  if (rc) return rc;
+  const bool shs16 = (3 * in->M) % 4 == 0 && (((uintptr_t)in->shs | (uintptr_t)out->shs) & 15u) == 0;
+  HGS_HIP(hipSetDevice(device));
+  return launch_hier_transform(*in, *out, *args, shs16, static_cast<hipStream_t>(stream));
+}
+
 size_t hgs_ssim_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W) {
   if (!ssim_sizes_ok(N, C, H, W)) return 0;
   return ssim_tmp_bytes(N, C, H, W);

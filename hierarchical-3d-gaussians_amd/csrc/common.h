@@ -324,6 +324,10 @@ int launch_hier_trim_plan(const hgs_hier_view& in, const hgs_hier_trim_args& arg
                           hgs_hier_trim_report* report, hipStream_t s, int device);
 int launch_hier_trim_apply(const hgs_hier_view& in, const hgs_hier_view& out, const void* tmp, int32_t* old_of_new,
                            int32_t* new_of_old, bool shs16, hipStream_t s);
+// similarity transform (hier_transform.hip): sizes, pointers, alignment and the parameter block checked by the caller;
+// shs16: move shs in 16-byte pieces (12 M a multiple of 16, both bases aligned)
+int launch_hier_transform(const hgs_hier_view& in, const hgs_hier_view& out, const hgs_hier_transform_args& a, bool shs16,
+                          hipStream_t s);
 // fused SSIM loss (ssim.hip): ssim_sizes_ok sets the error message; the launches expect sizes it accepted
 bool ssim_sizes_ok(int32_t N, int32_t C, int32_t H, int32_t W);
 size_t ssim_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W);

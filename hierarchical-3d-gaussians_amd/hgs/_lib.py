@@ -84,6 +84,11 @@ class HierTrimReport(C.Structure):
     _fields_ = [("first_bad", C.c_int32 * 4), ("kept", C.c_int64), ("stubs", C.c_int64)]
 
 
+class HierTransformArgs(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("q", C.c_double * 4), ("s", C.c_double), ("log_s", C.c_double),
+                ("t", C.c_double * 3), ("D1", C.c_double * 9), ("D2", C.c_double * 25), ("D3", C.c_double * 49)]
+
+
 class ResidRows(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("means3D", "shs", "opacities", "scales", "rotations")]
 
@@ -179,6 +184,7 @@ SIGNATURES = {
     "hgs_hier_trim_plan": (C.c_int, [C.POINTER(HierView), C.POINTER(HierTrimArgs), _P, C.POINTER(HierTrimReport), _P,
                                      C.c_int]),
     "hgs_hier_trim_apply": (C.c_int, [C.POINTER(HierView), C.POINTER(HierView), _P, _P, _P, _P, C.c_int]),
+    "hgs_hier_transform": (C.c_int, [C.POINTER(HierView), C.POINTER(HierView), C.POINTER(HierTransformArgs), _P, C.c_int]),
     "hgs_ssim_tmp_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "hgs_ssim_fwd": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int]),
     "hgs_ssim_bwd": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,

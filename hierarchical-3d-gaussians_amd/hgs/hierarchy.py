@@ -10,7 +10,9 @@ chunk at a time, behind ``python -m hgs.merge_hierarchies``).  ``align_hierarchy
 (the same rule on the device, behind ``--align`` and ``python -m hgs.align_hierarchy``) re-express every node's rotation
 and scales in the frame closest to its parent's, opt-in.  ``trim_hierarchy`` (the numpy spec) and ``trim_hierarchy_gpu``
 (the same rule on the device, behind ``python -m hgs.trim_hierarchy``) make a smaller copy: a detail floor, a region, a
-node budget.
+node budget.  ``transform_hierarchy`` (the numpy spec) and ``transform_hierarchy_gpu`` (the same rule on the device, behind
+``python -m hgs.transform_hierarchy``) move a hierarchy to another frame by a similarity ``similarity(...)`` builds: means,
+rotations, scales, boxes and SH bands follow; ``transform_camera`` moves a camera with it.
 Layout = DESIGN.md '.hier layout':
 
   one Gaussian per node, Gaussian index == node index (``start`` = node id)
@@ -960,3 +962,287 @@ def trim_hierarchy_gpu(h: Hierarchy, min_extent=0.0, roi=None, max_nodes=None, s
         stats["plan_ms"], stats["apply_ms"] = ev[0].elapsed_time(mid), mid.elapsed_time(ev[1])
     stub_ids = ((h.nodes[:, 6][old_of_new.long()] > 0) & (out.nodes[:, 6] == 0)).nonzero().flatten().to(torch.int32)
     return TrimResult(out, old_of_new, new_of_old, float(e), int(rep.stubs), stub_ids)
+
+
+# ---- similarity transform: x' = s R x + t, rotations, scales, boxes and SH bands following -------------------------------
+TRANSFORM_MAX_NODES = (1 << 31) - 1
+TRANSFORM_SH_WIDTHS = (1, 4, 9, 16)
+_SH_C1 = 0.4886025119029199
+_SH_C2 = (1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792, 0.5462742152960396)
+_SH_C3 = (-0.5900435899266435, 2.890611442640554, -0.4570457994644658, 0.3731763325901154, -0.4570457994644658,
+          1.445305721320277, -0.5900435899266435)
+
+
+def sh_band_basis(d):
+    """The basis polynomials of bands 1, 2, 3 (the renderer's, with their signs and constants: a colour is
+    sum_m c_m b_m(d)) at unit directions d float64 [n,3] -> (b1 [n,3], b2 [n,5], b3 [n,7]).  csrc/abi.cpp repeats it
+    for the consistency check of hgs_hier_transform."""
+    d = np.asarray(d, dtype=np.float64)
+    x, y, z = d[:, 0], d[:, 1], d[:, 2]
+    xx, yy, zz, xy, yz, xz = x * x, y * y, z * z, x * y, y * z, x * z
+    b1 = np.stack([-_SH_C1 * y, _SH_C1 * z, -_SH_C1 * x], 1)
+    b2 = np.stack([_SH_C2[0] * xy, _SH_C2[1] * yz, _SH_C2[2] * (2.0 * zz - xx - yy), _SH_C2[3] * xz,
+                   _SH_C2[4] * (xx - yy)], 1)
+    b3 = np.stack([_SH_C3[0] * y * (3 * xx - yy), _SH_C3[1] * xy * z, _SH_C3[2] * y * (4 * zz - xx - yy),
+                   _SH_C3[3] * z * (2 * zz - 3 * xx - 3 * yy), _SH_C3[4] * x * (4 * zz - xx - yy),
+                   _SH_C3[5] * z * (xx - yy), _SH_C3[6] * x * (xx - 3 * yy)], 1)
+    return b1, b2, b3
+
+
+def fibonacci_sphere(n=64):
+    """n fixed unit directions (float64 [n,3]): z_i = 1 - (2 i + 1) / n, longitude i times the golden angle."""
+    i = np.arange(n, dtype=np.float64)
+    z = 1.0 - (2.0 * i + 1.0) / n
+    r = np.sqrt(1.0 - z * z)
+    phi = i * (np.pi * (3.0 - np.sqrt(5.0)))
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], 1)
+
+
+def sh_rotation_blocks(R):
+    """(D1 [3,3], D2 [5,5], D3 [7,7]) float64 with c' = D_l c the band-l coefficients of the rotated function:
+    c' . b_l(d') = c . b_l(R^T d') for every direction d'.  D_l = lstsq(B_l(d), B_l(R^T d)) over the 64 directions of
+    ``fibonacci_sphere`` (the bands are rotation invariant, so the fit is exact up to rounding); entries within 1e-13
+    of -1, 0 or 1 are set to that value, so the identity and the signed permutations that give such blocks are exact."""
+    R = np.asarray(R, dtype=np.float64).reshape(3, 3)
+    d = fibonacci_sphere(64)
+    out = []
+    for B, Br in zip(sh_band_basis(d), sh_band_basis(d @ R)):        # rows of d @ R are R^T d
+        D = np.linalg.lstsq(B, Br, rcond=None)[0]
+        for v in (-1.0, 0.0, 1.0):
+            D[np.abs(D - v) < 1e-13] = v
+        out.append(D)
+    return tuple(out)
+
+
+@dataclass
+class Similarity:
+    """x' = s R x + t with everything a transform of a hierarchy needs, float64 (``similarity`` builds it):
+    R [3,3] proper rotation, q_R [4] its quaternion (w,x,y,z), s > 0, log_s = log(s), t [3], and the SH blocks
+    D1 [3,3], D2 [5,5], D3 [7,7] of ``sh_rotation_blocks``.  The device consumes this block as it is."""
+    R: np.ndarray
+    q_R: np.ndarray
+    s: float
+    log_s: float
+    t: np.ndarray
+    D1: np.ndarray
+    D2: np.ndarray
+    D3: np.ndarray
+
+    def inverse(self) -> "Similarity":
+        """x = R^T (x' - t) / s."""
+        Ri = self.R.T.copy()
+        si = 1.0 / self.s
+        return similarity(R=Ri, scale=si, translate=-(si * (Ri @ self.t)))
+
+    def compose(self, other: "Similarity") -> "Similarity":
+        """The map x -> self(other(x)): ``other`` is applied first."""
+        return similarity(R=self.R @ other.R, scale=self.s * other.s, translate=self.s * (self.R @ other.t) + self.t)
+
+    def apply(self, x):
+        """s R x + t on points float64 [...,3] (numpy)."""
+        return self.s * (np.asarray(x, dtype=np.float64) @ self.R.T) + self.t
+
+    def matrix(self):
+        """The 4x4 row-vector matrix S: [x', 1] = [x, 1] S (float64)."""
+        S = np.eye(4)
+        S[:3, :3] = self.s * self.R.T
+        S[3, :3] = self.t
+        return S
+
+
+def similarity(R=None, quat=None, scale=1.0, translate=(0.0, 0.0, 0.0)) -> Similarity:
+    """The parameter block of x' = s R x + t, built on the host in float64.  ``R`` [3,3] (kept as given; refused unless
+    |R R^T - I| <= 1e-9 and det R > 0: no mirrors) or ``quat`` (w,x,y,z), normalised here; neither: the identity
+    rotation.  ``scale`` finite and > 0, ``translate`` finite."""
+    if R is not None and quat is not None:
+        raise ValueError("give R or quat, not both")
+    if quat is not None:
+        q = np.asarray(quat, dtype=np.float64).reshape(-1)
+        n = float(np.linalg.norm(q)) if q.shape == (4,) else 0.0
+        if not (np.isfinite(n) and n > 0.0):
+            raise ValueError("quat is four finite numbers (w,x,y,z), not all zero")
+        R = _rot_from_quat((q / n)[None])[0]
+    R = np.eye(3) if R is None else np.array(R, dtype=np.float64)
+    if R.shape != (3, 3) or not np.isfinite(R).all() or np.abs(R @ R.T - np.eye(3)).max() > 1e-9:
+        raise ValueError("R is not orthonormal (|R R^T - I| > 1e-9): shear and non-uniform scale are not similarities")
+    if np.linalg.det(R) <= 0:
+        raise ValueError("det R < 0: a mirror, not a rotation")
+    s = float(scale)
+    if not (np.isfinite(s) and s > 0.0):
+        raise ValueError(f"scale = {s}; a finite number > 0 expected")
+    t = np.asarray(translate, dtype=np.float64).reshape(-1)
+    if t.shape != (3,) or not np.isfinite(t).all():
+        raise ValueError("translate is three finite numbers")
+    D1, D2, D3 = sh_rotation_blocks(R)
+    return Similarity(R=R, q_R=_quat_from_rot(R[None])[0], s=s, log_s=float(np.log(s)), t=t.copy(), D1=D1, D2=D2, D3=D3)
+
+
+def check_similarity(sim: Similarity):
+    """The checks hgs_hier_transform makes on its parameter block, on the host (ValueError names the first that fails):
+    s, t finite and s > 0; log_s = log(s) to 1e-12; |R R^T - I| <= 1e-9, det R > 0; q_R reproduces R to 1e-9; every D_l
+    orthogonal to 1e-9 and D_l^T b_l(d) = b_l(R^T d) to 1e-9 at the 16 directions of ``fibonacci_sphere(16)``."""
+    R, t = np.asarray(sim.R, dtype=np.float64).reshape(3, 3), np.asarray(sim.t, dtype=np.float64).reshape(-1)
+    if not (np.isfinite(sim.s) and np.isfinite(sim.log_s) and t.shape == (3,) and np.isfinite(t).all() and sim.s > 0):
+        raise ValueError("bad transform: s and t must be finite and s > 0")
+    if not abs(sim.log_s - np.log(sim.s)) <= 1e-12:
+        raise ValueError("bad transform: log_s is not log(s)")
+    if not np.abs(R @ R.T - np.eye(3)).max() <= 1e-9:
+        raise ValueError("bad transform: R is not orthonormal (|R R^T - I| > 1e-9)")
+    if not np.linalg.det(R) > 0:
+        raise ValueError("bad transform: det R < 0 (a mirror)")
+    if not np.abs(_rot_from_quat(np.asarray(sim.q_R, dtype=np.float64).reshape(1, 4))[0] - R).max() <= 1e-9:
+        raise ValueError("bad transform: q does not reproduce R")
+    d = fibonacci_sphere(16)
+    for l, D, b, br in zip((1, 2, 3), (sim.D1, sim.D2, sim.D3), sh_band_basis(d), sh_band_basis(d @ R)):
+        D = np.asarray(D, dtype=np.float64)
+        if D.shape != (2 * l + 1, 2 * l + 1) or not np.abs(D @ D.T - np.eye(2 * l + 1)).max() <= 1e-9:
+            raise ValueError(f"bad transform: D{l} is not orthogonal")
+        if not np.abs(b @ D - br).max() <= 1e-9:
+            raise ValueError(f"bad transform: D{l} is not the SH block of R")
+
+
+def _transform_sh_width(shs):
+    M = int(shs.shape[1]) if shs.dim() == 3 else int(shs.shape[1]) // 3
+    if M not in TRANSFORM_SH_WIDTHS:
+        raise ValueError(f"M = {M} SH coefficients per row; whole bands only: one of {TRANSFORM_SH_WIDTHS}")
+    return M
+
+
+def transform_rows(sim: Similarity, xyz, shs, log_scales, rots, round32=True):
+    """The row rule on numpy arrays (xyz [G,3], shs [G,M,3], log_scales [G,3], rots [G,4]): every product and sum in
+    float64, every sum left to right, rounded once to float32 (``round32=False``: left in float64).
+    xyz'_a = ((R_a0 x_0 + R_a1 x_1) + R_a2 x_2) s + t_a; rots' = q_R (x) q (Hamilton, norms kept); log_scales' =
+    log_scales + log s; SH band 0 keeps its bits, band l: c'_{m,ch} = sum_m' D_l[m][m'] c_{m',ch}."""
+    R, t = sim.R, sim.t
+    x = np.asarray(xyz, dtype=np.float64)
+    out_x = np.stack([((R[a, 0] * x[:, 0] + R[a, 1] * x[:, 1]) + R[a, 2] * x[:, 2]) * sim.s + t[a] for a in range(3)], 1)
+    out_q = _quat_mul(sim.q_R[None, :], np.asarray(rots, dtype=np.float64))
+    out_ls = np.asarray(log_scales, dtype=np.float64) + sim.log_s
+    c = np.asarray(shs)
+    out_c = c.astype(np.float32 if round32 else np.float64)           # band 0: the input's bits
+    cd = c.astype(np.float64)
+    for l, D in ((1, sim.D1), (2, sim.D2), (3, sim.D3)):
+        o, n = l * l, 2 * l + 1
+        if c.shape[1] < o + n:
+            break
+        for m in range(n):
+            acc = D[m, 0] * cd[:, o, :]
+            for k in range(1, n):
+                acc = acc + D[m, k] * cd[:, o + k, :]
+            out_c[:, o + m, :] = acc
+    if round32:
+        out_x, out_q, out_ls = (v.astype(np.float32) for v in (out_x, out_q, out_ls))
+    return out_x, out_c, out_ls, out_q
+
+
+def transform_boxes(sim: Similarity, boxes):
+    """The box rule on float32 numpy boxes [N,2,4]: lo'_a = (sum_b (R_ab >= 0 ? R_ab lo_b : R_ab hi_b)) s + t_a, hi'_a
+    the same with lo and hi swapped (float64, left to right, rounded once): the AABB of the rotated box.  Every term
+    is monotone in its input, so nested boxes stay nested after rounding.  boxes'[:,0,3] = the largest edge of the
+    ROUNDED box in float32, as the builder computes it; boxes[:,1,3] is copied."""
+    b = np.asarray(boxes, dtype=np.float32).reshape(-1, 2, 4)
+    lo, hi = b[:, 0, :3].astype(np.float64), b[:, 1, :3].astype(np.float64)
+    out = b.copy()
+    for a in range(3):
+        tl = [sim.R[a, k] * (lo[:, k] if sim.R[a, k] >= 0 else hi[:, k]) for k in range(3)]
+        th = [sim.R[a, k] * (hi[:, k] if sim.R[a, k] >= 0 else lo[:, k]) for k in range(3)]
+        out[:, 0, a] = (((tl[0] + tl[1]) + tl[2]) * sim.s + sim.t[a]).astype(np.float32)
+        out[:, 1, a] = (((th[0] + th[1]) + th[2]) * sim.s + sim.t[a]).astype(np.float32)
+    e = out[:, 1, :3] - out[:, 0, :3]
+    out[:, 0, 3] = np.maximum(np.maximum(e[:, 0], e[:, 1]), e[:, 2])
+    return out
+
+
+def transform_hierarchy(h: Hierarchy, sim: Similarity) -> Hierarchy:
+    """Move a hierarchy by x' = s R x + t (the float64 numpy spec; ``transform_hierarchy_gpu`` is the same rule on the
+    device): all G rows by ``transform_rows`` (the skybox tail behind the N nodes included), the N boxes by
+    ``transform_boxes``; ``nodes`` and ``alpha`` are copied bit for bit.  M must be 1, 4, 9 or 16.  The identity
+    reproduces every bit of finite input except the sign of a zero (-0.0 + 0.0 = +0.0).  For signed-permutation
+    rotations the boxes are the permuted boxes; for others they grow (the AABB of the rotated AABB, up to sqrt 3),
+    and with them the LOD sizes: what is invariant is the content rendered at a given cut, not the cut at a given
+    granularity.  -> a new Hierarchy (host)."""
+    M = _transform_sh_width(h.shs)
+    check_similarity(sim)
+    G, N = int(h.xyz.shape[0]), int(h.nodes.shape[0])
+    if N < 1 or G < N or G > TRANSFORM_MAX_NODES:
+        raise ValueError(f"G = {G} rows, N = {N} nodes; 1 <= N <= G <= 2^31 - 1 expected")
+    np32 = lambda v: v.detach().cpu().numpy().astype(np.float32)
+    x, c, ls, q = transform_rows(sim, np32(h.xyz), np32(h.shs).reshape(G, M, 3), np32(h.log_scales), np32(h.rots))
+    boxes = transform_boxes(sim, np32(h.boxes).reshape(N, 2, 4))
+    cp = lambda v: v.detach().cpu().clone()
+    return Hierarchy(xyz=torch.from_numpy(x), shs=torch.from_numpy(c).reshape(h.shs.shape), alpha=cp(h.alpha),
+                     log_scales=torch.from_numpy(ls), rots=torch.from_numpy(q), nodes=cp(h.nodes),
+                     boxes=torch.from_numpy(boxes).reshape(h.boxes.shape))
+
+
+def transform_args(sim: Similarity):
+    """``sim`` as the C ABI's hgs_hier_transform_args (the same doubles)."""
+    from . import _lib
+    a = _lib.HierTransformArgs()
+    a.R[:] = [float(v) for v in np.asarray(sim.R, dtype=np.float64).reshape(-1)]
+    a.q[:] = [float(v) for v in np.asarray(sim.q_R, dtype=np.float64).reshape(-1)]
+    a.s, a.log_s = float(sim.s), float(sim.log_s)
+    a.t[:] = [float(v) for v in np.asarray(sim.t, dtype=np.float64).reshape(-1)]
+    for name in ("D1", "D2", "D3"):
+        getattr(a, name)[:] = [float(v) for v in np.asarray(getattr(sim, name), dtype=np.float64).reshape(-1)]
+    return a
+
+
+def transform_hierarchy_gpu(h: Hierarchy, sim: Similarity, inplace=False, stats=None) -> Hierarchy:
+    """``transform_hierarchy`` on the GPU (csrc/hier_transform.hip, hgs_hier_transform).  ``h``: contiguous device
+    tensors (float32 rows of G >= N, int32 nodes [N,7], boxes [N,2,4]).  ``inplace``: ``h``'s own tensors are rewritten
+    and ``h`` is returned; otherwise ``h`` is left as it is and a new Hierarchy on the same device is returned.  Every
+    output bit equals the spec's.  The call is asynchronous on the current stream.  ``stats`` (a dict, optional)
+    receives ``transform_ms`` (device events around the call).  No CPU fallback: raises without libhgs.so or a GPU."""
+    import ctypes as C
+    from . import _lib
+    lib = _lib.lib()
+    if not torch.cuda.is_available():
+        raise RuntimeError("transform_hierarchy_gpu needs a GPU (there is no CPU fallback; transform_hierarchy is the "
+                           "numpy spec)")
+    M = _transform_sh_width(h.shs)
+    check_similarity(sim)
+    G, N = int(h.xyz.shape[0]), int(h.nodes.shape[0])
+    if N < 1 or G < N or G > TRANSFORM_MAX_NODES:
+        raise ValueError(f"G = {G} rows, N = {N} nodes; 1 <= N <= G <= 2^31 - 1 expected")
+    dev = h.nodes.device
+    for name in ("xyz", "shs", "alpha", "log_scales", "rots", "nodes", "boxes"):
+        t = getattr(h, name)
+        want = torch.int32 if name == "nodes" else torch.float32
+        if not (t.is_cuda and t.device == dev and t.dtype == want and t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {want} tensor on {dev}")
+    out = h if inplace else Hierarchy(*(torch.empty_like(getattr(h, k)) for k in
+                                        ("xyz", "shs", "alpha", "log_scales", "rots", "nodes", "boxes")))
+    p = lambda t: t.data_ptr()
+    view = lambda x: _lib.HierView(G, N, M, 0, p(x.xyz), p(x.shs), p(x.alpha), p(x.log_scales), p(x.rots), p(x.nodes),
+                                   p(x.boxes))
+    args = transform_args(sim)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        _lib.check(lib.hgs_hier_transform(C.byref(view(h)), C.byref(view(out)), C.byref(args), stream, dev.index or 0),
+                   "hgs_hier_transform")
+        ev[1].record()
+    if stats is not None:
+        ev[1].synchronize()
+        stats["transform_ms"] = ev[0].elapsed_time(ev[1])
+    return out
+
+
+def transform_camera(cam, sim: Similarity):
+    """The camera that sees a hierarchy moved by ``sim`` as ``cam`` saw the original: the stored (row-vector)
+    ``world_view_transform`` and ``full_proj_transform`` left-multiplied by the inverse of ``sim.matrix()``, so that
+    [x', 1] W' = [x, 1] W, and camera_center' = s R c + t.  The view matrix then carries the factor 1 / s: distances
+    in camera space are the original's.  Computed in float64, stored in the camera's dtype.  -> a copy of ``cam``."""
+    import copy
+    Si = np.linalg.inv(sim.matrix())
+    out = copy.copy(cam)
+    for name in ("world_view_transform", "full_proj_transform"):
+        m = getattr(cam, name)
+        moved = Si @ m.detach().cpu().double().numpy()
+        setattr(out, name, torch.from_numpy(moved).to(dtype=m.dtype, device=m.device))
+    c = cam.camera_center
+    setattr(out, "camera_center", torch.from_numpy(sim.apply(c.detach().cpu().double().numpy()))
+            .to(dtype=c.dtype, device=c.device))
+    return out

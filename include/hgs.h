@@ -643,6 +643,39 @@ int hgs_hier_trim_apply(const hgs_hier_view* in, const hgs_hier_view* out, const
                         int32_t* new_of_old, hgs_stream_t stream, int device);
 
 /* ---------------------------------------------------------------------------
+ * Similarity transform of a hierarchy on the device: the rule of hgs.hierarchy.transform_hierarchy (DESIGN.md section 4
+ * and section 7 f-18).  The map is x' = s R x + t, R a proper rotation, s > 0.  All G rows are transformed (a skybox
+ * tail behind the N nodes included), the N boxes are transformed, nodes and alpha are copied bit for bit.  Every product
+ * and sum in double, every sum left to right, no contraction, one rounding to float32:
+ *   xyz'_a        = ((R[3a] x_0 + R[3a+1] x_1) + R[3a+2] x_2) s + t_a
+ *   rots'         = q (x) rots, the Hamilton product (w,x,y,z); norms are not renormalised
+ *   log_scales'_k = log_scales_k + log_s
+ *   shs           band 0 (coefficient 0) keeps its bits; band l = 1, 2, 3 (coefficients l^2 .. l^2 + 2 l), per channel:
+ *                 c'_m = sum_m' D_l[m (2 l + 1) + m'] c_m', M = 1, 4, 9 or 16 only (whole bands)
+ *   boxes         lo'_a = (sum_b (R_ab >= 0 ? R_ab lo_b : R_ab hi_b)) s + t_a, hi'_a the same with lo and hi swapped;
+ *                 boxes'[n,0,3] = max_a (hi'_a - lo'_a) in float32 on the rounded values; boxes[n,1,3] is copied
+ * The device does not derive the SH blocks: it consumes D1, D2, D3 as given (hgs.hierarchy.sh_rotation_blocks), so the
+ * spec and the kernel share every bit of them.  Each array of `out` is the same pointer as in `in` (in place) or memory
+ * that does not overlap any array of `in`; both views have the same G, N and M.  Asynchronous on `stream`, no host wait.
+ * Checked before any HIP call (HGS_ERR_INVALID, hgs_last_error names it, nothing is written): 1 <= N <= G <= 2^31 - 1;
+ * an output array that overlaps its input array without being that array is refused; every array 4-byte aligned, rots and boxes 16-byte aligned (shs moves in 16-byte pieces where 12 M is a multiple of 16
+ * and both shs bases are 16-byte aligned, in 4-byte pieces otherwise); M in {1, 4, 9, 16}; |R R^T - I| <= 1e-9 and
+ * det R > 0; q reproduces R to 1e-9; s and t finite, s > 0; |log_s - log(s)| <= 1e-12; every D_l orthogonal to 1e-9 and
+ * consistent with R: D_l^T b_l(d) = b_l(R^T d) to 1e-9 at 16 fixed directions, b_l the renderer's basis of band l. */
+typedef struct hgs_hier_transform_args {
+  double R[9];    /* row-major */
+  double q[4];    /* the quaternion of R, (w,x,y,z) */
+  double s;
+  double log_s;   /* log(s) */
+  double t[3];
+  double D1[9];   /* SH blocks, row-major: c' = D_l c */
+  double D2[25];
+  double D3[49];
+} hgs_hier_transform_args;
+int hgs_hier_transform(const hgs_hier_view* in, const hgs_hier_view* out, const hgs_hier_transform_args* args,
+                       hgs_stream_t stream, int device);
+
+/* ---------------------------------------------------------------------------
  * Fused SSIM loss (hgs.loss.ssim): the standard SSIM of the reference's loss -- an 11-tap
  * Gaussian window (sigma 1.5, normalised to sum 1) applied separably, zero padding, C1 = 0.01^2, C2 = 0.03^2 -- of
  * img1 against img2, both float32 [N,C,H,W] contiguous on the device, and its gradient with respect to img1.
