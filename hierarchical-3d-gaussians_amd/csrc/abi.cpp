@@ -582,6 +582,19 @@ int hgs_sort_pairs(const uint64_t* keys_in, const uint32_t* vals_in, uint64_t* k
 }
 
 constexpr int32_t kHierBuildMaxP = 1 << 30;
+constexpr int64_t kHierMaxNodes = 0x7fffffff;   // merge, align, trim and transform: node indices are int32
+
+// The workspace pointer of a hierarchy call: there, and kAlign-aligned (those workspaces are carved without slack).
+static int check_hier_tmp(const void* tmp) {
+  if (!tmp) { set_error("null argument"); return HGS_ERR_INVALID; }
+  if ((uintptr_t)tmp & (kAlign - 1)) { set_error("tmp must be %d-byte aligned", (int)kAlign); return HGS_ERR_INVALID; }
+  return HGS_OK;
+}
+
+// shs may move in 16-byte pieces: 12 M a multiple of 16 and both bases aligned
+static bool shs16_ok(const hgs_hier_view* in, const hgs_hier_view* out) {
+  return (3 * in->M) % 4 == 0 && (((uintptr_t)in->shs | (uintptr_t)out->shs) & 15u) == 0;
+}
 
 size_t hgs_hier_build_tmp_bytes(int32_t P) {
   if (P < 1 || P > kHierBuildMaxP) return 0;
@@ -599,17 +612,15 @@ int hgs_hier_build(const float* xyz, const float* scales, const float* rots, con
     return HGS_ERR_INVALID;
   }
   if (((uintptr_t)out_shs | (uintptr_t)out_rots | (uintptr_t)out_boxes) & 15u) { set_error("out_shs / out_rots / out_boxes must be 16-byte aligned"); return HGS_ERR_INVALID; }
-  if ((uintptr_t)tmp & (kAlign - 1)) { set_error("tmp must be %d-byte aligned", (int)kAlign); return HGS_ERR_INVALID; }
+  if (int rc = check_hier_tmp(tmp)) return rc;
   HGS_HIP(hipSetDevice(device));
   return launch_hier_build(xyz, scales, rots, opacity, shs, P, M, out_xyz, out_shs, out_alpha, out_log_scales, out_rots,
                            out_nodes, out_boxes, tmp, static_cast<hipStream_t>(stream));
 }
 
-constexpr int64_t kHierMergeMaxN = 0x7fffffff;
-
 static int check_merged_view(const hgs_hier_view* merged, int32_t k) {
   if (k < 1) { set_error("bad sizes: k=%d chunks < 1", k); return HGS_ERR_INVALID; }
-  if (merged->N < 1 + (int64_t)k || merged->N > kHierMergeMaxN) {
+  if (merged->N < 1 + (int64_t)k || merged->N > kHierMaxNodes) {
     set_error("bad sizes: merged N=%lld not in [1 + k, 2^31 - 1] (k=%d)", (long long)merged->N, k);
     return HGS_ERR_INVALID;
   }
@@ -625,7 +636,7 @@ static bool null_view(const hgs_hier_view* v) {
 int hgs_hier_merge_place(const hgs_hier_view* chunk, int32_t index, int32_t k, int64_t base, const hgs_hier_view* merged,
                          void* tmp, hgs_hier_merge_report* report, hgs_stream_t stream, int device) {
   if (!chunk || !merged || !report) { set_error("null argument"); return HGS_ERR_INVALID; }
-  if (chunk->N < 1 || chunk->N > kHierMergeMaxN) { set_error("bad sizes: chunk N=%lld not in [1, 2^31 - 1]", (long long)chunk->N); return HGS_ERR_INVALID; }
+  if (chunk->N < 1 || chunk->N > kHierMaxNodes) { set_error("bad sizes: chunk N=%lld not in [1, 2^31 - 1]", (long long)chunk->N); return HGS_ERR_INVALID; }
   if (chunk->G < chunk->N) { set_error("bad sizes: chunk G=%lld < N=%lld", (long long)chunk->G, (long long)chunk->N); return HGS_ERR_INVALID; }
   int rc = check_merged_view(merged, k);
   if (rc) return rc;
@@ -652,28 +663,28 @@ int hgs_hier_merge_root(const hgs_hier_view* merged, int32_t k, hgs_stream_t str
 }
 
 size_t hgs_hier_align_tmp_bytes(int64_t N) {
-  if (N < 1 || N > kHierMergeMaxN) return 0;
+  if (N < 1 || N > kHierMaxNodes) return 0;
   return hier_align_tmp_bytes(N);
 }
 
 int hgs_hier_align(const int32_t* nodes, int64_t N, float* log_scales, float* rots, void* tmp,
                    hgs_hier_align_report* report, hgs_stream_t stream, int device) {
-  if (N < 1 || N > kHierMergeMaxN) { set_error("bad sizes: N=%lld not in [1, 2^31 - 1]", (long long)N); return HGS_ERR_INVALID; }
+  if (N < 1 || N > kHierMaxNodes) { set_error("bad sizes: N=%lld not in [1, 2^31 - 1]", (long long)N); return HGS_ERR_INVALID; }
   if (!nodes || !log_scales || !rots || !tmp || !report) { set_error("null argument"); return HGS_ERR_INVALID; }
   if ((uintptr_t)rots & 15u) { set_error("rots must be 16-byte aligned"); return HGS_ERR_INVALID; }
-  if ((uintptr_t)tmp & (kAlign - 1)) { set_error("tmp must be %d-byte aligned", (int)kAlign); return HGS_ERR_INVALID; }
+  if (int rc = check_hier_tmp(tmp)) return rc;
   HGS_HIP(hipSetDevice(device));
   return launch_hier_align(nodes, N, log_scales, rots, tmp, report, static_cast<hipStream_t>(stream));
 }
 
 size_t hgs_hier_trim_tmp_bytes(int64_t N) {
-  if (N < 1 || N > kHierMergeMaxN) return 0;
+  if (N < 1 || N > kHierMaxNodes) return 0;
   return hier_trim_tmp_bytes(N);
 }
 
-// Sizes, pointers and alignment of one side of a trim call.
-static int check_trim_view(const hgs_hier_view* v, const char* side) {
-  if (v->N < 1 || v->N > kHierMergeMaxN) { set_error("bad sizes: %s N=%lld not in [1, 2^31 - 1]", side, (long long)v->N); return HGS_ERR_INVALID; }
+// Sizes, pointers and alignment of one side of a trim or transform call.
+static int check_hier_view(const hgs_hier_view* v, const char* side) {
+  if (v->N < 1 || v->N > kHierMaxNodes) { set_error("bad sizes: %s N=%lld not in [1, 2^31 - 1]", side, (long long)v->N); return HGS_ERR_INVALID; }
   if (v->G < v->N) { set_error("bad sizes: %s G=%lld < N=%lld", side, (long long)v->G, (long long)v->N); return HGS_ERR_INVALID; }
   if (v->M < 1 || v->M > 64) { set_error("bad sizes: %s M=%d not in [1, 64]", side, v->M); return HGS_ERR_INVALID; }
   if (null_view(v)) { set_error("null argument"); return HGS_ERR_INVALID; }
@@ -688,13 +699,12 @@ static int check_trim_view(const hgs_hier_view* v, const char* side) {
 int hgs_hier_trim_plan(const hgs_hier_view* in, const hgs_hier_trim_args* args, void* tmp, hgs_hier_trim_report* report,
                        hgs_stream_t stream, int device) {
   if (!in || !args || !report) { set_error("null argument"); return HGS_ERR_INVALID; }
-  int rc = check_trim_view(in, "input");
+  int rc = check_hier_view(in, "input");
   if (rc) return rc;
   bool nan = std::isnan(args->min_extent);
   for (int a = 0; a < 3 && args->use_roi; ++a) nan = nan || std::isnan(args->roi_lo[a]) || std::isnan(args->roi_hi[a]);
   if (nan) { set_error("min_extent or a region bound is NaN"); return HGS_ERR_INVALID; }
-  if (!tmp) { set_error("null argument"); return HGS_ERR_INVALID; }
-  if ((uintptr_t)tmp & (kAlign - 1)) { set_error("tmp must be %d-byte aligned", (int)kAlign); return HGS_ERR_INVALID; }
+  if ((rc = check_hier_tmp(tmp))) return rc;
   for (int k = 0; k < 4; ++k) report->first_bad[k] = -1;
   report->kept = report->stubs = 0;
   HGS_HIP(hipSetDevice(device));
@@ -704,12 +714,12 @@ int hgs_hier_trim_plan(const hgs_hier_view* in, const hgs_hier_trim_args* args, 
 int hgs_hier_trim_apply(const hgs_hier_view* in, const hgs_hier_view* out, const void* tmp, int32_t* old_of_new,
                         int32_t* new_of_old, hgs_stream_t stream, int device) {
   if (!in || !out) { set_error("null argument"); return HGS_ERR_INVALID; }
-  int rc = check_trim_view(in, "input");
-  if (!rc) rc = check_trim_view(out, "output");
+  int rc = check_hier_view(in, "input");
+  if (!rc) rc = check_hier_view(out, "output");
   if (rc) return rc;
   if (in->M != out->M) { set_error("bad sizes: input M=%d != output M=%d", in->M, out->M); return HGS_ERR_INVALID; }
   if (!tmp || !old_of_new || !new_of_old) { set_error("null argument"); return HGS_ERR_INVALID; }
-  if ((uintptr_t)tmp & (kAlign - 1)) { set_error("tmp must be %d-byte aligned", (int)kAlign); return HGS_ERR_INVALID; }
+  if ((rc = check_hier_tmp(tmp))) return rc;
   if (((uintptr_t)old_of_new | (uintptr_t)new_of_old) & 3u) { set_error("old_of_new / new_of_old must be 4-byte aligned"); return HGS_ERR_INVALID; }
   int64_t planned_N = 0, kept = 0;
   if (!hier_trim_planned(device, tmp, &planned_N, &kept)) {
@@ -718,9 +728,8 @@ int hgs_hier_trim_apply(const hgs_hier_view* in, const hgs_hier_view* out, const
   }
   if (in->N != planned_N) { set_error("bad sizes: input N=%lld, the plan was made for N=%lld", (long long)in->N, (long long)planned_N); return HGS_ERR_INVALID; }
   if (out->N != kept) { set_error("bad sizes: output N=%lld != the plan's kept count %lld", (long long)out->N, (long long)kept); return HGS_ERR_INVALID; }
-  const bool shs16 = (3 * in->M) % 4 == 0 && (((uintptr_t)in->shs | (uintptr_t)out->shs) & 15u) == 0;
   HGS_HIP(hipSetDevice(device));
-  return launch_hier_trim_apply(*in, *out, tmp, old_of_new, new_of_old, shs16, static_cast<hipStream_t>(stream));
+  return launch_hier_trim_apply(*in, *out, tmp, old_of_new, new_of_old, shs16_ok(in, out), static_cast<hipStream_t>(stream));
 }
 
 // The renderer's SH basis of bands 1..3 at a unit direction (hgs.hierarchy.sh_band_basis), b[0..3), b[3..8), b[8..15).
@@ -793,10 +802,10 @@ static int check_transform_args(const hgs_hier_transform_args* a) {
 int hgs_hier_transform(const hgs_hier_view* in, const hgs_hier_view* out, const hgs_hier_transform_args* args,
                        hgs_stream_t stream, int device) {
   if (!in || !out || !args) { set_error("null argument"); return HGS_ERR_INVALID; }
-  int rc = check_trim_view(in, "input");
-  if (!rc) rc = check_trim_view(out, "output");
+  int rc = check_hier_view(in, "input");
+  if (!rc) rc = check_hier_view(out, "output");
   if (rc) return rc;
-  if (in->G > kHierMergeMaxN) { set_error("bad sizes: G=%lld > 2^31 - 1", (long long)in->G); return HGS_ERR_INVALID; }
+  if (in->G > kHierMaxNodes) { set_error("bad sizes: G=%lld > 2^31 - 1", (long long)in->G); return HGS_ERR_INVALID; }
   if (in->G != out->G || in->N != out->N || in->M != out->M) {
     set_error("bad sizes: input (G=%lld, N=%lld, M=%d) != output (G=%lld, N=%lld, M=%d)", (long long)in->G, (long long)in->N,
               in->M, (long long)out->G, (long long)out->N, out->M);
@@ -818,9 +827,8 @@ int hgs_hier_transform(const hgs_hier_view* in, const hgs_hier_view* out, const 
   }
   rc = check_transform_args(args);
   if (rc) return rc;
-  const bool shs16 = (3 * in->M) % 4 == 0 && (((uintptr_t)in->shs | (uintptr_t)out->shs) & 15u) == 0;
   HGS_HIP(hipSetDevice(device));
-  return launch_hier_transform(*in, *out, *args, shs16, static_cast<hipStream_t>(stream));
+  return launch_hier_transform(*in, *out, *args, shs16_ok(in, out), static_cast<hipStream_t>(stream));
 }
 
 size_t hgs_ssim_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W) {

@@ -13,18 +13,16 @@
 //              Arithmetic in double, contraction off, every sum in the spec's order: the choice and the bits are the spec's.
 //
 // Any numbering works (the builder's BFS, the merger's chunks side by side): only depth and parent are read.
-#include "common.h"
+#include "hier_nodes.h"
 
 #pragma clang fp contract(off)
 
 namespace hgs {
 namespace {
 
-constexpr int kNodeInts = 7;        // depth, parent, start, count_leafs, count_merged, start_children, count_children
 constexpr int kHaThreads = 256;
 constexpr int kMaxDepth = 255;
 constexpr int kLevels = kMaxDepth + 1;
-constexpr uint32_t kNone = 0xffffffffu;
 
 // Device half of the report, read back with the level counts in one copy.
 struct HaResult {
@@ -186,8 +184,8 @@ int launch_hier_align(const int32_t* nodes, int64_t N, float* log_scales, float*
   HaResult host;
   HGS_HIP(hipMemcpyAsync(&host, t.res, sizeof(host), hipMemcpyDeviceToHost, s));
   HGS_HIP(wait_stream(s));
-  for (int c = 0; c < 3; ++c) report->first_bad[c] = host.first_bad[c] == kNone ? -1 : (int32_t)host.first_bad[c];
-  report->first_bad[3] = host.second_root == kNone ? -1 : (int32_t)host.second_root;
+  first_bad_from_minima(host.first_bad, 3, report->first_bad);
+  first_bad_from_minima(&host.second_root, 1, &report->first_bad[3]);
   report->roots = (int32_t)host.counts[0];
   int levels = 0;
   while (levels < kLevels && host.counts[levels]) ++levels;
@@ -195,12 +193,9 @@ int launch_hier_align(const int32_t* nodes, int64_t N, float* log_scales, float*
   report->reserved[0] = report->reserved[1] = 0;
   static const char* const what[4] = {"depth outside [0, 255]", "parent outside [0, N) at a node of depth > 0",
                                       "parent's depth is not the node's depth - 1", "more than one node of depth 0"};
-  for (int c = 0; c < 4; ++c) {
-    if (report->first_bad[c] >= 0) {
-      set_error("not a valid hierarchy: %s (first offending node %d); nothing was changed", what[c], report->first_bad[c]);
-      return HGS_ERR_INVALID;
-    }
-  }
+  if (fail_on_first_bad(report->first_bad, what, 4,
+                        "not a valid hierarchy: %s (first offending node %d); nothing was changed"))
+    return HGS_ERR_INVALID;
   if (host.first_root == kNone) {
     report->roots = 0;
     set_error("not a valid hierarchy: no node of depth 0; nothing was changed");

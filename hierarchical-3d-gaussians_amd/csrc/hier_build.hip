@@ -14,12 +14,11 @@
 // (2^d nodes), level D has 2^D nodes of length 1 or 2 (c = P - 2^D of length 2) and level D + 1 the 2c leaves under
 // them.  On level D the ranges tile [0, P) in order, so the number of length-2 nodes in front of node i is l_i - i:
 // its children's place, no prefix sum.
-#include "common.h"
+#include "hier_nodes.h"
 
 namespace hgs {
 namespace {
 
-constexpr int kNodeInts = 7;        // depth, parent, start, count_leafs, count_merged, start_children, count_children
 constexpr int kMomDoubles = 10;     // mean xyz, covariance xx xy xz yy yz zz, weight w = alpha * s0 * s1 * s2
 constexpr int kShFloats = 48;       // output SH rows are padded to 16 coefficients
 constexpr int kHbThreads = 256;
@@ -103,14 +102,7 @@ struct BuildIn {
   int32_t P, M;
 };
 
-struct BuildOut {
-  float* xyz;
-  float* shs;
-  float* alpha;
-  float* log_scales;
-  float* rots;
-  int32_t* nodes;
-  float* boxes;
+struct BuildOut : HierRows {
   int2* range;                // [l, h) of the sorted leaves under each node
   double* mom;                // [N, kMomDoubles]
 };
@@ -429,7 +421,7 @@ int launch_hier_build(const float* xyz, const float* scales, const float* rots, 
     ++levels;
   }
   const BuildIn in{xyz, scales, rots, opacity, shs, t.order, P, M};
-  const BuildOut out{out_xyz, out_shs, out_alpha, out_log_scales, out_rots, out_nodes, out_boxes, t.range, t.mom};
+  const BuildOut out{{out_xyz, out_shs, out_alpha, out_log_scales, out_rots, out_nodes, out_boxes}, t.range, t.mom};
   // ---- topology and leaves, top-down
   hipLaunchKernelGGL(hb_root_kernel, dim3(1), dim3(64), 0, s, in, out, D == 0);
   HGS_LAUNCH_CHECK("hb_root", s, false);

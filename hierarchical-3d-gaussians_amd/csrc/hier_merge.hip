@@ -5,22 +5,21 @@
 //              its nodes 1..N-1 at base_c .. base_c + N - 2 (base_0 = 1 + k, base_{c+1} = base_c + N_c - 1)
 //   rows       attribute rows and boxes are copied into place (hipMemcpyAsync, host or device source): no kernel
 //   nodes      hm_nodes_kernel: one thread per node remaps depth / parent / start / start_children and validates the
-//              chunk in the same pass (first offending node per check, the children counts summed)
+//              chunk in the same pass (hier_nodes.h's checks: first offending node per check, the children counts summed)
 //   root       hm_root_kernel: one wave computes the root row and box from rows 1..k in double, as the spec
 //
 // Rows at index >= N of a chunk (a skybox tail appended after the node rows) are not read.
-#include "common.h"
+#include "hier_nodes.h"
 
 namespace hgs {
 namespace {
 
-constexpr int kNodeInts = 7;        // depth, parent, start, count_leafs, count_merged, start_children, count_children
 constexpr int kHmThreads = 256;
 constexpr int kHmWaves = kHmThreads / 64;
 constexpr int kChecks = 3;
 
-// Device half of the report: the first offending node per check as an unsigned minimum (0xffffffff = none), and the
-// sum of the children counts.
+// Device half of the report: the first offending node per check as an unsigned minimum (kNone = none), and the sum of
+// the children counts.
 struct HmResult {
   uint32_t first_bad[4];
   unsigned long long children_sum;
@@ -41,23 +40,12 @@ __global__ __launch_bounds__(kHmThreads) void hm_nodes_kernel(const int32_t* __r
   int64_t cc = 0;
   if (i < N) {
     const int32_t* nd = nodes + i * kNodeInts;
-    const int32_t depth = nd[0], parent = nd[1], start = nd[2], leafs = nd[3], merged = nd[4], sc = nd[5];
+    const int32_t depth = nd[0], parent = nd[1], leafs = nd[3], merged = nd[4], sc = nd[5];
     cc = nd[6];
-    const bool bad_row = start != i || (int64_t)leafs + merged != 1;
-    bool bad_parent;
-    if (i == 0) {
-      bad_parent = parent != -1;
-    } else if (parent < 0 || parent >= N) {
-      bad_parent = true;
-    } else {
-      const int32_t* pn = nodes + (int64_t)parent * kNodeInts;
-      const int64_t ps = pn[5], pc = pn[6];
-      bad_parent = !(i >= ps && i < ps + pc);
-    }
-    const bool bad_children = cc < 0 || (cc > 0 && (sc < 1 || (int64_t)sc + cc > N));
-    if (bad_row) atomicMin(&res->first_bad[0], (uint32_t)i);
-    if (bad_children) atomicMin(&res->first_bad[1], (uint32_t)i);
-    if (bad_parent) atomicMin(&res->first_bad[2], (uint32_t)i);
+    const uint32_t v = node_layout(nodes, i, N);
+    if (v & kBadRow) atomicMin(&res->first_bad[0], (uint32_t)i);
+    if (v & kBadChildren) atomicMin(&res->first_bad[1], (uint32_t)i);
+    if (v & kBadParent) atomicMin(&res->first_bad[2], (uint32_t)i);
     auto remap = [&](int64_t id) { return (int32_t)(id == 0 ? (int64_t)root_slot : base + id - 1); };
     const int64_t id = remap(i);
     int32_t* o = out + id * kNodeInts;
@@ -80,16 +68,6 @@ __global__ __launch_bounds__(kHmThreads) void hm_nodes_kernel(const int32_t* __r
   }
 }
 
-struct RootRows {
-  float* xyz;
-  float* shs;
-  float* alpha;
-  float* log_scales;
-  float* rots;
-  int32_t* nodes;
-  float* boxes;
-};
-
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -107,7 +85,7 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 // the spec's weight of chunk root r: clamp_min(alpha * s0 * s1 * s2, 1e-30), s = exp(log_scales) in double
-__device__ __forceinline__ double root_weight(const RootRows& m, int64_t r) {
+__device__ __forceinline__ double root_weight(const HierRows& m, int64_t r) {
   const double s0 = exp((double)m.log_scales[r * 3 + 0]), s1 = exp((double)m.log_scales[r * 3 + 1]),
                s2 = exp((double)m.log_scales[r * 3 + 2]);
   return fmax((double)m.alpha[r] * ((s0 * s1) * s2), 1e-30);
@@ -115,7 +93,7 @@ __device__ __forceinline__ double root_weight(const RootRows& m, int64_t r) {
 
 // One wave: node 0's row and box from the chunk roots at rows 1..k (merge_hierarchies' formulas, in double; the sums
 // run in another order than torch's, so the row agrees to float32 rounding).
-__global__ __launch_bounds__(64) void hm_root_kernel(RootRows m, int32_t k, int32_t M) {
+__global__ __launch_bounds__(64) void hm_root_kernel(HierRows m, int32_t k, int32_t M) {
 #pragma clang fp contract(off)
   const int lane = threadIdx.x;
   double W = 0.0;
@@ -230,16 +208,14 @@ int launch_hier_merge_place(const hgs_hier_view& chunk, int32_t index, int64_t b
   HmResult host;
   HGS_HIP(hipMemcpyAsync(&host, res, sizeof(host), hipMemcpyDeviceToHost, s));
   HGS_HIP(hipStreamSynchronize(s));
-  for (int c = 0; c < kChecks; ++c)
-    report->first_bad[c] = host.first_bad[c] == 0xffffffffu ? -1 : (int32_t)host.first_bad[c];
+  first_bad_from_minima(host.first_bad, kChecks, report->first_bad);   // (a chunk that fails is the caller's to refuse)
   report->reserved = 0;
   report->children_sum = (int64_t)host.children_sum;
   return HGS_OK;
 }
 
 int launch_hier_merge_root(const hgs_hier_view& merged, int32_t k, hipStream_t s) {
-  const RootRows m{merged.xyz, merged.shs, merged.alpha, merged.log_scales, merged.rots, merged.nodes, merged.boxes};
-  hipLaunchKernelGGL(hm_root_kernel, dim3(1), dim3(64), 0, s, m, k, merged.M);
+  hipLaunchKernelGGL(hm_root_kernel, dim3(1), dim3(64), 0, s, HierRows::of(merged), k, merged.M);
   HGS_LAUNCH_CHECK("hm_root", s, false);
   return HGS_OK;
 }

@@ -18,24 +18,15 @@
 //
 // In place (an output array == the input array) or out of place (no overlap): a workgroup reads its rows before it
 // writes them, and no workgroup touches another's rows.  No workspace, no host wait.
-#include "common.h"
+#include "hier_nodes.h"
 
 #pragma clang fp contract(off)
 
 namespace hgs {
 namespace {
 
-constexpr int kNodeInts = 7;
 constexpr int kTfThreads = 256;
 constexpr int kTfRows = 128;          // rows per workgroup of the row kernel
-
-struct TfIn {
-  const float* xyz; const float* shs; const float* alpha; const float* log_scales; const float* rots;
-  const int32_t* nodes; const float* boxes;
-};
-struct TfOut {
-  float* xyz; float* shs; float* alpha; float* log_scales; float* rots; int32_t* nodes; float* boxes;
-};
 
 // Band L of one (row, channel) column in LDS, in place: p -> coefficient 0 of the channel, 3 words between coefficients.
 template <int L>
@@ -54,8 +45,8 @@ __device__ __forceinline__ void tf_band(float* p, const double* D) {
 }
 
 template <int M>
-__global__ __launch_bounds__(kTfThreads) void tf_rows_kernel(TfIn in, TfOut out, int64_t G, hgs_hier_transform_args a,
-                                                             int shs16) {
+__global__ __launch_bounds__(kTfThreads) void tf_rows_kernel(HierRowsIn in, HierRows out, int64_t G,
+                                                             hgs_hier_transform_args a, int shs16) {
   constexpr int W = 3 * M, kStride = W | 1;
   __shared__ float sh[M == 1 ? 1 : kTfRows * kStride];
   const int64_t r0 = (int64_t)blockIdx.x * kTfRows;
@@ -136,7 +127,7 @@ __global__ __launch_bounds__(kTfThreads) void tf_rows_kernel(TfIn in, TfOut out,
   }
 }
 
-__global__ __launch_bounds__(kTfThreads) void tf_boxes_kernel(TfIn in, TfOut out, int64_t N, hgs_hier_transform_args a) {
+__global__ __launch_bounds__(kTfThreads) void tf_boxes_kernel(HierRowsIn in, HierRows out, int64_t N, hgs_hier_transform_args a) {
   const int64_t n0 = (int64_t)blockIdx.x * kTfThreads;
   const int64_t i = n0 + threadIdx.x;
   if (i < N) {
@@ -168,8 +159,8 @@ __global__ __launch_bounds__(kTfThreads) void tf_boxes_kernel(TfIn in, TfOut out
 
 int launch_hier_transform(const hgs_hier_view& in, const hgs_hier_view& out, const hgs_hier_transform_args& a, bool shs16,
                           hipStream_t s) {
-  const TfIn i{in.xyz, in.shs, in.alpha, in.log_scales, in.rots, in.nodes, in.boxes};
-  const TfOut o{out.xyz, out.shs, out.alpha, out.log_scales, out.rots, out.nodes, out.boxes};
+  const HierRowsIn i = HierRowsIn::of(in);
+  const HierRows o = HierRows::of(out);
   const int64_t G = in.G, N = in.N;
   const dim3 grid((unsigned)((G + kTfRows - 1) / kTfRows)), block(kTfThreads);
   const int s16 = shs16 ? 1 : 0;

@@ -6,11 +6,11 @@
 //              the kept nodes are copied in ascending old order, node records renumbered.
 //   plan       ht_plan_kernel: one thread per node reads its record, its own box and its parent's (the grandparent's only
 //              for the closure check of a kept node), evaluates test, the keep flag, the three layout checks of the merger
-//              (restated here: hier_merge.hip stays as it is) and the closure check (first offending node per check),
-//              and writes the workgroup's keep sum and stub sum; ht_scan_kernel: the chained scan of common.h over the
-//              keep sums, the stub sums added up beside it (one atomic per scan chunk: one per stub wave on a single
-//              word cost 4 ms at 4.2 M stubs); ONE host wait reads back the kept count, the stub count and the checks.
-//              Nothing has been written to any output at that point.
+//              (node_layout of hier_nodes.h, the text hier_merge.hip runs) and the closure check (first offending node
+//              per check), and writes the workgroup's keep sum and stub sum; ht_scan_kernel: the chained scan of
+//              common.h over the keep sums, the stub sums added up beside it (one atomic per scan chunk: one per stub
+//              wave on a single word cost 4 ms at 4.2 M stubs); ONE host wait reads back the kept count, the stub count
+//              and the checks.  Nothing has been written to any output at that point.
 //   apply      asynchronous.  ht_maps_kernel: new_of_old and old_of_new from the flags and the scanned sums;
 //              ht_gather_kernel: one workgroup per kHtRows OUTPUT rows stages their source rows in LDS, then copies tensor
 //              by tensor, one thread per 16-byte piece (shs where 12 M is a multiple of 16 and both bases are aligned,
@@ -19,6 +19,7 @@
 //              set is a run of the old order (under an extent floor it is nearly a prefix of the BFS order).
 //
 // Rows at index >= N of the input (a skybox tail) are not read; rows at index >= N' of the output are not written.
+#include "hier_nodes.h"
 #include "lod_cut.h"   // the workgroup sums and the launcher of the chained scan (the cut rules in it are not used here)
 
 #include <mutex>
@@ -29,7 +30,6 @@ namespace {
 
 constexpr int kHtThreads = 256;
 constexpr int kHtRows = 128;            // output rows per workgroup of the gather
-constexpr uint32_t kNone = 0xffffffffu;
 constexpr uint32_t kKeep = 1u, kTest = 2u;   // bits of a node's flag byte
 
 // Device half of the report (the kept and stub counts are the two words behind the scanned workgroup sums).
@@ -61,29 +61,17 @@ __global__ __launch_bounds__(kHtThreads) void ht_plan_kernel(const int32_t* __re
   uint32_t keep = 0, stub = 0;
   if (i < N) {
     const int32_t* nd = nodes + i * kNodeInts;
-    const int32_t parent = nd[1], start = nd[2], leafs = nd[3], merged = nd[4], sc = nd[5];
+    const int32_t parent = nd[1];
     const int64_t cc = nd[6];
     // ---- the merger's three checks
-    const bool bad_row = start != i || (int64_t)leafs + merged != 1;
-    const bool parent_in_range = i > 0 && parent >= 0 && parent < N;
-    bool bad_parent;
-    if (i == 0) {
-      bad_parent = parent != -1;
-    } else if (!parent_in_range) {
-      bad_parent = true;
-    } else {
-      const int32_t* pn = nodes + (int64_t)parent * kNodeInts;
-      const int64_t ps = pn[5], pc = pn[6];
-      bad_parent = !(i >= ps && i < ps + pc);
-    }
-    const bool bad_children = cc < 0 || (cc > 0 && (sc < 1 || (int64_t)sc + cc > N));
-    if (bad_row) atomicMin(&res->first_bad[0], (uint32_t)i);
-    if (bad_children) atomicMin(&res->first_bad[1], (uint32_t)i);
-    if (bad_parent) atomicMin(&res->first_bad[2], (uint32_t)i);
+    const uint32_t v = node_layout(nodes, i, N);
+    if (v & kBadRow) atomicMin(&res->first_bad[0], (uint32_t)i);
+    if (v & kBadChildren) atomicMin(&res->first_bad[1], (uint32_t)i);
+    if (v & kBadParent) atomicMin(&res->first_bad[2], (uint32_t)i);
     // ---- the rule
     const bool test_self = ht_test(boxes, i, a);
     bool k = i == 0;
-    if (parent_in_range) {
+    if (v & kParentInRange) {
       k = ht_test(boxes, parent, a);
       if (k && parent != 0) {          // closure: a kept node's parent is kept (a bad grandparent index is check [2]'s)
         const int32_t pp = nodes[(int64_t)parent * kNodeInts + 1];
@@ -120,14 +108,6 @@ __global__ __launch_bounds__(kHtThreads) void ht_maps_kernel(const uint8_t* __re
   }
 }
 
-struct HtIn {
-  const float* xyz; const float* shs; const float* alpha; const float* log_scales; const float* rots;
-  const int32_t* nodes; const float* boxes;
-};
-struct HtOut {
-  float* xyz; float* shs; float* alpha; float* log_scales; float* rots; int32_t* nodes; float* boxes;
-};
-
 // rows [r0, r0 + rows) of a tensor of `ppr` pieces of type T per row <- the rows src[0 .. rows) of `in`
 template <typename T>
 __device__ __forceinline__ void ht_copy_rows(T* __restrict__ out, const T* __restrict__ in, const int32_t* src,
@@ -142,7 +122,8 @@ __device__ __forceinline__ void ht_copy_rows(T* __restrict__ out, const T* __res
 }
 
 // One workgroup per kHtRows output rows.  S: 16-byte pieces of an shs row (0: shs goes in W 4-byte pieces).
-__global__ __launch_bounds__(kHtThreads) void ht_gather_kernel(HtIn in, HtOut out, const int32_t* __restrict__ old_of_new,
+__global__ __launch_bounds__(kHtThreads) void ht_gather_kernel(HierRowsIn in, HierRows out,
+                                                               const int32_t* __restrict__ old_of_new,
                                                                const int32_t* __restrict__ new_of_old,
                                                                const uint8_t* __restrict__ flags, int32_t kept,
                                                                uint32_t S, uint32_t W) {
@@ -241,20 +222,16 @@ int launch_hier_trim_plan(const hgs_hier_view& in, const hgs_hier_trim_args& arg
   HGS_HIP(hipMemcpyAsync(&host, t.res, sizeof(host), hipMemcpyDeviceToHost, s));
   HGS_HIP(hipMemcpyAsync(totals, t.block_sums + nblk, sizeof(totals), hipMemcpyDeviceToHost, s));
   HGS_HIP(wait_stream(s));
-  for (int k = 0; k < 4; ++k) report->first_bad[k] = host.first_bad[k] == kNone ? -1 : (int32_t)host.first_bad[k];
+  first_bad_from_minima(host.first_bad, 4, report->first_bad);
   report->kept = (int64_t)totals[0];
   report->stubs = (int64_t)totals[1];
   static const char* const what[4] = {
       "start != node index or count_leafs + count_merged != 1", "children range outside [1, N)",
       "parent outside [0, N) or not claiming the node (node 0: parent != -1)",
       "a kept node under a dropped parent (the boxes do not nest, or the extents grow downwards)"};
-  for (int k = 0; k < 4; ++k) {
-    if (report->first_bad[k] >= 0) {
-      set_error("not a hierarchy that can be trimmed: %s (first offending node %d); nothing was written", what[k],
-                report->first_bad[k]);
-      return HGS_ERR_INVALID;
-    }
-  }
+  if (fail_on_first_bad(report->first_bad, what, 4,
+                        "not a hierarchy that can be trimmed: %s (first offending node %d); nothing was written"))
+    return HGS_ERR_INVALID;
   std::lock_guard<std::mutex> lock(g_ht_mutex);
   if (g_ht_plans.size() >= kHtMaxPlans) g_ht_plans.erase(g_ht_plans.begin());
   g_ht_plans.push_back(HtPlan{device, tmp, N, (int64_t)totals[0]});
@@ -270,11 +247,9 @@ int launch_hier_trim_apply(const hgs_hier_view& in, const hgs_hier_view& out, co
   hipLaunchKernelGGL(ht_maps_kernel, dim3(nblk), dim3(kHtThreads), 0, s, t.flags, t.block_sums, (int32_t)N, (int32_t)kept,
                      old_of_new, new_of_old);
   HGS_LAUNCH_CHECK("ht_maps", s, false);
-  const HtIn i{in.xyz, in.shs, in.alpha, in.log_scales, in.rots, in.nodes, in.boxes};
-  const HtOut o{out.xyz, out.shs, out.alpha, out.log_scales, out.rots, out.nodes, out.boxes};
   const uint32_t W = 3u * (uint32_t)in.M, S = shs16 ? W / 4u : 0u;
-  hipLaunchKernelGGL(ht_gather_kernel, dim3((unsigned)((kept + kHtRows - 1) / kHtRows)), dim3(kHtThreads), 0, s, i, o,
-                     old_of_new, new_of_old, t.flags, (int32_t)kept, S, W);
+  hipLaunchKernelGGL(ht_gather_kernel, dim3((unsigned)((kept + kHtRows - 1) / kHtRows)), dim3(kHtThreads), 0, s,
+                     HierRowsIn::of(in), HierRows::of(out), old_of_new, new_of_old, t.flags, (int32_t)kept, S, W);
   HGS_LAUNCH_CHECK("ht_gather", s, false);
   return HGS_OK;
 }

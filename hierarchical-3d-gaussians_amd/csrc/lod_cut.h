@@ -1,15 +1,15 @@
 // The rules of the hierarchy cut, each ONCE, for the four calls that must agree bit for bit: expand_to_size +
-// get_interpolation_weights (lod.hip), the frustum-culled cut (lod_frustum.hip), the budget-exact cut
-// (lod_budget.hip) and the cut for several views (lod_views.hip).  Included by those four files only.  What decides -- the size of a node, the cull, the weight -- is
-// float32 in a fixed operation order with contraction off (oracle/lod_oracle.py, tests/frustum_spec.py and
-// tests/budget_cut_spec.py restate it); the rest is the shape the calls share: per-node emission counts,
-// workgroup sums, the chained scan of common.h, an emit pass in ascending node order.
+// get_interpolation_weights (lod.hip), the frustum-culled cut (lod_frustum.hip), the budget-exact cut (lod_budget.hip)
+// and the cut for several views (lod_views.hip); hier_trim.hip takes the workgroup sums and the scan launcher from here.
+// The node record is hier_nodes.h's.  What decides -- the size of a node, the cull, the weight -- is float32 in a fixed
+// operation order with contraction off (oracle/lod_oracle.py, tests/frustum_spec.py and tests/budget_cut_spec.py restate
+// it); the rest is the shape the calls share: per-node emission counts, workgroup sums, the chained scan of common.h, an
+// emit pass in ascending node order.
 #pragma once
-#include "common.h"
+#include "hier_nodes.h"   // the node record
 
 namespace hgs {
 
-constexpr int kNodeInts = 7;   // depth,parent,start,count_leafs,count_merged,start_children,count_children
 // boxes: 8 floats per node = min.xyz+extent, max.xyz+pad
 constexpr int kMaxLevels = 64;
 constexpr float kFltMax = 3.4028234663852886e38f;

@@ -22,6 +22,7 @@ Children of a node are contiguous (BFS numbering).
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 import struct
 import time
@@ -180,18 +181,89 @@ def build_hierarchy(scene) -> Hierarchy:
                      nodes=torch.from_numpy(nodes), boxes=torch.from_numpy(boxes))
 
 
+# ---- what the *_gpu wrappers share ----------------------------------------------------------------------------------------
+_ROWS = ("xyz", "shs", "alpha", "log_scales", "rots", "nodes", "boxes")      # the order of hgs_hier_view
+_ROW_WIDTH = {"xyz": 3, "alpha": 1, "log_scales": 3, "rots": 4, "nodes": 7, "boxes": 8}
+
+
+def _need_gpu(who, spec_name, spec_kind="numpy spec", device=None):
+    """-> (libhgs.so, ``device`` or the current GPU); raises without either: the ``*_gpu`` functions have no CPU fallback."""
+    global _lib                 # the binding module, for every helper and wrapper behind this call (not imported at
+    from . import _lib          # module level: tests/golden/make_upstream_golden.py loads this file on its own)
+    lib = _lib.lib()
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{who} needs a GPU (there is no CPU fallback; {spec_name} is the {spec_kind})")
+    return lib, torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+
+
+def _device_rows(h, names, who, in_place_rows=None):
+    """-> the device of ``h.nodes``, after checking that every tensor ``names`` of ``h`` is contiguous, of its dtype (nodes
+    int32, the rest float32) and on that device.  ``in_place_rows`` = N (a tool that rewrites ``h``): each also holds at
+    least N whole rows, and the message says that ``who`` works in place."""
+    dev = h.nodes.device
+    why = "" if in_place_rows is None else f" ({who} works in place)"
+    for name in names:
+        t = getattr(h, name)
+        want = torch.int32 if name == "nodes" else torch.float32
+        if not (t.is_cuda and t.device == dev and t.dtype == want and t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {want} tensor on {dev}{why}")
+        if in_place_rows is not None:
+            width = _ROW_WIDTH[name]
+            if t.numel() % width or t.numel() // width < in_place_rows:
+                raise ValueError(f"{name} has {t.numel()} values; at least {in_place_rows} rows of {width} expected")
+    return dev
+
+
+def _hier_view(h, G, N, M):
+    return _lib.HierView(G, N, M, 0, h.xyz.data_ptr(), h.shs.data_ptr(), h.alpha.data_ptr(), h.log_scales.data_ptr(),
+                         h.rots.data_ptr(), h.nodes.data_ptr(), h.boxes.data_ptr())
+
+
+def _empty_hierarchy(dev, n, shs_shape, alpha_shape=(1,)) -> Hierarchy:
+    """n uninitialised rows and nodes on ``dev``; shs [n, *shs_shape], alpha [n, *alpha_shape]."""
+    e = lambda *shape, dtype=torch.float32: torch.empty(n, *shape, dtype=dtype, device=dev)
+    return Hierarchy(xyz=e(3), shs=e(*shs_shape), alpha=e(*alpha_shape), log_scales=e(3), rots=e(4),
+                     nodes=e(7, dtype=torch.int32), boxes=e(2, 4))
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+class _device_events:
+    """Two device events around the block on the current stream -> the pair.  With ``stats``, a block that ends without
+    raising waits for the second event and stores the milliseconds between them in ``stats[key]``."""
+    __slots__ = ("stats", "key", "pair")
+
+    def __init__(self, stats=None, key=None):
+        self.stats, self.key, self.pair = stats, key, [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+
+    def __enter__(self):
+        self.pair[0].record()
+        return self.pair
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.pair[1].record()
+            if self.stats is not None:
+                self.pair[1].synchronize()
+                self.stats[self.key] = self.pair[0].elapsed_time(self.pair[1])
+
+
+def _raise_first_bad(checks, first_bad, make_error):
+    """A report's ``first_bad`` walked in the order of ``checks``: raises make_error(check, node) at the first offender."""
+    for check, node in zip(checks, first_bad):
+        if node >= 0:
+            raise make_error(check, int(node))
+
+
 def build_hierarchy_gpu(scene, device=None, align=False) -> Hierarchy:
     """``build_hierarchy`` on the GPU (csrc/hier_build.hip, hgs_hier_build): same input (an hgs.synth.Scene of activated
     rows, M in {1, 4, 9, 16} SH coefficients), same topology, numbering and merge rule, a ``Hierarchy`` of tensors on
     ``device`` (default: the current GPU).  nodes, boxes and the leaf rows of xyz / shs / alpha / rots are bit-exact
     against ``build_hierarchy``; interior rows agree to rounding.  ``align`` (opt-in): run
     ``align_hierarchy_gpu`` on the result.  No CPU fallback: raises without libhgs.so or a GPU."""
-    import ctypes as C
-    from . import _lib
-    lib = _lib.lib()
-    if not torch.cuda.is_available():
-        raise RuntimeError("build_hierarchy_gpu needs a GPU (there is no CPU fallback; build_hierarchy is the numpy spec)")
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    lib, dev = _need_gpu("build_hierarchy_gpu", "build_hierarchy", device=device)
     P = int(scene.means3D.shape[0])
     M = int(scene.shs.shape[1])
     if P < 1:
@@ -202,16 +274,13 @@ def build_hierarchy_gpu(scene, device=None, align=False) -> Hierarchy:
     xyz, scales, rots = f(scene.means3D, P, 3), f(scene.scales, P, 3), f(scene.rotations, P, 4)
     opacity, shs = f(scene.opacities, P), f(scene.shs, P, M, 3)
     N = 2 * P - 1
-    e = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
-    out = Hierarchy(xyz=e(N, 3), shs=e(N, 16, 3), alpha=e(N, 1), log_scales=e(N, 3), rots=e(N, 4),
-                    nodes=e(N, 7, dtype=torch.int32), boxes=e(N, 2, 4))
-    tmp = e(lib.hgs_hier_build_tmp_bytes(P), dtype=torch.uint8)
+    out = _empty_hierarchy(dev, N, (16, 3))
+    tmp = torch.empty(lib.hgs_hier_build_tmp_bytes(P), dtype=torch.uint8, device=dev)
     p = _lib.ptr
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.hgs_hier_build(p(xyz), p(scales), p(rots), p(opacity), p(shs), P, M, p(out.xyz), p(out.shs),
-                                      p(out.alpha), p(out.log_scales), p(out.rots), p(out.nodes), p(out.boxes), p(tmp),
-                                      stream, dev.index or 0), "hgs_hier_build")
+        _lib.check(lib.hgs_hier_build(p(xyz), p(scales), p(rots), p(opacity), p(shs), P, M,
+                                      *(p(getattr(out, name)) for name in _ROWS), p(tmp), _stream(dev), dev.index or 0),
+                   "hgs_hier_build")
     return align_hierarchy_gpu(out) if align else out
 
 
@@ -480,12 +549,7 @@ def merge_hierarchies_gpu(sources, device=None, stats=None, align=False) -> Hier
     ``read_s`` (host seconds loading paths) and ``merge_ms`` (device events around the placements and the root).
     ``align`` (opt-in): run ``align_hierarchy_gpu`` on the merged hierarchy once the root is written (``stats`` then
     also receives ``align_ms``).  No CPU fallback: raises without libhgs.so or a GPU."""
-    import ctypes as C
-    from . import _lib
-    lib = _lib.lib()
-    if not torch.cuda.is_available():
-        raise RuntimeError("merge_hierarchies_gpu needs a GPU (there is no CPU fallback; merge_hierarchies is the spec)")
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    lib, dev = _need_gpu("merge_hierarchies_gpu", "merge_hierarchies", "spec", device)
     sources = list(sources)
     k = len(sources)
     if k < 1:
@@ -505,20 +569,12 @@ def merge_hierarchies_gpu(sources, device=None, stats=None, align=False) -> Hier
     bases, N = merge_layout([n for _, n, _ in sizes])
     if N > MERGE_MAX_NODES:
         raise ValueError(f"the merged hierarchy would have {N} nodes; at most 2^31 - 1")
-    e = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
-    out = Hierarchy(xyz=e(N, 3), shs=e(N, M, 3), alpha=e(N, 1), log_scales=e(N, 3), rots=e(N, 4),
-                    nodes=e(N, 7, dtype=torch.int32), boxes=e(N, 2, 4))
-    tmp = e(_lib.HIER_MERGE_TMP_BYTES, dtype=torch.uint8)
-    p = lambda t: t.data_ptr()
-
-    def view(G, n, h):
-        return _lib.HierView(G, n, M, 0, p(h.xyz), p(h.shs), p(h.alpha), p(h.log_scales), p(h.rots), p(h.nodes),
-                             p(h.boxes))
-
-    merged = view(N, N, out)
+    out = _empty_hierarchy(dev, N, (M, 3))
+    tmp = torch.empty(_lib.HIER_MERGE_TMP_BYTES, dtype=torch.uint8, device=dev)
+    merged = _hier_view(out, N, N, M)
     events, read_s = [], 0.0
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _stream(dev)
         for c, (src, path, name) in enumerate(zip(sources, is_path, names)):
             G, n, _ = sizes[c]
             if path:
@@ -538,24 +594,19 @@ def merge_hierarchies_gpu(sources, device=None, stats=None, align=False) -> Hier
                 return t.to(dtype).contiguous()
             h = Hierarchy(xyz=arr(h.xyz), shs=arr(h.shs), alpha=arr(h.alpha), log_scales=arr(h.log_scales),
                           rots=arr(h.rots), nodes=h.nodes.detach().to(dev, torch.int32).contiguous(), boxes=arr(h.boxes))
-            rep = _lib.HierMergeReport()
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            ev[0].record()
-            _lib.check(lib.hgs_hier_merge_place(C.byref(view(G, n, h)), c, k, bases[c], C.byref(merged), p(tmp),
-                                                C.byref(rep), stream, dev.index or 0), f"hgs_hier_merge_place ({name})")
-            ev[1].record()
+            rep, chunk = _lib.HierMergeReport(), _hier_view(h, G, n, M)
+            with _device_events() as ev:
+                _lib.check(lib.hgs_hier_merge_place(C.byref(chunk), c, k, bases[c], C.byref(merged),
+                                                    tmp.data_ptr(), C.byref(rep), stream, dev.index or 0),
+                           f"hgs_hier_merge_place ({name})")
             events.append(ev)
             del h
-            for check, node in zip(MERGE_CHECKS, rep.first_bad):
-                if node >= 0:
-                    raise ChunkValidationError(name, check, int(node))
+            _raise_first_bad(MERGE_CHECKS, rep.first_bad, lambda check, node: ChunkValidationError(name, check, node))
             if rep.children_sum != n - 1:
                 raise ChunkValidationError(name, "children counts do not sum to N - 1", None,
                                            f"they sum to {rep.children_sum}, N = {n}")
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record()
-        _lib.check(lib.hgs_hier_merge_root(C.byref(merged), k, stream, dev.index or 0), "hgs_hier_merge_root")
-        ev[1].record()
+        with _device_events() as ev:
+            _lib.check(lib.hgs_hier_merge_root(C.byref(merged), k, stream, dev.index or 0), "hgs_hier_merge_root")
         events.append(ev)
     align_stats = {}
     if align:
@@ -666,13 +717,17 @@ def alignment_dots(h: Hierarchy):
     return np.abs((q[ids] * q[nodes[ids, 1]]).sum(1))
 
 
-class HierarchyAlignError(ValueError):
-    """A hierarchy ``align_hierarchy_gpu`` rejected (and left untouched): ``check`` (what failed, one of ALIGN_CHECKS)
-    and ``node`` (the first offending node, None when no node has depth 0)."""
+class HierarchyCheckError(ValueError):
+    """A hierarchy a tool rejected: ``check`` (what failed) and ``node`` (the first offending node)."""
 
     def __init__(self, check, node, message):
         super().__init__(message)
         self.check, self.node = check, node
+
+
+class HierarchyAlignError(HierarchyCheckError):
+    """A hierarchy ``align_hierarchy_gpu`` rejected (and left untouched): ``check`` (what failed, one of ALIGN_CHECKS)
+    and ``node`` (the first offending node, None when no node has depth 0)."""
 
 
 def align_hierarchy_gpu(h: Hierarchy, stats=None) -> Hierarchy:
@@ -683,43 +738,25 @@ def align_hierarchy_gpu(h: Hierarchy, stats=None) -> Hierarchy:
     node of depth 0): a hierarchy that fails raises ``HierarchyAlignError`` naming the check and the first offending
     node, and is left untouched.  ``stats`` (a dict, optional) receives ``align_ms`` (device events around the call).
     No CPU fallback: raises without libhgs.so or a GPU."""
-    import ctypes as C
-    from . import _lib
-    lib = _lib.lib()
-    if not torch.cuda.is_available():
-        raise RuntimeError("align_hierarchy_gpu needs a GPU (there is no CPU fallback; align_hierarchy is the numpy spec)")
+    lib, _ = _need_gpu("align_hierarchy_gpu", "align_hierarchy")
     N = int(h.nodes.shape[0])
     if N < 1 or N > ALIGN_MAX_NODES:
         raise ValueError(f"N = {N} nodes; 1 .. 2^31 - 1 expected")
-    dev = h.nodes.device
-    for name, dtype, width in (("nodes", torch.int32, 7), ("log_scales", torch.float32, 3), ("rots", torch.float32, 4)):
-        t = getattr(h, name)
-        if not (t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous {dtype} tensor on {dev} (align_hierarchy_gpu works in place)")
-        if t.numel() % width or t.numel() // width < N:
-            raise ValueError(f"{name} has {t.numel()} values; at least {N} rows of {width} expected")
+    dev = _device_rows(h, ("nodes", "log_scales", "rots"), "align_hierarchy_gpu", in_place_rows=N)
     tmp = torch.empty(lib.hgs_hier_align_tmp_bytes(N), dtype=torch.uint8, device=dev)
     rep = _lib.HierAlignReport()
     rep.first_bad[:] = [-1] * 4              # (a call that fails its size checks does not fill the report)
     p = _lib.ptr
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record()
-        rc = lib.hgs_hier_align(p(h.nodes), N, p(h.log_scales), p(h.rots), p(tmp), C.byref(rep), stream, dev.index or 0)
-        ev[1].record()
-    if rc != 0:
-        msg = lib.hgs_last_error()
-        msg = msg.decode() if msg else "?"
-        for check, node in zip(ALIGN_CHECKS, rep.first_bad):
-            if node >= 0:
-                raise HierarchyAlignError(check, int(node), f"hgs_hier_align: {msg}")
-        if rc == 1 and "no node of depth 0" in msg:
-            raise HierarchyAlignError("no node of depth 0", None, f"hgs_hier_align: {msg}")
-        raise _lib.HgsError(f"hgs_hier_align failed (code {rc}): {msg}", rc)
-    if stats is not None:
-        ev[1].synchronize()
-        stats["align_ms"] = ev[0].elapsed_time(ev[1])
+    with torch.cuda.device(dev), _device_events(stats, "align_ms"):
+        rc = lib.hgs_hier_align(p(h.nodes), N, p(h.log_scales), p(h.rots), p(tmp), C.byref(rep), _stream(dev),
+                                dev.index or 0)
+        if rc != 0:
+            msg = (lib.hgs_last_error() or b"?").decode()
+            _raise_first_bad(ALIGN_CHECKS, rep.first_bad,
+                             lambda check, node: HierarchyAlignError(check, node, f"hgs_hier_align: {msg}"))
+            if rc == 1 and "no node of depth 0" in msg:
+                raise HierarchyAlignError("no node of depth 0", None, f"hgs_hier_align: {msg}")
+            raise _lib.HgsError(f"hgs_hier_align failed (code {rc}): {msg}", rc)
     return h
 
 
@@ -730,13 +767,9 @@ TRIM_MAX_NODES = (1 << 31) - 1
 _FLT_MAX = 3.4028234663852886e38
 
 
-class HierarchyTrimError(ValueError):
+class HierarchyTrimError(HierarchyCheckError):
     """A hierarchy ``trim_hierarchy`` / ``trim_hierarchy_gpu`` rejected (nothing was written): ``check`` (what failed,
     one of TRIM_CHECKS) and ``node`` (the first offending node)."""
-
-    def __init__(self, check, node, message):
-        super().__init__(message)
-        self.check, self.node = check, node
 
 
 @dataclass
@@ -790,8 +823,9 @@ def _trim_test(boxes, e, roi):
     return t
 
 
-def trim_layout_checks(nodes):
-    """The merger's three layout checks on int32 nodes [N,7] (numpy) -> [first offending node or -1] x 3."""
+def layout_check_masks(nodes):
+    """The merger's three layout checks (csrc/hier_nodes.h node_layout, in numpy) on int32 nodes [N,7] -> the offenders
+    of each check, bool [N] x 3: a bad row, a bad children range, a parent that does not claim the node."""
     nd = np.asarray(nodes).astype(np.int64)
     N = nd.shape[0]
     i = np.arange(N)
@@ -802,8 +836,12 @@ def trim_layout_checks(nodes):
     ps, pc = sc[np.where(in_range, parent, 0)], cc[np.where(in_range, parent, 0)]
     bad_parent = ~in_range | ~((i >= ps) & (i < ps + pc))
     bad_parent[0] = parent[0] != -1
-    first = lambda m: int(np.nonzero(m)[0][0]) if m.any() else -1
-    return [first(bad_row), first(bad_children), first(bad_parent)]
+    return bad_row, bad_children, bad_parent
+
+
+def trim_layout_checks(nodes):
+    """``layout_check_masks`` -> [first offending node or -1] x 3."""
+    return [int(np.nonzero(m)[0][0]) if m.any() else -1 for m in layout_check_masks(nodes)]
 
 
 def trim_budget_extent(nodes, boxes, max_nodes, roi=None):
@@ -843,10 +881,9 @@ def trim_hierarchy(h: Hierarchy, min_extent=0.0, roi=None, max_nodes=None) -> Tr
         raise ValueError(f"G = {G} rows, N = {N} nodes; 1 <= N <= G, N <= 2^31 - 1 expected")
     boxes = h.boxes.detach().cpu().numpy().astype(np.float32).reshape(-1, 2, 4)
     assert boxes.shape[0] == N
-    for check, node in zip(TRIM_CHECKS, trim_layout_checks(nodes)):
-        if node >= 0:
-            raise HierarchyTrimError(check, node, f"not a hierarchy that can be trimmed: {check} (first offending node "
-                                                  f"{node}); nothing was written")
+    refuse = lambda check, node: HierarchyTrimError(check, node, f"not a hierarchy that can be trimmed: {check} (first "
+                                                                 f"offending node {node}); nothing was written")
+    _raise_first_bad(TRIM_CHECKS, trim_layout_checks(nodes), refuse)
     if K is not None:
         e = max(e, trim_budget_extent(nodes, boxes, K, roi))
     test = _trim_test(boxes, e, roi)
@@ -856,9 +893,7 @@ def trim_hierarchy(h: Hierarchy, min_extent=0.0, roi=None, max_nodes=None) -> Tr
     grand = parent[np.maximum(parent, 0)]
     open_ = keep & (parent > 0) & ~test[np.maximum(grand, 0)]
     if open_.any():
-        node = int(np.nonzero(open_)[0][0])
-        raise HierarchyTrimError(TRIM_CHECKS[3], node, f"not a hierarchy that can be trimmed: {TRIM_CHECKS[3]} (first "
-                                                       f"offending node {node}); nothing was written")
+        raise refuse(TRIM_CHECKS[3], int(np.nonzero(open_)[0][0]))
     old = np.nonzero(keep)[0]
     new_of_old = np.full(N, -1, dtype=np.int32)
     new_of_old[old] = np.arange(old.size, dtype=np.int32)
@@ -906,21 +941,12 @@ def trim_hierarchy_gpu(h: Hierarchy, min_extent=0.0, roi=None, max_nodes=None, s
     allocated or written then.  ``stats`` (a dict, optional) receives ``trim_ms`` (device events around plan, the
     allocation and apply) and its two parts ``plan_ms`` (plan, its host wait and the allocation) and ``apply_ms``.
     No CPU fallback: raises without libhgs.so or a GPU."""
-    import ctypes as C
-    from . import _lib
-    lib = _lib.lib()
-    if not torch.cuda.is_available():
-        raise RuntimeError("trim_hierarchy_gpu needs a GPU (there is no CPU fallback; trim_hierarchy is the numpy spec)")
+    lib, _ = _need_gpu("trim_hierarchy_gpu", "trim_hierarchy")
     e, roi, K = _trim_params(min_extent, roi, max_nodes)
     G, N, M = _tensor_sizes(h)
     if N < 1 or G < N or N > TRIM_MAX_NODES:
         raise ValueError(f"G = {G} rows, N = {N} nodes; 1 <= N <= G, N <= 2^31 - 1 expected")
-    dev = h.nodes.device
-    for name in ("xyz", "shs", "alpha", "log_scales", "rots", "nodes", "boxes"):
-        t = getattr(h, name)
-        want = torch.int32 if name == "nodes" else torch.float32
-        if not (t.is_cuda and t.device == dev and t.dtype == want and t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous {want} tensor on {dev}")
+    dev = _device_rows(h, _ROWS, "trim_hierarchy_gpu")
     boxes = h.boxes.reshape(-1, 2, 4)
     if K is not None:
         e = max(e, _trim_budget_extent_torch(h.nodes, boxes, K, roi))
@@ -928,37 +954,26 @@ def trim_hierarchy_gpu(h: Hierarchy, min_extent=0.0, roi=None, max_nodes=None, s
     if roi is not None:
         args.roi_lo[:], args.roi_hi[:] = [float(x) for x in roi[0]], [float(x) for x in roi[1]]
     p = lambda t: t.data_ptr()
-    view = lambda g, n, x: _lib.HierView(g, n, M, 0, p(x.xyz), p(x.shs), p(x.alpha), p(x.log_scales), p(x.rots),
-                                         p(x.nodes), p(x.boxes))
     tmp = torch.empty(lib.hgs_hier_trim_tmp_bytes(N), dtype=torch.uint8, device=dev)
     rep = _lib.HierTrimReport()
     rep.first_bad[:] = [-1] * 4              # (a call that fails its size checks does not fill the report)
-    vin = view(G, N, h)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record()
+    vin = _hier_view(h, G, N, M)
+    with torch.cuda.device(dev), _device_events(stats, "trim_ms") as ev:
+        stream = _stream(dev)
         rc = lib.hgs_hier_trim_plan(C.byref(vin), C.byref(args), p(tmp), C.byref(rep), stream, dev.index or 0)
         if rc != 0:
-            msg = lib.hgs_last_error()
-            msg = msg.decode() if msg else "?"
-            for check, node in zip(TRIM_CHECKS, rep.first_bad):
-                if node >= 0:
-                    raise HierarchyTrimError(check, int(node), f"hgs_hier_trim_plan: {msg}")
+            msg = (lib.hgs_last_error() or b"?").decode()
+            _raise_first_bad(TRIM_CHECKS, rep.first_bad,
+                             lambda check, node: HierarchyTrimError(check, node, f"hgs_hier_trim_plan: {msg}"))
             raise _lib.HgsError(f"hgs_hier_trim_plan failed (code {rc}): {msg}", rc)
         n = int(rep.kept)
-        em = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
-        out = Hierarchy(xyz=em(n, 3), shs=em(n, *h.shs.shape[1:]), alpha=em(n, *h.alpha.shape[1:]), log_scales=em(n, 3),
-                        rots=em(n, 4), nodes=em(n, 7, dtype=torch.int32), boxes=em(n, 2, 4))
-        old_of_new, new_of_old = em(n, dtype=torch.int32), em(N, dtype=torch.int32)
+        out = _empty_hierarchy(dev, n, h.shs.shape[1:], h.alpha.shape[1:])
+        old_of_new, new_of_old = (torch.empty(m, dtype=torch.int32, device=dev) for m in (n, N))
         mid = torch.cuda.Event(enable_timing=True)
         mid.record()
-        _lib.check(lib.hgs_hier_trim_apply(C.byref(vin), C.byref(view(n, n, out)), p(tmp), p(old_of_new), p(new_of_old),
-                                           stream, dev.index or 0), "hgs_hier_trim_apply")
-        ev[1].record()
+        _lib.check(lib.hgs_hier_trim_apply(C.byref(vin), C.byref(_hier_view(out, n, n, M)), p(tmp), p(old_of_new),
+                                           p(new_of_old), stream, dev.index or 0), "hgs_hier_trim_apply")
     if stats is not None:
-        ev[1].synchronize()
-        stats["trim_ms"] = ev[0].elapsed_time(ev[1])
         stats["plan_ms"], stats["apply_ms"] = ev[0].elapsed_time(mid), mid.elapsed_time(ev[1])
     stub_ids = ((h.nodes[:, 6][old_of_new.long()] > 0) & (out.nodes[:, 6] == 0)).nonzero().flatten().to(torch.int32)
     return TrimResult(out, old_of_new, new_of_old, float(e), int(rep.stubs), stub_ids)
@@ -1194,39 +1209,18 @@ def transform_hierarchy_gpu(h: Hierarchy, sim: Similarity, inplace=False, stats=
     and ``h`` is returned; otherwise ``h`` is left as it is and a new Hierarchy on the same device is returned.  Every
     output bit equals the spec's.  The call is asynchronous on the current stream.  ``stats`` (a dict, optional)
     receives ``transform_ms`` (device events around the call).  No CPU fallback: raises without libhgs.so or a GPU."""
-    import ctypes as C
-    from . import _lib
-    lib = _lib.lib()
-    if not torch.cuda.is_available():
-        raise RuntimeError("transform_hierarchy_gpu needs a GPU (there is no CPU fallback; transform_hierarchy is the "
-                           "numpy spec)")
+    lib, _ = _need_gpu("transform_hierarchy_gpu", "transform_hierarchy")
     M = _transform_sh_width(h.shs)
     check_similarity(sim)
     G, N = int(h.xyz.shape[0]), int(h.nodes.shape[0])
     if N < 1 or G < N or G > TRANSFORM_MAX_NODES:
         raise ValueError(f"G = {G} rows, N = {N} nodes; 1 <= N <= G <= 2^31 - 1 expected")
-    dev = h.nodes.device
-    for name in ("xyz", "shs", "alpha", "log_scales", "rots", "nodes", "boxes"):
-        t = getattr(h, name)
-        want = torch.int32 if name == "nodes" else torch.float32
-        if not (t.is_cuda and t.device == dev and t.dtype == want and t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous {want} tensor on {dev}")
-    out = h if inplace else Hierarchy(*(torch.empty_like(getattr(h, k)) for k in
-                                        ("xyz", "shs", "alpha", "log_scales", "rots", "nodes", "boxes")))
-    p = lambda t: t.data_ptr()
-    view = lambda x: _lib.HierView(G, N, M, 0, p(x.xyz), p(x.shs), p(x.alpha), p(x.log_scales), p(x.rots), p(x.nodes),
-                                   p(x.boxes))
+    dev = _device_rows(h, _ROWS, "transform_hierarchy_gpu")
+    out = h if inplace else Hierarchy(*(torch.empty_like(getattr(h, name)) for name in _ROWS))
     args = transform_args(sim)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record()
-        _lib.check(lib.hgs_hier_transform(C.byref(view(h)), C.byref(view(out)), C.byref(args), stream, dev.index or 0),
-                   "hgs_hier_transform")
-        ev[1].record()
-    if stats is not None:
-        ev[1].synchronize()
-        stats["transform_ms"] = ev[0].elapsed_time(ev[1])
+    with torch.cuda.device(dev), _device_events(stats, "transform_ms"):
+        _lib.check(lib.hgs_hier_transform(C.byref(_hier_view(h, G, N, M)), C.byref(_hier_view(out, G, N, M)),
+                                          C.byref(args), _stream(dev), dev.index or 0), "hgs_hier_transform")
     return out
 
 
