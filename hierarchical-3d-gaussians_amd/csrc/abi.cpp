@@ -831,6 +831,33 @@ int hgs_hier_transform(const hgs_hier_view* in, const hgs_hier_view* out, const 
   return launch_hier_transform(*in, *out, *args, shs16_ok(in, out), static_cast<hipStream_t>(stream));
 }
 
+size_t hgs_hier_refit_tmp_bytes(int64_t N) {
+  if (N < 1 || N > kHierMaxNodes) return 0;
+  return hier_refit_tmp_bytes(N);
+}
+
+int hgs_hier_refit(const hgs_hier_view* in, float* boxes_out, int32_t leaf_mode, void* tmp, hgs_hier_refit_report* report,
+                   hgs_stream_t stream, int device) {
+  if (!in || !boxes_out || !report) { set_error("null argument"); return HGS_ERR_INVALID; }
+  int rc = check_hier_view(in, "input");
+  if (rc) return rc;
+  if ((uintptr_t)boxes_out & 15u) { set_error("boxes_out must be 16-byte aligned"); return HGS_ERR_INVALID; }
+  // boxes_out is the input's boxes (in place) or does not overlap them
+  const uintptr_t a = (uintptr_t)in->boxes, b = (uintptr_t)boxes_out;
+  const size_t bytes = (size_t)in->N * 32;
+  if (a != b && a < b + bytes && b < a + bytes) {
+    set_error("boxes_out overlaps the input boxes without being the same array");
+    return HGS_ERR_INVALID;
+  }
+  if (leaf_mode < 0 || leaf_mode > 2) { set_error("bad leaf mode %d: 0 (keep), 1 (cube) or 2 (ellipsoid) expected", leaf_mode); return HGS_ERR_INVALID; }
+  if ((rc = check_hier_tmp(tmp))) return rc;
+  for (int k = 0; k < 7; ++k) report->first_bad[k] = -1;
+  report->levels = 0;
+  report->leaves = report->children_sum = 0;
+  HGS_HIP(hipSetDevice(device));
+  return launch_hier_refit(*in, boxes_out, leaf_mode, tmp, report, static_cast<hipStream_t>(stream));
+}
+
 size_t hgs_ssim_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W) {
   if (!ssim_sizes_ok(N, C, H, W)) return 0;
   return ssim_tmp_bytes(N, C, H, W);

@@ -328,6 +328,10 @@ int launch_hier_trim_apply(const hgs_hier_view& in, const hgs_hier_view& out, co
 // shs16: move shs in 16-byte pieces (12 M a multiple of 16, both bases aligned)
 int launch_hier_transform(const hgs_hier_view& in, const hgs_hier_view& out, const hgs_hier_transform_args& a, bool shs16,
                           hipStream_t s);
+// box refit (hier_refit.hip): sizes, pointers, alignment, overlap and the mode checked by the caller (1 <= N <= 2^31 - 1)
+size_t hier_refit_tmp_bytes(int64_t N);
+int launch_hier_refit(const hgs_hier_view& in, float* boxes_out, int32_t mode, void* tmp, hgs_hier_refit_report* report,
+                      hipStream_t s);
 // fused SSIM loss (ssim.hip): ssim_sizes_ok sets the error message; the launches expect sizes it accepted
 bool ssim_sizes_ok(int32_t N, int32_t C, int32_t H, int32_t W);
 size_t ssim_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W);

@@ -89,6 +89,13 @@ class HierTransformArgs(C.Structure):
                 ("t", C.c_double * 3), ("D1", C.c_double * 9), ("D2", C.c_double * 25), ("D3", C.c_double * 49)]
 
 
+class HierRefitReport(C.Structure):
+    _fields_ = [("first_bad", C.c_int32 * 7), ("levels", C.c_int32), ("leaves", C.c_int64), ("children_sum", C.c_int64)]
+
+
+HIER_REFIT_KEEP, HIER_REFIT_CUBE, HIER_REFIT_ELLIPSOID = 0, 1, 2
+
+
 class ResidRows(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("means3D", "shs", "opacities", "scales", "rotations")]
 
@@ -185,6 +192,8 @@ SIGNATURES = {
                                      C.c_int]),
     "hgs_hier_trim_apply": (C.c_int, [C.POINTER(HierView), C.POINTER(HierView), _P, _P, _P, _P, C.c_int]),
     "hgs_hier_transform": (C.c_int, [C.POINTER(HierView), C.POINTER(HierView), C.POINTER(HierTransformArgs), _P, C.c_int]),
+    "hgs_hier_refit_tmp_bytes": (C.c_size_t, [C.c_int64]),
+    "hgs_hier_refit": (C.c_int, [C.POINTER(HierView), _P, C.c_int32, _P, C.POINTER(HierRefitReport), _P, C.c_int]),
     "hgs_ssim_tmp_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "hgs_ssim_fwd": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int]),
     "hgs_ssim_bwd": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,

@@ -12,7 +12,9 @@ and scales in the frame closest to its parent's, opt-in.  ``trim_hierarchy`` (th
 (the same rule on the device, behind ``python -m hgs.trim_hierarchy``) make a smaller copy: a detail floor, a region, a
 node budget.  ``transform_hierarchy`` (the numpy spec) and ``transform_hierarchy_gpu`` (the same rule on the device, behind
 ``python -m hgs.transform_hierarchy``) move a hierarchy to another frame by a similarity ``similarity(...)`` builds: means,
-rotations, scales, boxes and SH bands follow; ``transform_camera`` moves a camera with it.
+rotations, scales, boxes and SH bands follow; ``transform_camera`` moves a camera with it.  ``refit_boxes`` (the numpy
+spec) and ``refit_boxes_gpu`` (the same rule on the device, behind ``python -m hgs.refit_hierarchy`` and ``--refit`` on the
+transform command) derive every box again from the rows: leaves first, parents as unions of their children.
 Layout = DESIGN.md '.hier layout':
 
   one Gaussian per node, Gaussian index == node index (``start`` = node id)
@@ -1240,3 +1242,175 @@ def transform_camera(cam, sim: Similarity):
     setattr(out, "camera_center", torch.from_numpy(sim.apply(c.detach().cpu().double().numpy()))
             .to(dtype=c.dtype, device=c.device))
     return out
+
+
+# ---- box refit: every box again from the rows it encloses, leaves first, parents as unions ---------------------------------
+# hgs_hier_refit_report.first_bad, in the order they are reported: the merger's three layout checks, the depth checks of
+# the aligner, the leaf boxes
+REFIT_CHECKS = MERGE_CHECKS + ("depth outside [0, 255]",
+                               "depth is not the parent's depth + 1 (without a parent in [0, N): depth != 0)",
+                               "more than one node of depth 0",
+                               "a leaf whose box is not finite or has lo > hi")
+REFIT_CHILDREN_SUM = "count_children does not sum to N - 1 (two nodes claim the same children)"
+REFIT_LEAF_MODES = {"keep": 0, "cube": 1, "ellipsoid": 2}      # hgs_hier_refit's leaf_mode
+REFIT_MAX_NODES = (1 << 31) - 1
+
+
+class HierarchyRefitError(HierarchyCheckError):
+    """A hierarchy ``refit_boxes`` / ``refit_boxes_gpu`` rejected (nothing was written): ``check`` (what failed, one of
+    REFIT_CHECKS or REFIT_CHILDREN_SUM) and ``node`` (the first offending node, None for the children sum)."""
+
+
+def _refit_mode(leaf):
+    if leaf not in REFIT_LEAF_MODES:
+        raise ValueError(f"leaf = {leaf!r}; one of {', '.join(REFIT_LEAF_MODES)} expected")
+    return REFIT_LEAF_MODES[leaf]
+
+
+def leaf_boxes(xyz, log_scales, rots, mode, round32=True):
+    """The leaf rule of ``refit_boxes`` on float32 numpy rows -> (lo [n,3], hi [n,3]), float32 (``round32=False``: the
+    float64 values before their one rounding).  With s_k = exp(double(log_scales_k)): ``"cube"``: e = 3 max_k s_k,
+    lo = x - e, hi = x + e (the builder's leaf rule on the stored rows); ``"ellipsoid"``: q^ = q / |q| with |q| =
+    sqrt(((w w + x x) + y y) + z z), R = _rot_from_quat(q^), h_a = 3 sqrt(((R_a0 R_a0) s_0^2 + (R_a1 R_a1) s_1^2) +
+    (R_a2 R_a2) s_2^2), lo = x - h, hi = x + h: the AABB of the 3 sigma ellipsoid.  Float64, every sum left to right.
+    A NaN or inf row gives a box that is not finite; so does a zero quaternion under ``"ellipsoid"``."""
+    if mode not in ("cube", "ellipsoid"):
+        raise ValueError(f"mode = {mode!r}; cube or ellipsoid expected")
+    x = np.asarray(xyz, dtype=np.float32).reshape(-1, 3).astype(np.float64)
+    with np.errstate(all="ignore"):
+        s = np.exp(np.asarray(log_scales, dtype=np.float32).reshape(-1, 3).astype(np.float64))
+        if mode == "cube":
+            h = (3.0 * s.max(axis=1))[:, None]                 # (np.max propagates a NaN)
+        else:
+            q = np.asarray(rots, dtype=np.float32).reshape(-1, 4).astype(np.float64)
+            n = np.sqrt(((q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1]) + q[:, 2] * q[:, 2]) + q[:, 3] * q[:, 3])
+            R = _rot_from_quat(q / n[:, None])
+            v = s * s
+            h = 3.0 * np.sqrt(((R[:, :, 0] * R[:, :, 0]) * v[:, None, 0] + (R[:, :, 1] * R[:, :, 1]) * v[:, None, 1])
+                              + (R[:, :, 2] * R[:, :, 2]) * v[:, None, 2])
+        lo, hi = x - h, x + h
+        return (lo.astype(np.float32), hi.astype(np.float32)) if round32 else (lo, hi)
+
+
+def _box_extent(lo, hi):
+    """boxes[:,0,3] of float32 (lo, hi): the largest edge, a float32 subtraction, as the builder computes it."""
+    with np.errstate(all="ignore"):
+        e = hi - lo
+    return np.maximum(np.maximum(e[:, 0], e[:, 1]), e[:, 2])
+
+
+def refit_first_bad(nodes, leaf_lo, leaf_hi):
+    """The seven checks of ``refit_boxes`` on int32 nodes [N,7] and the float32 boxes (lo [N,3], hi [N,3]) its leaves
+    are about to get (rows of other nodes are ignored) -> ([first offending node or -1] x 7 in the order of
+    REFIT_CHECKS, the sum of count_children over the valid children ranges)."""
+    nd = np.asarray(nodes).astype(np.int64)
+    N = nd.shape[0]
+    i = np.arange(N)
+    depth, parent, cc = nd[:, 0], nd[:, 1], nd[:, 6]
+    masks = list(layout_check_masks(nodes))
+    masks.append((depth < 0) | (depth > 255))
+    in_range = (parent >= 0) & (parent < N)
+    masks.append((depth != 0) & (~in_range | (depth[np.where(in_range, parent, 0)] != depth - 1)))
+    roots = i[depth == 0]
+    second = np.zeros(N, dtype=bool)
+    second[roots[1:2]] = True
+    masks.append(second)
+    with np.errstate(all="ignore"):
+        ok = np.isfinite(leaf_lo).all(1) & np.isfinite(leaf_hi).all(1) & (leaf_lo <= leaf_hi).all(1)
+    masks.append((cc == 0) & ~ok)
+    first = [int(np.nonzero(m)[0][0]) if m.any() else -1 for m in masks]
+    return first, int(cc[~masks[1]].sum())
+
+
+def refit_boxes(h: Hierarchy, leaf="cube") -> Hierarchy:
+    """Every box again from the rows it is meant to enclose (the float64 numpy spec; ``refit_boxes_gpu`` is the same
+    rule on the device).  Only ``boxes`` changes: the five row tensors, ``nodes`` and rows at index >= N come back bit
+    for bit.  A leaf (count_children == 0) by ``leaf``: ``"keep"`` its input box, all eight floats; ``"cube"`` or
+    ``"ellipsoid"`` the box ``leaf_boxes`` gives its row.  A node with children: lo = min, hi = max over the FINAL boxes
+    of its children [start_children, start_children + count_children), children before parents; its own Gaussian is
+    not included (the builder's and the merger's rule).  Every written box: boxes[n,0,3] = max_a (hi_a - lo_a) in
+    float32 on the rounded values; boxes[n,1,3] is copied.  The result nests exactly (min, max and rounding are
+    monotone); ``"keep"`` returns the bits of a hierarchy this package built or merged.
+    Refused with ``HierarchyRefitError`` (check, first offending node), all before anything is computed: the three
+    layout checks, a depth outside [0, 255], a depth that is not the parent's + 1, a second node of depth 0, a leaf
+    whose box is not finite or has lo > hi (NaN or inf rows, a zero quaternion under ``"ellipsoid"``, a bad kept box
+    under ``"keep"``), and a count_children sum other than N - 1.  -> a new Hierarchy (host)."""
+    _refit_mode(leaf)
+    nodes = h.nodes.detach().cpu().numpy().astype(np.int32)
+    N, G = nodes.shape[0], int(h.xyz.shape[0])
+    if N < 1 or G < N or N > REFIT_MAX_NODES:
+        raise ValueError(f"G = {G} rows, N = {N} nodes; 1 <= N <= G, N <= 2^31 - 1 expected")
+    np32 = lambda v: v.detach().cpu().numpy().astype(np.float32)
+    boxes = np32(h.boxes).reshape(-1, 2, 4)
+    assert boxes.shape[0] == N
+    if leaf == "keep":
+        lo, hi = boxes[:, 0, :3].copy(), boxes[:, 1, :3].copy()
+    else:
+        lo, hi = leaf_boxes(np32(h.xyz)[:N], np32(h.log_scales)[:N], np32(h.rots)[:N], leaf)
+    first_bad, children_sum = refit_first_bad(nodes, lo, hi)
+    refuse = lambda check, node: HierarchyRefitError(check, node, f"not a hierarchy that can be refit: {check} (first "
+                                                                  f"offending node {node}); nothing was written")
+    _raise_first_bad(REFIT_CHECKS, first_bad, refuse)
+    if children_sum != N - 1:
+        raise HierarchyRefitError(REFIT_CHILDREN_SUM, None, f"not a hierarchy that can be refit: count_children sums to "
+                                                            f"{children_sum} over {N} nodes; nothing was written")
+    depth, sc, cc = nodes[:, 0].astype(np.int64), nodes[:, 5].astype(np.int64), nodes[:, 6].astype(np.int64)
+    out = boxes.copy()
+    leaf_ids = np.nonzero(cc == 0)[0]
+    if leaf != "keep":
+        out[leaf_ids, 0, :3], out[leaf_ids, 1, :3] = lo[leaf_ids], hi[leaf_ids]
+        out[leaf_ids, 0, 3] = _box_extent(lo[leaf_ids], hi[leaf_ids])
+    for d in range(int(depth.max()) - 1, -1, -1):              # children before parents
+        ids = np.nonzero((depth == d) & (cc > 0))[0]
+        if ids.size == 0:
+            continue
+        starts = np.concatenate([[0], np.cumsum(cc[ids])[:-1]])
+        kids = np.repeat(sc[ids] - starts, cc[ids]) + np.arange(int(cc[ids].sum()))
+        l = np.minimum.reduceat(out[kids, 0, :3], starts, axis=0)
+        u = np.maximum.reduceat(out[kids, 1, :3], starts, axis=0)
+        out[ids, 0, :3], out[ids, 1, :3] = l, u
+        out[ids, 0, 3] = _box_extent(l, u)
+    cp = lambda v: v.detach().cpu().clone()
+    return Hierarchy(xyz=cp(h.xyz), shs=cp(h.shs), alpha=cp(h.alpha), log_scales=cp(h.log_scales), rots=cp(h.rots),
+                     nodes=cp(h.nodes), boxes=torch.from_numpy(out).reshape(h.boxes.shape))
+
+
+def refit_boxes_gpu(h: Hierarchy, leaf="cube", inplace=False, stats=None, report=None) -> Hierarchy:
+    """``refit_boxes`` on the GPU (csrc/hier_refit.hip, hgs_hier_refit).  ``h``: contiguous device tensors (float32 rows
+    of G >= N, int32 nodes [N,7], boxes [N,2,4]); rows behind the N nodes are neither read nor written.  ``inplace``:
+    ``h.boxes`` is rewritten and ``h`` is returned; otherwise ``h`` is left as it is and the result is a Hierarchy with
+    a new ``boxes`` tensor that SHARES the six other tensors with ``h`` (no row changes, so none is copied).  Interior
+    boxes, extents and kept leaves equal the spec's bit for bit; ``"cube"`` and ``"ellipsoid"`` leaf coordinates are
+    within one float32 ulp of it (the device's double exp may round differently from numpy's).  A hierarchy that fails
+    a check raises ``HierarchyRefitError`` naming the check and the first offending node and is left untouched, in place
+    or out of place.  One host wait (the level sizes and the checks), the rest is asynchronous on the current stream.
+    ``stats`` (a dict, optional) receives ``refit_ms`` (device events around the call), ``levels`` and ``leaves``;
+    ``report`` (optional) a ``_lib.HierRefitReport`` to fill.  No CPU fallback: raises without libhgs.so or a GPU."""
+    lib, _ = _need_gpu("refit_boxes_gpu", "refit_boxes")
+    mode = _refit_mode(leaf)
+    G, N, M = _tensor_sizes(h)
+    if N < 1 or G < N or N > REFIT_MAX_NODES:
+        raise ValueError(f"G = {G} rows, N = {N} nodes; 1 <= N <= G, N <= 2^31 - 1 expected")
+    dev = _device_rows(h, _ROWS, "refit_boxes_gpu")
+    boxes_out = h.boxes if inplace else torch.empty_like(h.boxes)
+    tmp = torch.empty(lib.hgs_hier_refit_tmp_bytes(N), dtype=torch.uint8, device=dev)
+    rep = _lib.HierRefitReport() if report is None else report
+    rep.first_bad[:] = [-1] * 7              # (a call that fails its size checks does not fill the report)
+    p = _lib.ptr
+    with torch.cuda.device(dev), _device_events(stats, "refit_ms"):
+        rc = lib.hgs_hier_refit(C.byref(_hier_view(h, G, N, M)), p(boxes_out), mode, p(tmp), C.byref(rep), _stream(dev),
+                                dev.index or 0)
+        if rc != 0:
+            msg = (lib.hgs_last_error() or b"?").decode()
+            _raise_first_bad(REFIT_CHECKS, rep.first_bad,
+                             lambda check, node: HierarchyRefitError(check, node, f"hgs_hier_refit: {msg}"))
+            if rc == 1 and "count_children sums to" in msg:
+                raise HierarchyRefitError(REFIT_CHILDREN_SUM, None, f"hgs_hier_refit: {msg}")
+            raise _lib.HgsError(f"hgs_hier_refit failed (code {rc}): {msg}", rc)
+    if stats is not None:
+        stats["levels"], stats["leaves"] = int(rep.levels), int(rep.leaves)
+    if inplace:
+        # the library wrote h.boxes behind torch's back: an in-place no-op on an empty view bumps the version counter,
+        # which is what the cached "do these boxes nest?" answer of gaussian_hierarchy._C is keyed on
+        h.boxes.reshape(-1)[:0].zero_()
+    return h if inplace else Hierarchy(h.xyz, h.shs, h.alpha, h.log_scales, h.rots, h.nodes, boxes_out)

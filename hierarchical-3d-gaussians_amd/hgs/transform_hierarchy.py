@@ -2,7 +2,7 @@
 
     python -m hgs.transform_hierarchy <in.hier> <out.hier> [--scale S]
         [--quat w x y z | --axis-angle ax ay az deg | --matrix <16 numbers, row-major, similarity>]
-        [--translate x y z] [--invert] [--half]
+        [--translate x y z] [--invert] [--half] [--refit cube|ellipsoid|keep]
 
 The map is x' = s R x + t (``--invert``: its inverse).  ``--matrix`` takes the 4x4 matrix of column vectors
 [[s R, t], [0 0 0 1]] and replaces --scale, the rotation options and --translate; a matrix with shear, non-uniform
@@ -12,7 +12,9 @@ Steps:
   1. read the file (load_hierarchy: any of the layouts it accepts);
   2. ``hgs.hierarchy.transform_hierarchy_gpu`` in place on the device: every row -- the rows
      behind the node rows (the skybox tail) included -- gets its mean, rotation, scales and SH bands moved, every box
-     becomes the box of the rotated box, node records and opacities are copied;
+     becomes the box of the rotated box, node records and opacities are copied; ``--refit``: then
+     ``hgs.hierarchy.refit_boxes_gpu`` in place with that leaf rule, so that the boxes are tight in the new frame again
+     (a general rotation grows them by up to sqrt 3); without the flag the output is what it was before the flag existed;
   3. write the result (write_hierarchy; ``--half``: its half-precision variant).
 
 ``anchors.bin`` and ``exposure.json`` beside the input hold indices and per-image data, which a change of frame does
@@ -30,9 +32,10 @@ import numpy as np
 import torch
 
 USAGE = ("usage: python -m hgs.transform_hierarchy <in.hier> <out.hier> [--scale S] [--quat w x y z | --axis-angle ax ay az "
-         "deg | --matrix <16 numbers, row-major>] [--translate x y z] [--invert] [--half]   (at least one of --scale, "
+         "deg | --matrix <16 numbers, row-major>] [--translate x y z] [--invert] [--half] [--refit cube|ellipsoid|keep]   (at least one of --scale, "
          "--quat, --axis-angle, --matrix, --translate)")
 SIDE_FILES = ("anchors.bin", "exposure.json")
+REFIT_MODES = ("cube", "ellipsoid", "keep")
 MATRIX_TOL = 1e-6     # how far a typed matrix may be from a similarity; its rotation is then the nearest one (SVD)
 
 
@@ -63,9 +66,10 @@ def similarity_from_matrix(m):
 
 
 def parse_args(argv):
-    """-> dict(in_path, out_path, R or None, quat or None, scale, translate, invert, half), None for a usage error; a
-    --matrix that is not a similarity raises ``NotASimilarity``."""
+    """-> dict(in_path, out_path, R or None, quat or None, scale, translate, invert, half, refit or None), None for a
+    usage error; a --matrix that is not a similarity raises ``NotASimilarity``."""
     pos, scale, quat, axis_angle, matrix, translate, invert, half = [], None, None, None, None, None, False, False
+    refit = None
     take = lambda i, n: [float(x) for x in argv[i + 1:i + 1 + n]] if len(argv) >= i + 1 + n else None
     i = 0
     try:
@@ -91,6 +95,10 @@ def parse_args(argv):
                 invert, i = True, i + 1
             elif a == "--half":
                 half, i = True, i + 1
+            elif a == "--refit":
+                if i + 1 >= len(argv) or argv[i + 1] not in REFIT_MODES:
+                    return None
+                refit, i = argv[i + 1], i + 2
             elif a.startswith("--"):
                 return None
             else:
@@ -119,7 +127,7 @@ def parse_args(argv):
         R, scale, translate = similarity_from_matrix(matrix)
         translate = [float(v) for v in translate]
     return dict(in_path=pos[0], out_path=pos[1], R=R, quat=quat, scale=1.0 if scale is None else float(scale),
-                translate=[0.0, 0.0, 0.0] if translate is None else translate, invert=invert, half=half)
+                translate=[0.0, 0.0, 0.0] if translate is None else translate, invert=invert, half=half, refit=refit)
 
 
 def build_similarity(p):
@@ -131,7 +139,7 @@ def build_similarity(p):
 def run(p) -> dict:
     """Read, transform, write; -> figures of the run."""
     from gaussian_hierarchy._C import load_hierarchy, write_hierarchy
-    from .hierarchy import Hierarchy, transform_hierarchy_gpu
+    from .hierarchy import Hierarchy, refit_boxes_gpu, transform_hierarchy_gpu
     if not torch.cuda.is_available():
         raise RuntimeError("hgs.transform_hierarchy transforms on the GPU; no GPU is visible")
     sim = build_similarity(p)
@@ -147,6 +155,8 @@ def run(p) -> dict:
     h = Hierarchy(*(getattr(host, k).to(dev).contiguous() for k in names))
     stats = {}
     transform_hierarchy_gpu(h, sim, inplace=True, stats=stats)
+    if p.get("refit"):
+        refit_boxes_gpu(h, p["refit"], inplace=True, stats=stats)
     t1 = time.perf_counter()
     out_dir = os.path.dirname(os.path.abspath(out_path))
     os.makedirs(out_dir, exist_ok=True)
@@ -156,7 +166,8 @@ def run(p) -> dict:
     for f in beside:
         if in_dir != out_dir:
             shutil.copyfile(os.path.join(in_dir, f), os.path.join(out_dir, f))
-    return dict(nodes=N, tail=G - N, sim=sim, transform_ms=stats["transform_ms"], read_s=t_read,
+    return dict(nodes=N, tail=G - N, sim=sim, transform_ms=stats["transform_ms"], refit=p.get("refit"),
+                refit_ms=stats.get("refit_ms"), read_s=t_read,
                 write_s=time.perf_counter() - t1, beside=beside, same_dir=in_dir == out_dir, path=out_path)
 
 
@@ -180,6 +191,9 @@ def main(argv=None) -> int:
           f"N = {r['nodes']} nodes, {r['tail']} rows behind the nodes transformed with them, transform "
           f"{r['transform_ms']:.2f} ms on the device (read {r['read_s']:.2f} s, write {r['write_s']:.2f} s) -> {r['path']}",
           flush=True)
+    if r["refit"]:
+        print(f"transform_hierarchy: boxes refit in the new frame (--refit {r['refit']}), {r['refit_ms']:.2f} ms on the "
+              f"device", flush=True)
     for f in r["beside"]:
         how = "stays valid beside the output" if r["same_dir"] else "copied beside the output"
         print(f"transform_hierarchy: {f} holds indices / per-image data, which a change of frame does not touch: {how}",

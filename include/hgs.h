@@ -676,6 +676,49 @@ int hgs_hier_transform(const hgs_hier_view* in, const hgs_hier_view* out, const 
                        hgs_stream_t stream, int device);
 
 /* ---------------------------------------------------------------------------
+ * Refitting a hierarchy's boxes on the device, bottom-up: the rule of hgs.hierarchy.refit_boxes (DESIGN.md section 4
+ * and section 7 f-19).  Only boxes change: the rows, the node records and rows at index >= N are not written (rows at
+ * index >= N are not read).  Input: a hierarchy in this project's layout, G >= N.
+ *   a leaf (count_children == 0), by leaf_mode, with x its xyz and s_k = exp(double(log_scales_k)):
+ *     0 keep       the input box, all eight floats, bit for bit
+ *     1 cube       e = 3 max_k s_k; lo_a = f32(x_a - e), hi_a = f32(x_a + e) (the builder's leaf rule on the stored rows)
+ *     2 ellipsoid  q^ = q / |q| with |q| = sqrt(((w w + x x) + y y) + z z), R the rotation matrix of q^,
+ *                  h_a = 3 sqrt(((R_a0 R_a0) s_0^2 + (R_a1 R_a1) s_1^2) + (R_a2 R_a2) s_2^2); lo_a = f32(x_a - h_a),
+ *                  hi_a = f32(x_a + h_a): the AABB of the 3 sigma ellipsoid
+ *     in double, every sum left to right, no contraction, one rounding to float32
+ *   a node with children: lo = min, hi = max over the FINAL boxes of its children [start_children, start_children +
+ *     count_children), children before parents; its own Gaussian is not included (the builder's and the merger's rule);
+ *     min and max are exact
+ *   every written box: boxes[n,0,3] = max_a (hi_a - lo_a), a float32 subtraction on the rounded values; boxes[n,1,3] is
+ *     copied from the input (a kept leaf keeps its boxes[n,0,3] too)
+ * The output nests exactly: rounding is monotone, and a parent's extent is >= its child's.
+ * boxes_out float [N,2,4]: in->boxes itself (in place) or device memory that does not overlap it.  tmp:
+ * hgs_hier_refit_tmp_bytes(N) of device memory, 256-byte aligned.
+ * hgs_hier_refit_tmp_bytes: host only (no GPU needed); 0 for an N outside [1, 2^31 - 1].
+ * hgs_hier_refit: checked before any HIP call (HGS_ERR_INVALID, hgs_last_error names it): 1 <= N <= 2^31 - 1, N <= G,
+ * M in [1, 64]; every array 4-byte aligned, rots, boxes and boxes_out 16-byte aligned; a boxes_out that overlaps
+ * in->boxes without being that array; a leaf_mode outside {0, 1, 2}.  Then one pass over the nodes validates the
+ * hierarchy and evaluates every leaf's box for its test, a stable 8-bit sort of the node ids by depth gives the level
+ * lists, and ONE host wait reads `report` back.  A failed check returns HGS_ERR_INVALID with the check and its first
+ * offending node in the message and in `report`; nothing has been written to boxes_out then.  After it: a pass over
+ * the leaves and one launch per depth from the deepest level with children up to 0, asynchronous on `stream`. */
+typedef struct hgs_hier_refit_report {
+  int32_t first_bad[7]; /* first offending node per check, -1 if none: [0] start != i or count_leafs + count_merged
+                         * != 1; [1] a children range outside [1, N) or a negative children count; [2] node 0's parent
+                         * != -1, or another node's parent outside [0, N) or not claiming it; [3] depth outside [0, 255];
+                         * [4] a depth that is not the parent's + 1 (without a parent in [0, N): a depth != 0); [5] the
+                         * second node of depth 0; [6] a leaf whose box is not finite or has lo > hi on an axis (NaN or
+                         * inf rows, a zero quaternion under ellipsoid, a bad kept box under keep) */
+  int32_t levels;       /* depths in use, counted from 0 up to the first empty one */
+  int64_t leaves;       /* nodes with count_children == 0 */
+  int64_t children_sum; /* sum of count_children over the valid children ranges: N - 1, or the call is refused (two
+                         * nodes claim the same children) */
+} hgs_hier_refit_report;
+size_t hgs_hier_refit_tmp_bytes(int64_t N);
+int hgs_hier_refit(const hgs_hier_view* in, float* boxes_out, int32_t leaf_mode, void* tmp, hgs_hier_refit_report* report,
+                   hgs_stream_t stream, int device);
+
+/* ---------------------------------------------------------------------------
  * Fused SSIM loss (hgs.loss.ssim): the standard SSIM of the reference's loss -- an 11-tap
  * Gaussian window (sigma 1.5, normalised to sum 1) applied separably, zero padding, C1 = 0.01^2, C2 = 0.03^2 -- of
  * img1 against img2, both float32 [N,C,H,W] contiguous on the device, and its gradient with respect to img1.
