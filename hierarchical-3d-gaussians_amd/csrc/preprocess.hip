@@ -1047,8 +1047,9 @@ __global__ __launch_bounds__(kPreBlock) void k8_presum_work_kernel(const uint2* 
 
 // ---- K8a, phase 1: sum the instance partials (one contiguous run per Gaussian, emission order) -------------------------
 // The runs of a wave's 64 Gaussians lie BACK TO BACK in the scratch (emission order = Gaussian order), ~170 records of
-// 40 bytes: the wave streams that range through LDS with all lanes loading (coalesced, a dozen loads per lane in
-// flight) and every lane then sums its own run out of LDS -- in the same order as before, so the sums keep their bits.
+// 40 bytes: the wave streams that range through LDS with all lanes loading (coalesced; by LDS DMA the whole pass in
+// flight, through registers -- HGS_K8_STAGE=0 -- four loads per lane at a time) and every lane then sums its own run
+// out of LDS -- in the same order as before, so the sums keep their bits.
 // Round 3 had each lane walk its run in global memory: 2.7 dependent round trips per Gaussian on average, the longest
 // run of the wave for everybody, at 3 waves per SIMD (160 registers) to hide them.
 // Two routes per wave:
@@ -1058,10 +1059,75 @@ __global__ __launch_bounds__(kPreBlock) void k8_presum_work_kernel(const uint2* 
 //     sums at the segment's start; the other lanes walk their short runs in global memory (the wave's range is mostly
 //     the long run).
 // `st` is the calling wave's stage (kK8StageRec records).  Every lane of the wave calls (out-of-range lanes with n = 0).
+//
+// Staged (kK8ModeStage, the default): the pass goes into the stage by LDS DMA, every 16-byte piece of it in flight at
+// once and no register in between -- one round trip per pass where the register route takes one per four loads of a
+// lane.  A record is 40 bytes, so a pass starts 8-byte aligned: the DMA starts at the 16-byte boundary at or below it
+// (never in front of `inst`, whose base is 16-byte aligned -- the launcher checks) and the sums read the stage `shift`
+// bytes further in.  A pass is kK8DmaRec records, so that the shift and the last, partial piece fit the stage; the last
+// piece of the last run may reach 8 bytes past the records, inside the extent the workspace's size query rounds up to.
+// A pass boundary changes no bit: each lane still adds its own run in run order.  `off` is offsets[idx], loaded at
+// kernel entry next to tiles_touched (a culled row's word is uninitialised and never used).
 constexpr uint32_t kK8StageRec = 256;                                 // records per wave and pass: 10 KB
-__device__ __forceinline__ void k8_sum_runs(const GeomWs& g, const float* __restrict__ inst, int idx, uint32_t n,
-                                            int presummed, float2* st, double (&s)[10]) {
+constexpr uint32_t kK8StageBytes = kK8StageRec * kInstStride * 4;
+constexpr uint32_t kK8DmaRec = 254;                                   // 8 + 254 x 40 = 10 168 bytes: 636 pieces of 640
+static_assert((8 + kK8DmaRec * kInstStride * 4 + 15) / 16 <= kK8StageBytes / 16,
+              "a DMA pass, shifted, fits the stage in whole 16-byte pieces");
+constexpr int kK8ModePresum = 1, kK8ModeStage = 2, kK8ModeStageIn = 4;   // `mode` of the K8 kernels (launch_preprocess_bwd)
+// what the waves of a workgroup keep behind the four stages: the 64 rows of mean, scales, rotation, opacity and flags
+constexpr uint32_t kK8InWave = 64 * (12 + 12 + 16 + 4 + 4);           // 3 072 bytes per wave
+constexpr uint32_t kK8InMean = 0, kK8InScale = 768, kK8InRot = 1536, kK8InOp = 2560, kK8InFlags = 2816;
+constexpr uint32_t kK8LdsBytes = (kPreBlock / 64) * (kK8StageBytes + kK8InWave);   // 53 248: K8b's output stage at M = 16
+
+// number of 16-byte pieces and the shift of a pass of `cnt` records that starts at record `first` of the scratch
+__host__ __device__ __forceinline__ uint32_t k8_pass_shift(size_t first) { return (uint32_t)((first * (kInstStride * 4)) & 15u); }
+__host__ __device__ __forceinline__ uint32_t k8_pass_pieces(size_t first, uint32_t cnt) {
+  return (k8_pass_shift(first) + cnt * (kInstStride * 4) + 15u) >> 4;
+}
+
+// The wave's 64 rows of every per-Gaussian input into its block `in` of LDS, at kernel entry; k8_chain reads them there.
+// By LDS DMA (five wave-instructions; a wave's slice of a tensor is contiguous and 16-byte aligned when the tensor is),
+// waited for together with the first pass of the records: full waves of aligned tensors (kK8ModeStageIn), so that no
+// piece reaches past row P.  Every other wave -- the last one of a P off the wave grid, a torch view with a storage
+// offset -- loads its rows lane by lane, as the chain would, and every lane writes the row it will read back itself.
+// With a precomputed covariance the scales and rotations are absent and their slots stay unread.
+__device__ __forceinline__ void k8_stage_inputs(const hgs_raster_args& a, const GeomWs& g, int idx, int mode, unsigned char* in) {
+  const int lane = threadIdx.x & 63, wave_first = idx & ~63;
+  const bool sr = !a.cov3D_precomp;
+  if ((mode & kK8ModeStageIn) && wave_first + 64 <= a.P) {             // (wave-uniform)
+    const char* m = reinterpret_cast<const char*>(a.means3D + (size_t)wave_first * 3);
+    const char* o = reinterpret_cast<const char*>(a.opacities + wave_first);
+    const char* f = reinterpret_cast<const char*>(g.flags + wave_first);
+    if (lane < 48) __builtin_amdgcn_global_load_lds((gptr_t)(m + lane * 16), (lptr_t)(in + kK8InMean), 16, 0, 0);
+    if (sr) {
+      const char* sc = reinterpret_cast<const char*>(a.scales + (size_t)wave_first * 3);
+      const char* r = reinterpret_cast<const char*>(a.rotations + (size_t)wave_first * 4);
+      if (lane < 48) __builtin_amdgcn_global_load_lds((gptr_t)(sc + lane * 16), (lptr_t)(in + kK8InScale), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gptr_t)(r + lane * 16), (lptr_t)(in + kK8InRot), 16, 0, 0);
+    }
+    if (lane < 16) {
+      __builtin_amdgcn_global_load_lds((gptr_t)(o + lane * 16), (lptr_t)(in + kK8InOp), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gptr_t)(f + lane * 16), (lptr_t)(in + kK8InFlags), 16, 0, 0);
+    }
+  } else if (idx < a.P) {
+    float* m = reinterpret_cast<float*>(in + kK8InMean) + lane * 3;
+    m[0] = a.means3D[idx * 3 + 0]; m[1] = a.means3D[idx * 3 + 1]; m[2] = a.means3D[idx * 3 + 2];
+    if (sr) {
+      float* sc = reinterpret_cast<float*>(in + kK8InScale) + lane * 3;
+      sc[0] = a.scales[idx * 3 + 0]; sc[1] = a.scales[idx * 3 + 1]; sc[2] = a.scales[idx * 3 + 2];
+      reinterpret_cast<float4*>(in + kK8InRot)[lane] = reinterpret_cast<const float4*>(a.rotations)[idx];
+    }
+    reinterpret_cast<float*>(in + kK8InOp)[lane] = a.opacities[idx];
+    reinterpret_cast<uint32_t*>(in + kK8InFlags)[lane] = g.flags[idx];
+  }
+}
+
+template <bool STG>   // STG: the passes by LDS DMA
+__device__ __forceinline__ void k8_sum_runs(const float* __restrict__ inst, uint32_t off, uint32_t n,
+                                            int mode, float2* st, double (&s)[10]) {
   const int lane = threadIdx.x & 63;
+  const int presummed = mode & kK8ModePresum;
+  constexpr bool dma = STG;
   const unsigned long long long_mask = presummed ? __ballot(n > kK8LongRun) : 0ull;
   if (long_mask == 0ull) {
     uint32_t incl = n;
@@ -1075,30 +1141,45 @@ __device__ __forceinline__ void k8_sum_runs(const GeomWs& g, const float* __rest
     if (total) {                                                       // (wave-uniform)
       const unsigned long long nz = __ballot(n != 0u);
       const int first = __ffsll((long long)nz) - 1;
-      const uint32_t off_mine = n ? g.offsets[idx] : 0u;
-      const size_t base = (size_t)__shfl(off_mine, first, 64);         // (no instances before the first non-empty lane)
-      for (uint32_t c0 = 0; c0 < total; c0 += kK8StageRec) {
-        const uint32_t cn = min(kK8StageRec, total - c0) * 5u;           // float2 words of this pass
-        const float2* src = reinterpret_cast<const float2*>(inst) + (base + c0) * 5;
-        for (uint32_t t0 = 0; t0 < cn; t0 += 64u * 4u) {               // four loads in flight per lane
-          float2 v[4];
+      const size_t base = (size_t)__shfl(n ? off : 0u, first, 64);     // (no instances before the first non-empty lane)
+      const uint32_t pass = dma ? kK8DmaRec : kK8StageRec;
+      for (uint32_t c0 = 0; c0 < total; c0 += pass) {
+        const uint32_t cnt = min(pass, total - c0);
+        uint32_t shift2 = 0;                                           // where record c0 lies in the stage, in float2
+        if (dma) {
+          const uint32_t shift = k8_pass_shift(base + c0), pieces = k8_pass_pieces(base + c0, cnt);
+          const char* src = reinterpret_cast<const char*>(inst) + ((base + c0) * (kInstStride * 4) - shift);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const uint32_t t = t0 + (uint32_t)j * 64u + (uint32_t)lane;
-            v[j] = src[min(t, cn - 1u)];
+          for (uint32_t j = 0; j < kK8StageBytes / 1024; ++j) {        // (a wave-instruction fills 1 KB)
+            const uint32_t piece = j * 64u + (uint32_t)lane;
+            if (piece < pieces)
+              __builtin_amdgcn_global_load_lds((gptr_t)(src + (size_t)piece * 16), (lptr_t)(reinterpret_cast<char*>(st) + j * 1024), 16, 0, 0);
           }
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // (retires the kernel-entry input DMA as well)
+          shift2 = shift >> 3;
+        } else {
+          const uint32_t cn = cnt * 5u;                                // float2 words of this pass
+          const float2* src = reinterpret_cast<const float2*>(inst) + (base + c0) * 5;
+          for (uint32_t t0 = 0; t0 < cn; t0 += 64u * 4u) {             // four loads in flight per lane
+            float2 v[4];
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const uint32_t t = t0 + (uint32_t)j * 64u + (uint32_t)lane;
-            if (t < cn) st[t] = v[j];
+            for (int j = 0; j < 4; ++j) {
+              const uint32_t t = t0 + (uint32_t)j * 64u + (uint32_t)lane;
+              v[j] = src[min(t, cn - 1u)];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const uint32_t t = t0 + (uint32_t)j * 64u + (uint32_t)lane;
+              if (t < cn) st[t] = v[j];
+            }
           }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint32_t k0 = max(my0, c0), k1 = min(my1, c0 + kK8StageRec);
+        const uint32_t k0 = max(my0, c0), k1 = min(my1, c0 + pass);
         for (uint32_t k = k0; k < k1; ++k) {
-          const float2* r = st + (k - c0) * 5u;
+          const float2* r = st + shift2 + (k - c0) * 5u;
           const float2 v0 = r[0], v1 = r[1], v2 = r[2], v3 = r[3], v4 = r[4];
           s[0] += v0.x; s[1] += v0.y; s[2] += v1.x; s[3] += v1.y;
           s[4] += v2.x; s[5] += v2.y; s[6] += v3.x; s[7] += v3.y;
@@ -1109,16 +1190,15 @@ __device__ __forceinline__ void k8_sum_runs(const GeomWs& g, const float* __rest
       }
     }
   } else if (n != 0u) {
-    const size_t off = (size_t)g.offsets[idx];
     if (n > kK8LongRun) {
       const uint32_t nseg = k8_nseg(n);
       for (uint32_t j = 0; j < nseg; ++j) {                              // segment sums, in segment order
-        const double* ps = reinterpret_cast<const double*>(inst + (off + (size_t)j * kK8Seg) * kInstStride);
+        const double* ps = reinterpret_cast<const double*>(inst + ((size_t)off + (size_t)j * kK8Seg) * kInstStride);
 #pragma unroll
         for (int i = 0; i < 10; ++i) s[i] += ps[i];
       }
     } else {
-      const float2* ip = reinterpret_cast<const float2*>(inst) + off * 5;
+      const float2* ip = reinterpret_cast<const float2*>(inst) + (size_t)off * 5;
 #pragma unroll 2
       for (uint32_t k = 0; k < n; ++k) {
         const float2 v0 = ip[k * 5 + 0], v1 = ip[k * 5 + 1], v2 = ip[k * 5 + 2], v3 = ip[k * 5 + 3], v4 = ip[k * 5 + 4];
@@ -1134,16 +1214,33 @@ __device__ __forceinline__ void k8_sum_runs(const GeomWs& g, const float* __rest
 // s: the ten sums of the Gaussian's run.  p: its mean, as loaded.  gr: dL/drgb, clamp-masked (K1's flags) for SH colours,
 // the plain sums for precomputed colours.  The gradients arrive zeroed (cov3D_precomp leaves d_scale and d_rot alone).
 // (separate arrays, not a struct: with a struct K8a took 178 registers instead of 158)
-template <bool LOD>
+// STG: the raw inputs come from `in`, the wave's staged block (k8_stage_inputs, landed); else every value is loaded here,
+// lane by lane.  The staged route applies the activations with the text of load_scale_rot / load_opacity
+// (gaussian_math.h) to the same raw values; tests/test_k8_staged_gpu.py holds the two routes to the same bits.
+template <bool LOD, bool STG>
 __device__ __forceinline__ void k8_chain(const hgs_raster_args& a, const GeomWs& g, int idx, const double (&s)[10],
                                          float (&p)[3], float (&d_mean)[3], float (&d_m2)[3], float& d_op,
-                                         float (&d_scale)[3], float (&d_rot)[4], float (&d_c3)[6], float (&gr)[3]) {
-  CamLds cam;
-  load_camera(a, cam);
+                                         float (&d_scale)[3], float (&d_rot)[4], float (&d_c3)[6], float (&gr)[3],
+                                         const unsigned char* in, const CamLds* cam_entry) {
+  // (STG: the camera was loaded at kernel entry, in front of the DMA -- behind a write to memory the compiler would no
+  // longer take its 35 uniform words by scalar loads, and they would sit in 35 vector registers through the chain)
+  CamLds cam_here;
+  if constexpr (!STG) load_camera(a, cam_here);
+  const CamLds& cam = STG ? *cam_entry : cam_here;
   gr[0] = (float)s[6]; gr[1] = (float)s[7]; gr[2] = (float)s[8];
+  const int lane = threadIdx.x & 63;
+  static_assert(!(LOD && STG), "the LOD route gathers rows by index");
+  constexpr bool staged = STG;
   // ---- recompute the forward projection (double chain; clamp decisions from K1's flags) ----
-  const uint32_t flags = g.flags[idx];
-  load_mean<LOD>(a, lod_row_gather<LOD>(a, idx), p);
+  uint32_t flags;
+  if (staged) {
+    flags = reinterpret_cast<const uint32_t*>(in + kK8InFlags)[lane];
+    const float* m = reinterpret_cast<const float*>(in + kK8InMean) + lane * 3;
+    p[0] = m[0]; p[1] = m[1]; p[2] = m[2];
+  } else {
+    flags = g.flags[idx];
+    load_mean<LOD>(a, lod_row_gather<LOD>(a, idx), p);
+  }
   float q[4] = {1.f, 0.f, 0.f, 0.f};
   float sc[3] = {1.f, 1.f, 1.f};
   double qnorm = 1.0;
@@ -1152,7 +1249,23 @@ __device__ __forceinline__ void k8_chain(const hgs_raster_args& a, const GeomWs&
 #pragma unroll
     for (int i = 0; i < 6; ++i) pd.c3[i] = (double)a.cov3D_precomp[(size_t)idx * 6 + i];
   } else {
-    load_scale_rot<LOD>(a, idx, sc, q, &qnorm);
+    if (staged) {
+      const float* sr = reinterpret_cast<const float*>(in + kK8InScale) + lane * 3;
+      sc[0] = sr[0]; sc[1] = sr[1]; sc[2] = sr[2];
+      if (a.activations & HGS_ACT_SCALE_EXP) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) sc[i] = (float)exp((double)sc[i]);
+      }
+      const float4 qv = reinterpret_cast<const float4*>(in + kK8InRot)[lane];
+      q[0] = qv.x; q[1] = qv.y; q[2] = qv.z; q[3] = qv.w;
+      if (a.activations & HGS_ACT_ROT_NORMALIZE) {
+        const double w = q[0], x = q[1], y = q[2], z = q[3];
+        qnorm = fmax(sqrt(((w * w + x * x) + y * y) + z * z), 1e-12);
+        q[0] = (float)(w / qnorm); q[1] = (float)(x / qnorm); q[2] = (float)(y / qnorm); q[3] = (float)(z / qnorm);
+      }
+    } else {
+      load_scale_rot<LOD>(a, idx, sc, q, &qnorm);
+    }
     cov3d_from_scale_rot_d(sc, a.scale_modifier, q, pd);
   }
   project_gaussian_d(p, cam.vm, cam.pm, a.width, a.height, a.tanfovx, a.tanfovy, (flags & 8u) != 0,
@@ -1275,7 +1388,21 @@ __device__ __forceinline__ void k8_chain(const hgs_raster_args& a, const GeomWs&
   {
     float dod = 1.0f;
     double dact = 1.0;
-    const float o_act = load_opacity<LOD>(a, idx, &dact);
+    float o_act;
+    if (staged) {
+      const float raw = reinterpret_cast<const float*>(in + kK8InOp)[lane];
+      o_act = raw;
+      if (a.activations & HGS_ACT_OPACITY_SIGMOID) {
+        const double o = 1.0 / (1.0 + exp(-(double)raw));
+        dact = o * (1.0 - o);
+        o_act = (float)o;
+      } else if (a.activations & HGS_ACT_OPACITY_ABS) {
+        dact = raw > 0.f ? 1.0 : (raw < 0.f ? -1.0 : 0.0);
+        o_act = fabsf(raw);
+      }
+    } else {
+      o_act = load_opacity<LOD>(a, idx, &dact);
+    }
     float o_rec = o_act;      // the opacity K1 put into the record (same functions, same float)
     if (a.interpolation_weights && a.num_node_kids && !a.lod_per_pixel)
       o_rec = lod_opacity(o_act, a.interpolation_weights[idx], a.num_node_kids[idx], &dod);
@@ -1326,119 +1453,29 @@ __device__ __forceinline__ void k8_store_row(const hgs_raster_grads& out, int id
   }
 }
 
-template <bool ACC, bool LOD>   // ACC: add into the gradient buffers (accumulation over the views of one optimizer step)
+// ACC: add into the gradient buffers (accumulation over the views of one optimizer step).  STG: records and inputs staged
+// by LDS DMA (k8_sum_runs, k8_stage_inputs), the inputs in 12 KB of LDS next to the four stages -- 53 248 bytes together,
+// still three workgroups per compute unit; never with LOD, whose rows are gathered by index.
+// Two kernels over one body (k8a_body.h): preprocess_bwd_kernel<ACC, LOD> (registers) and preprocess_bwd_staged_kernel<ACC>.
+template <bool ACC, bool LOD>
 __global__ __launch_bounds__(kPreBlock) void preprocess_bwd_kernel(hgs_raster_args a, GeomWs g,
                                                                    const float* __restrict__ inst,
                                                                    float* __restrict__ drgb,
                                                                    float* __restrict__ dmean_rows,
                                                                    const uint32_t* __restrict__ lod_flag,
-                                                                   hgs_raster_grads out, int presummed) {
-  const int idx = blockIdx.x * kPreBlock + threadIdx.x;
-  const bool in_range = idx < a.P;
-  const uint32_t n = in_range ? g.tiles_touched[idx] : 0u;   // (out-of-range lanes stay for the wave-wide staging below)
-
-  double s[10];
-#pragma unroll
-  for (int i = 0; i < 10; ++i) s[i] = 0.0;
-  static_assert(kInstStride == 10, "instance record = the ten sums, 40 bytes");
-  __shared__ float2 stage[kPreBlock / 64][kK8StageRec * 5];
-  k8_sum_runs(g, inst, idx, n, presummed, stage[threadIdx.x >> 6], s);
-  if constexpr (!LOD) {
-    if (!in_range) return;
-  }
-
-  float d_mean[3] = {0.f, 0.f, 0.f};
-  float d_m2[3] = {0.f, 0.f, 0.f};
-  float d_op = 0.f;
-  float d_scale[3] = {0.f, 0.f, 0.f};
-  float d_rot[4] = {0.f, 0.f, 0.f, 0.f};
-  float d_c3[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  float gr[3] = {0.f, 0.f, 0.f};
-  float d_col[3] = {0.f, 0.f, 0.f};
-  if (n != 0) {                              // (culled: all-zero gradients; K8b zero-fills dL/dSH)
-    float p[3];
-    k8_chain<LOD>(a, g, idx, s, p, d_mean, d_m2, d_op, d_scale, d_rot, d_c3, gr);
-    // colour: precomputed colours get their gradient here; SH colours hand the clamp-masked dL/drgb to K8b
-    if (a.colors_precomp) {
-      d_col[0] = gr[0]; d_col[1] = gr[1]; d_col[2] = gr[2];
-    } else {
-      drgb[idx * 3 + 0] = gr[0];
-      drgb[idx * 3 + 1] = gr[1];
-      drgb[idx * 3 + 2] = gr[2];
-    }
-  }
-
-  if constexpr (LOD) {
-    if (a.lod_scatter) {
-      // scales, rotations, opacity: scattered here; the mean's gradient goes on to K8b (which adds the view-direction
-      // term and scatters it together with the SH gradients)
-      __shared__ float lds_v[8 * kPreBlock];
-      __shared__ int lds_par[kPreBlock];
-      __shared__ unsigned char lds_vis[kPreBlock];
-      const int t = threadIdx.x;
-      const int block_first = blockIdx.x * kPreBlock;
-      const int count = min(kPreBlock, a.P - block_first);
-      LodRow l;
-      l.r = l.p = 0; l.w = 1.0f; l.u = 0.0f;
-      if (in_range) l = lod_row<true>(a, idx);
-      const bool self = l.p == l.r;
-      const bool vis = in_range && n != 0;
-      const float wn = self ? 1.0f : l.w, u = (self || !vis) ? 0.0f : l.u;
-      float sgn = 1.0f;
-      if (vis && !self && u != 0.0f) {          // (weight 1: nothing goes to the parent, its quaternion is not needed)
-        const float4 qa = reinterpret_cast<const float4*>(a.rotations)[l.r];
-        const float4 qb = reinterpret_cast<const float4*>(a.rotations)[l.p];
-        sgn = (qa.x * qb.x + qa.y * qb.y + qa.z * qb.z + qa.w * qb.w) < 0.0f ? -1.0f : 1.0f;
-      }
-      if (in_range) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          dmean_rows[idx * 3 + j] = d_mean[j];
-          out.dL_dmeans2D[idx * 3 + j] = d_m2[j];
-        }
-      }
-      if (vis) {      // node row (culled rows have zero gradients: the caller's zero fill stands)
-        out.dL_dopacity[l.r] = wn * d_op;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) out.dL_dscales[l.r * 3 + j] = wn * d_scale[j];
-        reinterpret_cast<float4*>(out.dL_drotations)[l.r] = make_float4(wn * d_rot[0], wn * d_rot[1], wn * d_rot[2], wn * d_rot[3]);
-      }
-      lds_par[t] = in_range ? (int)l.p : -1;
-      lds_vis[t] = (vis && !self) ? 1 : 0;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) lds_v[j * kPreBlock + t] = u * d_scale[j];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) lds_v[(3 + j) * kPreBlock + t] = (u * sgn) * d_rot[j];
-      lds_v[7 * kPreBlock + t] = u * d_op;
-      __syncthreads();
-      if (t < count) {
-        const LodRun run = lod_run(a, lds_par, t, count, block_first, *lod_flag != 0u);
-        if (run.leader) {
-          float acc8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-          bool any = false;
-          for (int j = t; j < run.end; ++j) {
-            if (!lds_vis[j]) continue;
-            any = true;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) acc8[k] += lds_v[k * kPreBlock + j];
-          }
-          if (any) {
-            const size_t pp = (size_t)lds_par[t];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) lod_add(out.dL_dscales + pp * 3 + k, acc8[k], run.atomic);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) lod_add(out.dL_drotations + pp * 4 + k, acc8[3 + k], run.atomic);
-            lod_add(out.dL_dopacity + pp, acc8[7], run.atomic);
-          }
-        }
-      }
-      return;
-    }
-    if (!in_range) return;
-  }
-#pragma unroll
-  for (int j = 0; j < 3; ++j) out.dL_dmeans3D[idx * 3 + j] = d_mean[j] + (ACC ? out.dL_dmeans3D[idx * 3 + j] : 0.f);
-  k8_store_row<ACC>(out, idx, d_m2, d_op, d_scale, d_rot, d_c3, d_col);
+                                                                   hgs_raster_grads out, int mode) {
+  constexpr bool STG = false;
+#include "k8a_body.h"
+}
+template <bool ACC>
+__global__ __launch_bounds__(kPreBlock) void preprocess_bwd_staged_kernel(hgs_raster_args a, GeomWs g,
+                                                                          const float* __restrict__ inst,
+                                                                          float* __restrict__ drgb,
+                                                                          float* __restrict__ dmean_rows,
+                                                                          const uint32_t* __restrict__ lod_flag,
+                                                                          hgs_raster_grads out, int mode) {
+  constexpr bool LOD = false, STG = true;
+#include "k8a_body.h"
 }
 
 
@@ -1663,26 +1700,54 @@ __device__ __forceinline__ void k8_add_view_term(const float (&gr)[3], const flo
 // preprocess_bwd_kernel<false, false> and sh_bwd_kernel<false, true, false> compute together, to the bit, without the
 // 64 bytes per Gaussian that only pass between the two (drgb out and in, dL/dmeans3D out, in and out again, the mean and
 // tiles_touched a second time) and without the second launch.
+//   entry    tiles_touched and offsets; each full wave's 64 rows of inputs by LDS DMA into the 12 KB behind the stages
 //   phase 1  the run sums (k8_sum_runs); the waves' stages are the first 40 KB of the dynamic buffer
-//   phase 2  the double chain (k8_chain); every gradient but the SH block is stored from registers
+//   phase 2  the double chain (k8_chain) on the staged inputs, the wave's Jacobian rows landing in its stage meanwhile;
+//            every gradient but the SH block is stored from registers
 //   phase 3  K8b's JAC body on the mean and the masked dL/drgb still in registers (k8_add_view_term); dL/dmeans3D is
 //            written once; then the buffer becomes the [256][3M + 4] output stage (every lane fills its row from b[] and
 //            dL/drgb: no dsh[48] next to the chain) and the SH block leaves as whole lines (coop_store_sh)
 // 160 registers like K8a (the double chain): three waves per SIMD, which three 53 KB buffers per compute unit also allow.
 // No waves-per-SIMD hint: with its 168-register cap the compiler spills 32 bytes, without it it needs 160 and none.
+template <bool STG>   // STG: records, inputs and Jacobians staged by LDS DMA (HGS_K8_STAGE=0: the loads through registers)
 __global__ __launch_bounds__(kPreBlock) void preprocess_bwd_sh_kernel(hgs_raster_args a, GeomWs g,
                                                                          const float* __restrict__ inst,
-                                                                         hgs_raster_grads out, int presummed) {
+                                                                         hgs_raster_grads out, int mode) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int block_first = blockIdx.x * kPreBlock;
   const int idx = block_first + threadIdx.x;
   const bool in_range = idx < a.P;                           // (out-of-range lanes stay: wave-wide staging, barriers)
+  const int wave = threadIdx.x >> 6, wave_first = idx & ~63;
+  unsigned char* st = smem_raw + wave * kK8StageBytes;       // the wave's stage; its inputs lie behind the four stages
+  unsigned char* in = smem_raw + (kPreBlock / 64) * kK8StageBytes + wave * kK8InWave;
+  CamLds cam;                                                // (once, in front of every write to memory: scalar loads)
+  if constexpr (STG) {
+    load_camera(a, cam);
+    k8_stage_inputs(a, g, idx, mode, in);
+  }
   const uint32_t n = in_range ? g.tiles_touched[idx] : 0u;
+  uint32_t off = 0u;
+  if constexpr (STG) { if (in_range) off = g.offsets[idx]; }
+  else { if (n) off = g.offsets[idx]; }
 
   double s[10];
 #pragma unroll
   for (int i = 0; i < 10; ++i) s[i] = 0.0;
-  k8_sum_runs(g, inst, idx, n, presummed, reinterpret_cast<float2*>(smem_raw) + (threadIdx.x >> 6) * (kK8StageRec * 5), s);
+  k8_sum_runs<STG>(inst, off, n, mode, reinterpret_cast<float2*>(st), s);
+  // the wave's stage is free: its 64 Jacobian rows (2 304 contiguous bytes, 16-byte aligned; shjac holds whole waves)
+  // land in it during the double chain
+  const bool jac_staged = STG && wave_first < a.P;           // (wave-uniform)
+  if constexpr (STG) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // (a wave that staged no records: the inputs have landed)
+    if (jac_staged) {
+      const int lane = threadIdx.x & 63;
+      const char* src = reinterpret_cast<const char*>(g.shjac + (size_t)wave_first * kJacStride);
+      static_assert(64 * kJacStride * 4 == 2304, "64 Jacobian rows = 144 pieces of 16 bytes");
+      __builtin_amdgcn_global_load_lds((gptr_t)(src + lane * 16), (lptr_t)st, 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gptr_t)(src + 1024 + lane * 16), (lptr_t)(st + 1024), 16, 0, 0);
+      if (lane < 16) __builtin_amdgcn_global_load_lds((gptr_t)(src + 2048 + lane * 16), (lptr_t)(st + 2048), 16, 0, 0);
+    }
+  }
 
   float d_mean[3] = {0.f, 0.f, 0.f};
   float d_m2[3] = {0.f, 0.f, 0.f};
@@ -1694,20 +1759,32 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_bwd_sh_kernel(hgs_raster
   float b[16];
   const int nb = (a.sh_degree + 1) * (a.sh_degree + 1);
   float p[3];
-  if (n != 0) k8_chain<false>(a, g, idx, s, p, d_mean, d_m2, d_op, d_scale, d_rot, d_c3, gr);
-  if (in_range) {
+  if (n != 0) k8_chain<false, STG>(a, g, idx, s, p, d_mean, d_m2, d_op, d_scale, d_rot, d_c3, gr, in, &cam);
+  // Staged, the rows are stored behind phase 3's arithmetic: a wait for the Jacobian DMA in front of them costs nothing
+  // (it landed during the chain), behind them it would wait for the stores as well -- as the Jacobian loads of the
+  // register route do.
+  constexpr bool stores_last = STG;
+  if (in_range && !stores_last) {
     const float d_col[3] = {0.f, 0.f, 0.f};
     k8_store_row<false>(out, idx, d_m2, d_op, d_scale, d_rot, d_c3, d_col);
   }
   __builtin_amdgcn_sched_barrier(0);                         // (phase 3's loads stay out of the double chain's registers)
+  // every DMA of this wave has landed before its Jacobians are read and before the buffer becomes the output stage
+  if constexpr (STG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (n != 0) {
     float ux, uy, uz;
-    const float inv = unit_dir(p, a.campos, ux, uy, uz);
+    const float inv = unit_dir(p, STG ? cam.cam : a.campos, ux, uy, uz);
     sh_basis(a.sh_degree, ux, uy, uz, b);
-    const float* jp = g.shjac + (size_t)idx * kJacStride;
     float J[9];
+    if (jac_staged) {
+      const float* jl = reinterpret_cast<const float*>(st) + (threadIdx.x & 63) * kJacStride;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) J[k] = jp[k];
+      for (int k = 0; k < 9; ++k) J[k] = jl[k];
+    } else {
+      const float* jp = g.shjac + (size_t)idx * kJacStride;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) J[k] = jp[k];
+    }
     k8_add_view_term(gr, J, ux, uy, uz, inv, d_mean);
   } else {
 #pragma unroll
@@ -1716,6 +1793,10 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_bwd_sh_kernel(hgs_raster
   if (in_range) {
 #pragma unroll
     for (int j = 0; j < 3; ++j) out.dL_dmeans3D[idx * 3 + j] = d_mean[j];
+    if (stores_last) {
+      const float d_col[3] = {0.f, 0.f, 0.f};
+      k8_store_row<false>(out, idx, d_m2, d_op, d_scale, d_rot, d_c3, d_col);
+    }
   }
 
   float* lds = reinterpret_cast<float*>(smem_raw);
@@ -2053,8 +2134,9 @@ int launch_preprocess_bwd(const hgs_raster_args& a, const GeomWs& g, const BwdWs
                           hipStream_t s) {
   const int nblk = (a.P + kPreBlock - 1) / kPreBlock;
   if (nblk > 0) {
-    // long runs first, when the frame has them: mean run above 6 records (L > 6 P; HGS_K8_PRESUM=0 / 1 forces)
-    static const char* force = getenv("HGS_K8_PRESUM");
+    // long runs first, when the frame has them: mean run above 6 records (L > 6 P; HGS_K8_PRESUM=0 / 1 forces; read on
+    // every call, like the two switches below)
+    const char* force = getenv("HGS_K8_PRESUM");
     const bool presum = force ? force[0] == '1' : (uint64_t)L > 6ull * (uint64_t)a.P;
     if (presum) {
       HGS_HIP(hipMemsetAsync(w.work_counter, 0, sizeof(uint32_t), s));
@@ -2066,23 +2148,36 @@ int launch_preprocess_bwd(const hgs_raster_args& a, const GeomWs& g, const BwdWs
                          s, w.work, w.work_counter, g.tiles_touched, g.offsets, w.inst_grads);
       HGS_LAUNCH_CHECK("preprocess_bwd_long_runs", s, a.debug);
     }
+    // LDS DMA staging (k8_sum_runs, k8_stage_inputs; HGS_K8_STAGE=0 keeps the loads through registers; read on every
+    // call): the kernels' STG forms when the scratch and the Jacobians are 16-byte aligned and the rows are not gathered
+    // by index; in them the per-Gaussian inputs by DMA when every one of their tensors is aligned (a torch view with a
+    // storage offset is not; scales and rotations are absent with a precomputed covariance)
+    const char* stage_env = getenv("HGS_K8_STAGE");
+    const auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+    int mode = presum ? kK8ModePresum : 0;
+    if (!(stage_env && stage_env[0] == '0') && !a.lod_render_indices && al16(w.inst_grads) && al16(g.shjac)) {
+      mode |= kK8ModeStage;
+      if (al16(a.means3D) && al16(a.scales) && al16(a.rotations) && al16(a.opacities) && al16(g.flags)) mode |= kK8ModeStageIn;
+    }
+    const bool stg = (mode & kK8ModeStage) != 0;
     // the drop-in training call: K8a and K8b as one kernel (HGS_K8_FUSE=0 keeps them apart; read on every call)
     const char* fuse_env = getenv("HGS_K8_FUSE");
     const bool fused = !(fuse_env && fuse_env[0] == '0') && !a.lod_render_indices && !a.accumulate_grads &&
                        !a.defer_sh_bwd && a.shs && !a.shs_rest && out.dL_dshs && a.prepare_backward && !a.colors_precomp &&
                        ((a.M * 3) & 3) == 0;
-    if (fused) {                       // one dynamic LDS buffer: the four waves' run stages, then the output stage
-      const size_t stage_bytes = (size_t)(kPreBlock / 64) * kK8StageRec * 5 * sizeof(float2);
+    if (fused) {       // one dynamic LDS buffer: the four waves' run stages and staged inputs, then the output stage
+      const size_t stage_bytes = kK8LdsBytes;
       const size_t rows_bytes = (size_t)kPreBlock * (a.M * 3 + 4) * sizeof(float);
-      hipLaunchKernelGGL(preprocess_bwd_sh_kernel, dim3(nblk), dim3(kPreBlock),
-                         stage_bytes > rows_bytes ? stage_bytes : rows_bytes, s, a, g, w.inst_grads, out, presum ? 1 : 0);
+      hipLaunchKernelGGL(stg ? preprocess_bwd_sh_kernel<true> : preprocess_bwd_sh_kernel<false>, dim3(nblk), dim3(kPreBlock),
+                         stage_bytes > rows_bytes ? stage_bytes : rows_bytes, s, a, g, w.inst_grads, out, mode);
       HGS_LAUNCH_CHECK("preprocess_bwd_sh", s, a.debug);
       return HGS_OK;
     }
     auto k8a = a.lod_render_indices ? preprocess_bwd_kernel<false, true>      // (accumulation is refused with lod, abi.cpp)
-                                    : (a.accumulate_grads ? preprocess_bwd_kernel<true, false> : preprocess_bwd_kernel<false, false>);
+               : stg ? (a.accumulate_grads ? preprocess_bwd_staged_kernel<true> : preprocess_bwd_staged_kernel<false>)
+                     : (a.accumulate_grads ? preprocess_bwd_kernel<true, false> : preprocess_bwd_kernel<false, false>);
     hipLaunchKernelGGL(k8a, dim3(nblk), dim3(kPreBlock), 0, s, a, g, w.inst_grads, w.drgb, w.dmean_rows, w.lod_flag, out,
-                       presum ? 1 : 0);
+                       mode);
     HGS_LAUNCH_CHECK("preprocess_bwd", s, a.debug);
     if (a.shs && out.dL_dshs && !a.defer_sh_bwd) {
       const size_t lds_bytes = (size_t)kPreBlock * (a.M * 3 + 4) * sizeof(float);
