@@ -583,6 +583,7 @@ int hgs_sort_pairs(const uint64_t* keys_in, const uint32_t* vals_in, uint64_t* k
 
 constexpr int32_t kHierBuildMaxP = 1 << 30;
 constexpr int64_t kHierMaxNodes = 0x7fffffff;   // merge, align, trim and transform: node indices are int32
+constexpr int64_t kHierReachMaxRegions = 1 << 24;   // view regions of one hgs_hier_reach call
 
 // The workspace pointer of a hierarchy call: there, and kAlign-aligned (those workspaces are carved without slack).
 static int check_hier_tmp(const void* tmp) {
@@ -708,7 +709,40 @@ int hgs_hier_trim_plan(const hgs_hier_view* in, const hgs_hier_trim_args* args, 
   for (int k = 0; k < 4; ++k) report->first_bad[k] = -1;
   report->kept = report->stubs = 0;
   HGS_HIP(hipSetDevice(device));
-  return launch_hier_trim_plan(*in, *args, tmp, report, static_cast<hipStream_t>(stream), device);
+  return launch_hier_trim_plan(*in, *args, nullptr, 0.0f, tmp, report, static_cast<hipStream_t>(stream), device);
+}
+
+int hgs_hier_trim_plan_keyed(const hgs_hier_view* in, const hgs_hier_trim_args* args, const float* key, float key_floor,
+                             void* tmp, hgs_hier_trim_report* report, hgs_stream_t stream, int device) {
+  if (!in || !args || !report || !key) { set_error("null argument"); return HGS_ERR_INVALID; }
+  int rc = check_hier_view(in, "input");
+  if (rc) return rc;
+  if ((uintptr_t)key & 3u) { set_error("key must be 4-byte aligned"); return HGS_ERR_INVALID; }
+  bool nan = std::isnan(args->min_extent) || std::isnan(key_floor);
+  for (int a = 0; a < 3 && args->use_roi; ++a) nan = nan || std::isnan(args->roi_lo[a]) || std::isnan(args->roi_hi[a]);
+  if (nan) { set_error("min_extent, key_floor or a region bound is NaN"); return HGS_ERR_INVALID; }
+  if ((rc = check_hier_tmp(tmp))) return rc;
+  for (int k = 0; k < 4; ++k) report->first_bad[k] = -1;
+  report->kept = report->stubs = 0;
+  HGS_HIP(hipSetDevice(device));
+  return launch_hier_trim_plan(*in, *args, key, key_floor, tmp, report, static_cast<hipStream_t>(stream), device);
+}
+
+size_t hgs_hier_reach_tmp_bytes(int64_t N, int64_t C) {
+  if (N < 1 || N > kHierMaxNodes || C < 1 || C > kHierReachMaxRegions) return 0;
+  return hier_reach_tmp_bytes(N, (int32_t)C);
+}
+
+int hgs_hier_reach(const float* boxes, int64_t N, const float* regions, int64_t C, float* reach, void* tmp,
+                   hgs_stream_t stream, int device) {
+  if (N < 1 || N > kHierMaxNodes) { set_error("bad sizes: N=%lld not in [1, 2^31 - 1]", (long long)N); return HGS_ERR_INVALID; }
+  if (C < 1 || C > kHierReachMaxRegions) { set_error("bad sizes: C=%lld regions not in [1, 2^24]", (long long)C); return HGS_ERR_INVALID; }
+  if (!boxes || !regions || !reach) { set_error("null argument"); return HGS_ERR_INVALID; }
+  if ((uintptr_t)boxes & 15u) { set_error("boxes must be 16-byte aligned"); return HGS_ERR_INVALID; }
+  if (((uintptr_t)regions | (uintptr_t)reach) & 3u) { set_error("regions / reach must be 4-byte aligned"); return HGS_ERR_INVALID; }
+  if (int rc = check_hier_tmp(tmp)) return rc;
+  HGS_HIP(hipSetDevice(device));
+  return launch_hier_reach(boxes, N, regions, (int32_t)C, reach, tmp, static_cast<hipStream_t>(stream));
 }
 
 int hgs_hier_trim_apply(const hgs_hier_view* in, const hgs_hier_view* out, const void* tmp, int32_t* old_of_new,

@@ -320,10 +320,16 @@ int launch_hier_align(const int32_t* nodes, int64_t N, float* log_scales, float*
 // shs16: copy shs in 16-byte pieces (12 M a multiple of 16, both bases aligned)
 size_t hier_trim_tmp_bytes(int64_t N);
 bool hier_trim_planned(int device, const void* tmp, int64_t* N, int64_t* kept);
-int launch_hier_trim_plan(const hgs_hier_view& in, const hgs_hier_trim_args& args, void* tmp,
-                          hgs_hier_trim_report* report, hipStream_t s, int device);
+// key: nullptr for the plain plan, else a device float per node and one more conjunct in test, key[p] >= key_floor
+int launch_hier_trim_plan(const hgs_hier_view& in, const hgs_hier_trim_args& args, const float* key, float key_floor,
+                          void* tmp, hgs_hier_trim_report* report, hipStream_t s, int device);
 int launch_hier_trim_apply(const hgs_hier_view& in, const hgs_hier_view& out, const void* tmp, int32_t* old_of_new,
                            int32_t* new_of_old, bool shs16, hipStream_t s);
+// view reach (hier_reach.hip): sizes, pointers and alignment checked by the caller (1 <= N <= 2^31 - 1, 1 <= C <= 2^24);
+// asynchronous on s
+size_t hier_reach_tmp_bytes(int64_t N, int32_t C);
+int launch_hier_reach(const float* boxes, int64_t N, const float* regions, int32_t C, float* reach, void* tmp,
+                      hipStream_t s);
 // similarity transform (hier_transform.hip): sizes, pointers, alignment and the parameter block checked by the caller;
 // shs16: move shs in 16-byte pieces (12 M a multiple of 16, both bases aligned)
 int launch_hier_transform(const hgs_hier_view& in, const hgs_hier_view& out, const hgs_hier_transform_args& a, bool shs16,

@@ -11,6 +11,10 @@
 //              common.h over the keep sums, the stub sums added up beside it (one atomic per scan chunk: one per stub
 //              wave on a single word cost 4 ms at 4.2 M stubs); ONE host wait reads back the kept count, the stub count
 //              and the checks.  Nothing has been written to any output at that point.
+//   keyed      hgs_hier_trim_plan_keyed: the same plan with one more conjunct in test, key[p] >= key_floor, key a device
+//              float per node (hgs.hierarchy.trim_to_views: the view reach of hier_reach.hip against a granularity).
+//              ht_plan_kernel<true> beside ht_plan_kernel<false>; the same tmp layout and plan record, so apply takes
+//              either plan.
 //   apply      asynchronous.  ht_maps_kernel: new_of_old and old_of_new from the flags and the scanned sums;
 //              ht_gather_kernel: one workgroup per kHtRows OUTPUT rows stages their source rows in LDS, then copies tensor
 //              by tensor, one thread per 16-byte piece (shs where 12 M is a multiple of 16 and both bases are aligned,
@@ -37,9 +41,13 @@ struct HtResult {
   uint32_t first_bad[4];   // unsigned minima, kNone = none
 };
 
-__device__ __forceinline__ bool ht_test(const float* __restrict__ boxes, int64_t n, const hgs_hier_trim_args& a) {
+// kKeyed: one more conjunct, key[n] >= key_floor (hgs_hier_trim_plan_keyed; a NaN key never passes)
+template <bool kKeyed>
+__device__ __forceinline__ bool ht_test(const float* __restrict__ boxes, int64_t n, const hgs_hier_trim_args& a,
+                                        const float* __restrict__ key, float key_floor) {
   const float4 mn = reinterpret_cast<const float4*>(boxes)[n * 2 + 0];
   bool ok = mn.w >= a.min_extent;                 // (a NaN extent never passes)
+  if constexpr (kKeyed) ok = ok && key[n] >= key_floor;
   if (a.use_roi) {
     const float4 mx = reinterpret_cast<const float4*>(boxes)[n * 2 + 1];
     ok = ok && mn.x <= a.roi_hi[0] && mx.x >= a.roi_lo[0] && mn.y <= a.roi_hi[1] && mx.y >= a.roi_lo[1] &&
@@ -48,14 +56,17 @@ __device__ __forceinline__ bool ht_test(const float* __restrict__ boxes, int64_t
   return ok;
 }
 
-// One thread per node: the checks of the row, its flags, the workgroup's keep sum and stub sum.
+// One thread per node: the checks of the row, its flags, the workgroup's keep sum and stub sum.  <false>: the plan of
+// hgs_hier_trim_plan (key and key_floor are not looked at); <true>: the keyed plan.
+template <bool kKeyed>
 __global__ __launch_bounds__(kHtThreads) void ht_plan_kernel(const int32_t* __restrict__ nodes,
                                                              const float* __restrict__ boxes, int32_t N,
                                                              hgs_hier_trim_args a, uint8_t* __restrict__ flags,
                                                              uint32_t* __restrict__ block_sums,
                                                              uint32_t* __restrict__ block_stubs,
                                                              unsigned long long* __restrict__ chain,
-                                                             HtResult* __restrict__ res) {
+                                                             HtResult* __restrict__ res, const float* __restrict__ key,
+                                                             float key_floor) {
   clear_scan_chain(chain, block_sums);
   const int64_t i = (int64_t)blockIdx.x * kHtThreads + threadIdx.x;
   uint32_t keep = 0, stub = 0;
@@ -69,13 +80,13 @@ __global__ __launch_bounds__(kHtThreads) void ht_plan_kernel(const int32_t* __re
     if (v & kBadChildren) atomicMin(&res->first_bad[1], (uint32_t)i);
     if (v & kBadParent) atomicMin(&res->first_bad[2], (uint32_t)i);
     // ---- the rule
-    const bool test_self = ht_test(boxes, i, a);
+    const bool test_self = ht_test<kKeyed>(boxes, i, a, key, key_floor);
     bool k = i == 0;
     if (v & kParentInRange) {
-      k = ht_test(boxes, parent, a);
+      k = ht_test<kKeyed>(boxes, parent, a, key, key_floor);
       if (k && parent != 0) {          // closure: a kept node's parent is kept (a bad grandparent index is check [2]'s)
         const int32_t pp = nodes[(int64_t)parent * kNodeInts + 1];
-        if (pp >= 0 && pp < N && !ht_test(boxes, pp, a)) atomicMin(&res->first_bad[3], (uint32_t)i);
+        if (pp >= 0 && pp < N && !ht_test<kKeyed>(boxes, pp, a, key, key_floor)) atomicMin(&res->first_bad[3], (uint32_t)i);
       }
     }
     keep = k ? 1u : 0u;
@@ -203,17 +214,24 @@ bool hier_trim_planned(int device, const void* tmp, int64_t* N, int64_t* kept) {
   return false;
 }
 
-int launch_hier_trim_plan(const hgs_hier_view& in, const hgs_hier_trim_args& args, void* tmp,
-                          hgs_hier_trim_report* report, hipStream_t s, int device) {
+// key == nullptr: the plain plan; else the keyed one (key float [N] on the device, key_floor)
+int launch_hier_trim_plan(const hgs_hier_view& in, const hgs_hier_trim_args& args, const float* key, float key_floor,
+                          void* tmp, hgs_hier_trim_report* report, hipStream_t s, int device) {
   forget_plan(device, tmp);
   const int64_t N = in.N;
   Carver c(tmp);
   const HtTmp t = carve_ht_tmp(c, N);
   HGS_HIP(hipMemsetAsync(t.res, 0xff, sizeof(HtResult), s));
   const int nblk = (int)((N + kHtThreads - 1) / kHtThreads);
-  hipLaunchKernelGGL(ht_plan_kernel, dim3((unsigned)nblk), dim3(kHtThreads), 0, s, in.nodes, in.boxes, (int32_t)N, args,
-                     t.flags, t.block_sums, t.block_all, t.chain, t.res);
-  HGS_LAUNCH_CHECK("ht_plan", s, false);
+  if (key) {
+    hipLaunchKernelGGL(ht_plan_kernel<true>, dim3((unsigned)nblk), dim3(kHtThreads), 0, s, in.nodes, in.boxes, (int32_t)N,
+                       args, t.flags, t.block_sums, t.block_all, t.chain, t.res, key, key_floor);
+    HGS_LAUNCH_CHECK("ht_plan_keyed", s, false);
+  } else {
+    hipLaunchKernelGGL(ht_plan_kernel<false>, dim3((unsigned)nblk), dim3(kHtThreads), 0, s, in.nodes, in.boxes, (int32_t)N,
+                       args, t.flags, t.block_sums, t.block_all, t.chain, t.res, key, key_floor);
+    HGS_LAUNCH_CHECK("ht_plan", s, false);
+  }
   const int rc = launch_scan_chunks(ht_scan_kernel, "ht_scan", nblk, s, t.block_sums, t.block_all, nblk, t.chain);
   if (rc) return rc;
   // ---- the one host wait
@@ -230,7 +248,9 @@ int launch_hier_trim_plan(const hgs_hier_view& in, const hgs_hier_trim_args& arg
       "parent outside [0, N) or not claiming the node (node 0: parent != -1)",
       "a kept node under a dropped parent (the boxes do not nest, or the extents grow downwards)"};
   if (fail_on_first_bad(report->first_bad, what, 4,
-                        "not a hierarchy that can be trimmed: %s (first offending node %d); nothing was written"))
+                        key ? "not a hierarchy that can be trimmed to views: %s (first offending node %d; "
+                              "hgs.refit_hierarchy makes the boxes nest); nothing was written"
+                            : "not a hierarchy that can be trimmed: %s (first offending node %d); nothing was written"))
     return HGS_ERR_INVALID;
   std::lock_guard<std::mutex> lock(g_ht_mutex);
   if (g_ht_plans.size() >= kHtMaxPlans) g_ht_plans.erase(g_ht_plans.begin());

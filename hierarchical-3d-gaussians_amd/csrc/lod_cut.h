@@ -1,6 +1,7 @@
 // The rules of the hierarchy cut, each ONCE, for the four calls that must agree bit for bit: expand_to_size +
 // get_interpolation_weights (lod.hip), the frustum-culled cut (lod_frustum.hip), the budget-exact cut (lod_budget.hip)
-// and the cut for several views (lod_views.hip); hier_trim.hip takes the workgroup sums and the scan launcher from here.
+// and the cut for several views (lod_views.hip); hier_trim.hip takes the workgroup sums and the scan launcher from here,
+// hier_reach.hip the squared distance of node_size widened to a box of viewpoints (box_d2).
 // The node record is hier_nodes.h's.  What decides -- the size of a node, the cull, the weight -- is float32 in a fixed
 // operation order with contraction off (oracle/lod_oracle.py, tests/frustum_spec.py and tests/budget_cut_spec.py restate
 // it); the rest is the shape the calls share: per-node emission counts, workgroup sums, the chained scan of common.h, an
@@ -91,6 +92,16 @@ __device__ __forceinline__ float box_size(float4 mn, float4 mx, Vec3 v) {       
   const float dist = sqrtf(d2);
   const float s = mn.w / dist;
   return d2 > 0.0f ? s : kFltMax;
+}
+// box_size with the viewpoint widened to the closed box [lo, hi] (hier_reach.hip), up to its squared distance: the
+// caller takes the minimum over its boxes and ends with extent / sqrtf(d2) as box_size does.  lo == hi == v gives
+// box_size's d2 bit for bit; the fmaxf chain makes d2 a non-negative number whatever the operands (never NaN).
+__device__ __forceinline__ float box_d2(float4 mn, float4 mx, Vec3 lo, Vec3 hi) {
+#pragma clang fp contract(off)
+  const float dx = fmaxf(fmaxf(mn.x - hi.x, lo.x - mx.x), 0.0f);
+  const float dy = fmaxf(fmaxf(mn.y - hi.y, lo.y - mx.y), 0.0f);
+  const float dz = fmaxf(fmaxf(mn.z - hi.z, lo.z - mx.z), 0.0f);
+  return (dx * dx + dy * dy) + dz * dz;
 }
 // entry_culled in its two halves: bit k = the ball is outside plane k ...
 __device__ __forceinline__ uint32_t planes_outside(float4 b, const Frustum& f) {

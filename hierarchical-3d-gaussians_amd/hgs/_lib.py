@@ -191,6 +191,10 @@ SIGNATURES = {
     "hgs_hier_trim_plan": (C.c_int, [C.POINTER(HierView), C.POINTER(HierTrimArgs), _P, C.POINTER(HierTrimReport), _P,
                                      C.c_int]),
     "hgs_hier_trim_apply": (C.c_int, [C.POINTER(HierView), C.POINTER(HierView), _P, _P, _P, _P, C.c_int]),
+    "hgs_hier_reach_tmp_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "hgs_hier_reach": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int]),
+    "hgs_hier_trim_plan_keyed": (C.c_int, [C.POINTER(HierView), C.POINTER(HierTrimArgs), _P, C.c_float, _P,
+                                           C.POINTER(HierTrimReport), _P, C.c_int]),
     "hgs_hier_transform": (C.c_int, [C.POINTER(HierView), C.POINTER(HierView), C.POINTER(HierTransformArgs), _P, C.c_int]),
     "hgs_hier_refit_tmp_bytes": (C.c_size_t, [C.c_int64]),
     "hgs_hier_refit": (C.c_int, [C.POINTER(HierView), _P, C.c_int32, _P, C.POINTER(HierRefitReport), _P, C.c_int]),

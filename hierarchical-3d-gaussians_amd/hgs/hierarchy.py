@@ -10,7 +10,9 @@ chunk at a time, behind ``python -m hgs.merge_hierarchies``).  ``align_hierarchy
 (the same rule on the device, behind ``--align`` and ``python -m hgs.align_hierarchy``) re-express every node's rotation
 and scales in the frame closest to its parent's, opt-in.  ``trim_hierarchy`` (the numpy spec) and ``trim_hierarchy_gpu``
 (the same rule on the device, behind ``python -m hgs.trim_hierarchy``) make a smaller copy: a detail floor, a region, a
-node budget.  ``transform_hierarchy`` (the numpy spec) and ``transform_hierarchy_gpu`` (the same rule on the device, behind
+node budget; ``trim_to_views`` (the numpy spec, on ``view_reach``) and ``trim_to_views_gpu`` (on the device, behind
+``python -m hgs.trim_to_views``) trim to the detail a set of camera positions (``view_regions``) can reach at a
+granularity.  ``transform_hierarchy`` (the numpy spec) and ``transform_hierarchy_gpu`` (the same rule on the device, behind
 ``python -m hgs.transform_hierarchy``) move a hierarchy to another frame by a similarity ``similarity(...)`` builds: means,
 rotations, scales, boxes and SH bands follow; ``transform_camera`` moves a camera with it.  ``refit_boxes`` (the numpy
 spec) and ``refit_boxes_gpu`` (the same rule on the device, behind ``python -m hgs.refit_hierarchy`` and ``--refit`` on the
@@ -888,7 +890,15 @@ def trim_hierarchy(h: Hierarchy, min_extent=0.0, roi=None, max_nodes=None) -> Tr
     _raise_first_bad(TRIM_CHECKS, trim_layout_checks(nodes), refuse)
     if K is not None:
         e = max(e, trim_budget_extent(nodes, boxes, K, roi))
-    test = _trim_test(boxes, e, roi)
+    th, old_of_new, new_of_old, stubs, stub_ids = _trim_by_test(h, nodes, _trim_test(boxes, e, roi), refuse)
+    return TrimResult(th, old_of_new, new_of_old, float(e), stubs, stub_ids)
+
+
+def _trim_by_test(h, nodes, test, refuse):
+    """The part of the rule behind test(p) (numpy bool [N]), for ``trim_hierarchy`` and ``trim_to_views``: the keep
+    flags, the closure check, both maps, the renumbered records and the copied rows -> (hierarchy, old_of_new,
+    new_of_old, stub count, stub_ids) on the host."""
+    N = nodes.shape[0]
     parent = nodes[:, 1].astype(np.int64)
     keep = np.ones(N, dtype=bool)
     keep[1:] = test[parent[1:]]
@@ -911,8 +921,8 @@ def trim_hierarchy(h: Hierarchy, min_extent=0.0, roi=None, max_nodes=None) -> Tr
     rows = lambda t: t.detach().cpu()[:N].index_select(0, idx).clone()
     th = Hierarchy(xyz=rows(h.xyz), shs=rows(h.shs), alpha=rows(h.alpha), log_scales=rows(h.log_scales),
                    rots=rows(h.rots), nodes=torch.from_numpy(out), boxes=rows(h.boxes.reshape(-1, 2, 4)))
-    return TrimResult(th, torch.from_numpy(old.astype(np.int32)), torch.from_numpy(new_of_old), float(e),
-                      int(stub.sum()), torch.from_numpy(np.nonzero(stub[old])[0].astype(np.int32)))
+    return (th, torch.from_numpy(old.astype(np.int32)), torch.from_numpy(new_of_old), int(stub.sum()),
+            torch.from_numpy(np.nonzero(stub[old])[0].astype(np.int32)))
 
 
 def _trim_budget_extent_torch(nodes, boxes, K, roi):
@@ -952,6 +962,19 @@ def trim_hierarchy_gpu(h: Hierarchy, min_extent=0.0, roi=None, max_nodes=None, s
     boxes = h.boxes.reshape(-1, 2, 4)
     if K is not None:
         e = max(e, _trim_budget_extent_torch(h.nodes, boxes, K, roi))
+    with torch.cuda.device(dev), _device_events(stats, "trim_ms") as ev:
+        out, old_of_new, new_of_old, rep, mid = _plan_and_apply(lib, h, (G, N, M), dev, e, roi)
+    if stats is not None:
+        stats["plan_ms"], stats["apply_ms"] = ev[0].elapsed_time(mid), mid.elapsed_time(ev[1])
+    return TrimResult(out, old_of_new, new_of_old, float(e), int(rep.stubs), _stub_ids(h, out, old_of_new))
+
+
+def _plan_and_apply(lib, h, sizes, dev, e, roi, key=None, key_floor=0.0):
+    """On the current stream of ``dev``: hgs_hier_trim_plan (with ``key``, a device float32 [N]: hgs_hier_trim_plan_keyed
+    at ``key_floor``), the allocation of the N' rows, hgs_hier_trim_apply -> (hierarchy, old_of_new, new_of_old, the
+    plan's report, the device event recorded between the allocation and apply).  A failed check raises
+    ``HierarchyTrimError`` before anything is allocated."""
+    G, N, M = sizes
     args = _lib.HierTrimArgs(float(e), 0 if roi is None else 1)
     if roi is not None:
         args.roi_lo[:], args.roi_hi[:] = [float(x) for x in roi[0]], [float(x) for x in roi[1]]
@@ -960,26 +983,261 @@ def trim_hierarchy_gpu(h: Hierarchy, min_extent=0.0, roi=None, max_nodes=None, s
     rep = _lib.HierTrimReport()
     rep.first_bad[:] = [-1] * 4              # (a call that fails its size checks does not fill the report)
     vin = _hier_view(h, G, N, M)
-    with torch.cuda.device(dev), _device_events(stats, "trim_ms") as ev:
-        stream = _stream(dev)
+    stream = _stream(dev)
+    if key is None:
+        name = "hgs_hier_trim_plan"
         rc = lib.hgs_hier_trim_plan(C.byref(vin), C.byref(args), p(tmp), C.byref(rep), stream, dev.index or 0)
-        if rc != 0:
-            msg = (lib.hgs_last_error() or b"?").decode()
-            _raise_first_bad(TRIM_CHECKS, rep.first_bad,
-                             lambda check, node: HierarchyTrimError(check, node, f"hgs_hier_trim_plan: {msg}"))
-            raise _lib.HgsError(f"hgs_hier_trim_plan failed (code {rc}): {msg}", rc)
-        n = int(rep.kept)
-        out = _empty_hierarchy(dev, n, h.shs.shape[1:], h.alpha.shape[1:])
-        old_of_new, new_of_old = (torch.empty(m, dtype=torch.int32, device=dev) for m in (n, N))
-        mid = torch.cuda.Event(enable_timing=True)
-        mid.record()
-        _lib.check(lib.hgs_hier_trim_apply(C.byref(vin), C.byref(_hier_view(out, n, n, M)), p(tmp), p(old_of_new),
-                                           p(new_of_old), stream, dev.index or 0), "hgs_hier_trim_apply")
-    if stats is not None:
-        stats["plan_ms"], stats["apply_ms"] = ev[0].elapsed_time(mid), mid.elapsed_time(ev[1])
-    stub_ids = ((h.nodes[:, 6][old_of_new.long()] > 0) & (out.nodes[:, 6] == 0)).nonzero().flatten().to(torch.int32)
-    return TrimResult(out, old_of_new, new_of_old, float(e), int(rep.stubs), stub_ids)
+    else:
+        name = "hgs_hier_trim_plan_keyed"
+        rc = lib.hgs_hier_trim_plan_keyed(C.byref(vin), C.byref(args), p(key), float(key_floor), p(tmp), C.byref(rep),
+                                          stream, dev.index or 0)
+    if rc != 0:
+        msg = (lib.hgs_last_error() or b"?").decode()
+        _raise_first_bad(TRIM_CHECKS, rep.first_bad,
+                         lambda check, node: HierarchyTrimError(check, node, f"{name}: {msg}"))
+        raise _lib.HgsError(f"{name} failed (code {rc}): {msg}", rc)
+    n = int(rep.kept)
+    out = _empty_hierarchy(dev, n, h.shs.shape[1:], h.alpha.shape[1:])
+    old_of_new, new_of_old = (torch.empty(m, dtype=torch.int32, device=dev) for m in (n, N))
+    mid = torch.cuda.Event(enable_timing=True)
+    mid.record()
+    _lib.check(lib.hgs_hier_trim_apply(C.byref(vin), C.byref(_hier_view(out, n, n, M)), p(tmp), p(old_of_new),
+                                       p(new_of_old), stream, dev.index or 0), "hgs_hier_trim_apply")
+    return out, old_of_new, new_of_old, rep, mid
 
+
+def _stub_ids(h, out, old_of_new):
+    """New indices of the stubs, ascending (int32, on the device): nodes with children that came out as leaves."""
+    return ((h.nodes[:, 6][old_of_new.long()] > 0) & (out.nodes[:, 6] == 0)).nonzero().flatten().to(torch.int32)
+
+
+# ---- trimming to the detail a set of views can reach ------------------------------------------------------------------------
+REACH_MAX_REGIONS = 1 << 24
+REACH_SLAB = 256            # kReachSlab of csrc/hier_reach.hip: the unit a split of the region range is made of
+_REACH_SPEC_PAIRS = 1 << 22   # (node, region) pairs per chunk of the numpy spec
+
+
+def _check_regions(lo, hi, names=None):
+    """(lo, hi) float32 [C,3], finite, lo <= hi, C >= 1, or a ValueError naming the entry."""
+    lo, hi = np.ascontiguousarray(lo, dtype=np.float32), np.ascontiguousarray(hi, dtype=np.float32)
+    if lo.ndim != 2 or lo.shape[1] != 3 or lo.shape != hi.shape:
+        raise ValueError(f"view regions are a pair (lo [C,3], hi [C,3]); got {lo.shape} and {hi.shape}")
+    C_ = lo.shape[0]
+    if C_ < 1 or C_ > REACH_MAX_REGIONS:
+        raise ValueError(f"{C_} view regions; 1 .. 2^24 expected (an empty view set reaches nothing)")
+    bad = ~(np.isfinite(lo).all(1) & np.isfinite(hi).all(1)) | (lo > hi).any(1)
+    if bad.any():
+        k = int(np.nonzero(bad)[0][0])
+        what = f"view region {k}" if names is None else names[k]
+        why = "lo > hi on an axis" if np.isfinite(lo[k]).all() and np.isfinite(hi[k]).all() else "not finite"
+        raise ValueError(f"{what}: {why} (lo = {lo[k].tolist()}, hi = {hi[k].tolist()})")
+    return lo, hi
+
+
+def view_regions(points=None, boxes=None, pad=0.0):
+    """A view set: C >= 1 closed boxes of camera positions -> (lo, hi), float32 [C,3] each.  ``points`` [P,3] become the
+    boxes [fl32(p - pad), fl32(p + pad)] (``pad`` = 0: the position itself); ``boxes`` [B,2,3] or [B,6] (lo.xyz, hi.xyz)
+    are taken as they are, behind the points.  Refused with a ValueError naming the entry: NaN, infinity, lo > hi,
+    pad < 0 (or NaN), an empty set."""
+    pad = float(pad)
+    if not pad >= 0.0 or pad == float("inf"):
+        raise ValueError(f"pad = {pad}; a finite number >= 0 expected")
+    as64 = lambda a: np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=np.float64)
+    lo, hi, names = [], [], []
+    with np.errstate(over="ignore"):             # (a number too large for float32 becomes infinity and is refused)
+        if points is not None:
+            pts = as64(points).reshape(-1, 3)
+            lo.append((pts - pad).astype(np.float32))
+            hi.append((pts + pad).astype(np.float32))
+            names += [f"view point {k}" for k in range(pts.shape[0])]
+        if boxes is not None:
+            bx = as64(boxes).reshape(-1, 6).astype(np.float32)
+            lo.append(bx[:, :3])
+            hi.append(bx[:, 3:])
+            names += [f"view box {k}" for k in range(bx.shape[0])]
+    if not names:
+        raise ValueError("an empty view set: no view point and no view box")
+    return _check_regions(np.concatenate(lo), np.concatenate(hi), names)
+
+
+def _reach_d2(boxes, lo, hi):
+    """d2(p, c), float32 [N, c]: squared distance from box p to region c, every operation float32 in the device's order."""
+    mn, mx = boxes[:, None, 0, :3], boxes[:, None, 1, :3]
+    d = np.fmax(np.fmax(mn - hi[None], lo[None] - mx), np.float32(0))
+    return (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+
+
+def _reach_of(ext, d2):
+    return np.where(d2 > 0, ext / np.sqrt(d2), np.float32(_FLT_MAX)).astype(np.float32)
+
+
+def view_reach(h: Hierarchy, regions) -> np.ndarray:
+    """The view reach of every node, leaves included (the numpy spec of csrc/hier_reach.hip) -> float32 [N]:
+    D2(p) = min over the regions c of d2(p, c), reach(p) = D2 > 0 ? extent(p) / sqrt(D2) : FLT_MAX -- ``node_size`` of
+    the cut with the viewpoint widened to a box, so no viewpoint inside any region sees p at a larger size.  fmax / fmin
+    as on the device: d2 is never NaN.  Walks the regions in chunks: memory stays O(N)."""
+    lo, hi = _check_regions(*regions)
+    boxes = np.ascontiguousarray(h.boxes.detach().cpu().numpy(), dtype=np.float32).reshape(-1, 2, 4)
+    N = boxes.shape[0]
+    step = max(1, _REACH_SPEC_PAIRS // max(N, 1))
+    best = np.full(N, np.inf, dtype=np.float32)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for c0 in range(0, lo.shape[0], step):
+            best = np.fmin(best, _reach_d2(boxes, lo[c0:c0 + step], hi[c0:c0 + step]).min(1))
+        return _reach_of(boxes[:, 0, 3], best)
+
+
+def view_reach_gpu(h: Hierarchy, regions, stats=None) -> torch.Tensor:
+    """``view_reach`` on the GPU (csrc/hier_reach.hip, hgs_hier_reach) -> a device float32 [N], the spec's bits.
+    ``h.boxes``: a contiguous float32 device tensor [N,2,4]; nothing else of ``h`` is read.  Asynchronous on the current
+    stream unless ``stats`` (a dict) is given: it receives ``reach_ms`` (device events around the call).  No CPU
+    fallback: raises without libhgs.so or a GPU."""
+    lib, _ = _need_gpu("view_reach_gpu", "view_reach")
+    lo, hi = _check_regions(*regions)
+    dev = _device_rows(h, ("boxes",), "view_reach_gpu")
+    N = h.boxes.numel() // 8
+    if N < 1 or N > TRIM_MAX_NODES:
+        raise ValueError(f"N = {N} nodes; 1 .. 2^31 - 1 expected")
+    with torch.cuda.device(dev), _device_events(stats, "reach_ms"):
+        return _reach_on_device(lib, h.boxes, N, lo, hi, dev)
+
+
+def _reach_on_device(lib, boxes, N, lo, hi, dev):
+    C_ = lo.shape[0]
+    regions = torch.from_numpy(np.concatenate([lo, hi], axis=1)).to(dev)          # [C,6]
+    reach = torch.empty(N, dtype=torch.float32, device=dev)
+    tmp = torch.empty(lib.hgs_hier_reach_tmp_bytes(N, C_), dtype=torch.uint8, device=dev)
+    _lib.check(lib.hgs_hier_reach(boxes.data_ptr(), N, regions.data_ptr(), C_, reach.data_ptr(), tmp.data_ptr(),
+                                  _stream(dev), dev.index or 0), "hgs_hier_reach")
+    return reach
+
+
+@dataclass
+class ViewTrimResult(TrimResult):
+    tau: float                  # the granularity that was used (float32; the larger of the given one and the budget's)
+    regions: tuple              # (lo, hi), numpy float32 [C,3] each
+
+    def covers(self, viewpoint, tau) -> bool:
+        """Does the contract hold for this view: ``viewpoint`` (rounded to float32) lies in one of the closed regions
+        and ``tau`` >= the granularity used?  Then ``exact_for(viewpoint, tau)`` is true and the cut of ``hierarchy`` is
+        the original's mapped through ``new_of_old``."""
+        v = np.asarray(viewpoint.detach().cpu().numpy() if torch.is_tensor(viewpoint) else viewpoint,
+                       dtype=np.float32).reshape(3)
+        lo, hi = self.regions
+        return bool(((lo <= v) & (v <= hi)).all(1).any() and np.float32(tau) >= np.float32(self.tau))
+
+
+def _view_tau(tau):
+    t = np.float32(tau)
+    if np.isnan(t):
+        raise ValueError("tau is NaN")
+    return t
+
+
+def view_budget_tau(nodes, boxes, reach, max_nodes, min_extent=0.0, roi=None):
+    """The granularity a node budget resolves to under a view set (numpy float32): the smallest reach value t among the
+    nodes with children that pass the extent and region tests such that 1 + sum of count_children over {p: reach(p)
+    >= t} <= max_nodes; nodes of equal reach go in together or not at all; +inf (the root alone: FLT_MAX < inf) if even
+    the first run does not fit."""
+    boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 2, 4)
+    reach = np.asarray(reach, dtype=np.float32)
+    cc = np.asarray(nodes)[:, 6].astype(np.int64)
+    cand = (cc > 0) & _trim_test(boxes, np.float32(min_extent), roi) & (reach == reach)   # (a NaN never passes a test)
+    r, c = reach[cand], cc[cand]
+    if r.size == 0:
+        return np.float32(np.inf)
+    order = np.argsort(-r, kind="stable")
+    r, total = r[order], 1 + np.cumsum(c[order])
+    last = np.ones(r.size, dtype=bool)
+    last[:-1] = r[:-1] != r[1:]
+    ok = np.nonzero(last & (total <= int(max_nodes)))[0]
+    return np.float32(r[ok[-1]]) if ok.size else np.float32(np.inf)
+
+
+def _view_budget_tau_torch(nodes, boxes, reach, K, e, roi):
+    """``view_budget_tau`` in torch on the tensors' device -> numpy float32."""
+    cc = nodes[:, 6].long()
+    cand = (cc > 0) & (boxes[:, 0, 3] >= float(e)) & (reach == reach)
+    if roi is not None:
+        lo, hi = (torch.from_numpy(r).to(boxes.device) for r in roi)
+        cand &= (boxes[:, 0, :3] <= hi).all(1) & (boxes[:, 1, :3] >= lo).all(1)
+    r, c = reach[cand], cc[cand]
+    if r.numel() == 0:
+        return np.float32(np.inf)
+    r, order = torch.sort(r, descending=True, stable=True)
+    total = 1 + torch.cumsum(c[order], 0)
+    last = torch.ones_like(r, dtype=torch.bool)
+    last[:-1] = r[:-1] != r[1:]
+    ok = (last & (total <= K)).nonzero().flatten()
+    return np.float32(r[ok[-1]].item()) if ok.numel() else np.float32(np.inf)
+
+
+_VIEW_HINT = "hgs.refit_hierarchy makes the boxes nest"
+
+
+def trim_to_views(h: Hierarchy, regions, tau, min_extent=0.0, roi=None, max_nodes=None) -> ViewTrimResult:
+    """Trim a hierarchy to the detail a view set can reach at granularity ``tau`` (the numpy spec;
+    ``trim_to_views_gpu`` is the same rule on the device).  ``regions``: ``view_regions(...)``.  test(p) = reach(p) >=
+    tau (``view_reach``) and extent(p) >= min_extent and, with ``roi``, box(p) meets it; the rest is ``trim_hierarchy``'s
+    rule word for word: node 0 is kept, node n > 0 iff test(parent(n)), stubs, renumbering, the four checks (closure
+    fails where the boxes do not nest: ``hgs.refit_hierarchy`` mends that).  ``max_nodes`` = K resolves to a
+    granularity first (``view_budget_tau``); the larger of it and ``tau`` is used, and at most K nodes stay.
+    The contract: for every float32 viewpoint v inside a region (borders included) and every tau' >= result.tau,
+    ``result.exact_for(v, tau')`` holds: the cut, its weights and an LOD render of the result are the original's mapped
+    through ``new_of_old``.  Elsewhere stubs stand in at weight 1, as under ``trim_hierarchy``.  -> ViewTrimResult (host
+    tensors)."""
+    lo, hi = _check_regions(*regions)
+    t = _view_tau(tau)
+    e, roi, K = _trim_params(min_extent, roi, max_nodes)
+    nodes = h.nodes.detach().cpu().numpy().astype(np.int32)
+    N = nodes.shape[0]
+    G = int(h.xyz.shape[0])
+    if N < 1 or G < N or N > TRIM_MAX_NODES:
+        raise ValueError(f"G = {G} rows, N = {N} nodes; 1 <= N <= G, N <= 2^31 - 1 expected")
+    boxes = h.boxes.detach().cpu().numpy().astype(np.float32).reshape(-1, 2, 4)
+    assert boxes.shape[0] == N
+    refuse = lambda check, node: HierarchyTrimError(check, node, f"not a hierarchy that can be trimmed to views: {check} "
+                                                                 f"(first offending node {node}; {_VIEW_HINT}); nothing "
+                                                                 f"was written")
+    _raise_first_bad(TRIM_CHECKS, trim_layout_checks(nodes), refuse)
+    reach = view_reach(h, (lo, hi))
+    if K is not None:
+        t = max(t, view_budget_tau(nodes, boxes, reach, K, e, roi))
+    test = _trim_test(boxes, e, roi) & (reach >= t)
+    th, old_of_new, new_of_old, stubs, stub_ids = _trim_by_test(h, nodes, test, refuse)
+    return ViewTrimResult(th, old_of_new, new_of_old, float(e), stubs, stub_ids, float(t), (lo, hi))
+
+
+def trim_to_views_gpu(h: Hierarchy, regions, tau, min_extent=0.0, roi=None, max_nodes=None,
+                      stats=None) -> ViewTrimResult:
+    """``trim_to_views`` on the GPU (csrc/hier_reach.hip: hgs_hier_reach; csrc/hier_trim.hip: hgs_hier_trim_plan_keyed on
+    the reach, then N' rows are allocated, then hgs_hier_trim_apply).  ``h`` as for ``trim_hierarchy_gpu``; it is not
+    modified.  Every output tensor, both maps, N', the stub count and tau equal the spec's bit for bit.  A node budget
+    is resolved with torch on the device, behind the reach pass.  A hierarchy that fails a check raises
+    ``HierarchyTrimError``; nothing has been allocated or written then.  ``stats`` (a dict, optional) receives
+    ``trim_ms`` (device events around everything) and its parts ``reach_ms``, ``plan_ms`` (the budget, plan, its host
+    wait and the allocation) and ``apply_ms``.  No CPU fallback: raises without libhgs.so or a GPU."""
+    lib, _ = _need_gpu("trim_to_views_gpu", "trim_to_views")
+    lo, hi = _check_regions(*regions)
+    t = _view_tau(tau)
+    e, roi, K = _trim_params(min_extent, roi, max_nodes)
+    G, N, M = _tensor_sizes(h)
+    if N < 1 or G < N or N > TRIM_MAX_NODES:
+        raise ValueError(f"G = {G} rows, N = {N} nodes; 1 <= N <= G, N <= 2^31 - 1 expected")
+    dev = _device_rows(h, _ROWS, "trim_to_views_gpu")
+    boxes = h.boxes.reshape(-1, 2, 4)
+    with torch.cuda.device(dev), _device_events(stats, "trim_ms") as ev:
+        reach = _reach_on_device(lib, h.boxes, N, lo, hi, dev)
+        reached = torch.cuda.Event(enable_timing=True)
+        reached.record()
+        if K is not None:
+            t = max(t, _view_budget_tau_torch(h.nodes, boxes, reach, K, e, roi))
+        out, old_of_new, new_of_old, rep, mid = _plan_and_apply(lib, h, (G, N, M), dev, e, roi, reach, t)
+    if stats is not None:
+        stats["reach_ms"], stats["plan_ms"] = ev[0].elapsed_time(reached), reached.elapsed_time(mid)
+        stats["apply_ms"] = mid.elapsed_time(ev[1])
+    return ViewTrimResult(out, old_of_new, new_of_old, float(e), int(rep.stubs), _stub_ids(h, out, old_of_new),
+                          float(t), (lo, hi))
 
 # ---- similarity transform: x' = s R x + t, rotations, scales, boxes and SH bands following -------------------------------
 TRANSFORM_MAX_NODES = (1 << 31) - 1

@@ -643,6 +643,34 @@ int hgs_hier_trim_apply(const hgs_hier_view* in, const hgs_hier_view* out, const
                         int32_t* new_of_old, hgs_stream_t stream, int device);
 
 /* ---------------------------------------------------------------------------
+ * Trimming a hierarchy to the detail a set of views can reach: the rule of hgs.hierarchy.trim_to_views (DESIGN.md
+ * section 4 and section 7 f-20), in two additions to the calls above.
+ * hgs_hier_reach: regions is a device array float32 [C,6], C closed boxes (lo.xyz, hi.xyz) of camera positions, a
+ * single position being lo == hi; finite, lo <= hi (the caller's business: the call does not look).  For every node p,
+ * leaves included, in float32 with contraction off and in this order:
+ *   d_a(p,c) = fmax(fmax(boxes[p,0,a] - hi_c[a], lo_c[a] - boxes[p,1,a]), 0)       a = x, y, z
+ *   d2(p,c)  = (dx*dx + dy*dy) + dz*dz                  D2(p) = min over c of d2(p,c)
+ *   reach[p] = D2 > 0 ? boxes[p,0,3] / sqrt(D2) : FLT_MAX
+ * -- node_size of the cut with the viewpoint widened to a box: no viewpoint inside any region sees the node larger.  A
+ * NaN box coordinate behaves as under fmaxf: d2 is never NaN.  reach: float32 [N] on the device.  Few nodes under many
+ * regions are split over the region range and folded with an integer minimum on d2's bit pattern: the result does not
+ * depend on the split or on any order.  Asynchronous on `stream`: no host wait.  tmp: hgs_hier_reach_tmp_bytes(N, C) of
+ * device memory, 256-byte aligned.  Checked before any HIP call: 1 <= N <= 2^31 - 1, 1 <= C <= 2^24, no null pointer,
+ * boxes 16-byte aligned, regions and reach 4-byte aligned.
+ * hgs_hier_reach_tmp_bytes: host only (no GPU needed); 0 for an N or a C out of range.
+ * hgs_hier_trim_plan_keyed: hgs_hier_trim_plan with one more conjunct in test: key[p] >= key_floor, key a device
+ * float32 [N] (4-byte aligned).  With key = reach and key_floor = a granularity tau, node n > 0 is kept iff some view of
+ * the set can see its parent at a size >= tau (and the parent passes the floor and the region of `args`).  A NaN key
+ * never passes; a NaN key_floor is refused.  Same checks (closure fails where the boxes do not nest:
+ * hgs.refit_hierarchy mends that), same single host wait, same report, same tmp (hgs_hier_trim_tmp_bytes(N)) and the
+ * same plan record: hgs_hier_trim_apply follows it unchanged.  key is not read by apply. */
+size_t hgs_hier_reach_tmp_bytes(int64_t N, int64_t C);
+int hgs_hier_reach(const float* boxes, int64_t N, const float* regions, int64_t C, float* reach, void* tmp,
+                   hgs_stream_t stream, int device);
+int hgs_hier_trim_plan_keyed(const hgs_hier_view* in, const hgs_hier_trim_args* args, const float* key, float key_floor,
+                             void* tmp, hgs_hier_trim_report* report, hgs_stream_t stream, int device);
+
+/* ---------------------------------------------------------------------------
  * Similarity transform of a hierarchy on the device: the rule of hgs.hierarchy.transform_hierarchy (DESIGN.md section 4
  * and section 7 f-18).  The map is x' = s R x + t, R a proper rotation, s > 0.  All G rows are transformed (a skybox
  * tail behind the N nodes included), the N boxes are transformed, nodes and alpha are copied bit for bit.  Every product
