@@ -28,7 +28,10 @@ import time
 import torch
 
 from . import ply
+from ._hier_command import require_gpu, usage_exit, write_output
 from .synth import Scene
+
+USAGE = "usage: python -m hgs.create_hierarchy [--align] <point_cloud.ply> <chunk dir> <out dir> [<scaffold dir>]"
 
 
 def read_skybox_count(ply_path, scaffold_dir=None) -> int:
@@ -77,10 +80,8 @@ def split_flags(argv, flags=("--align",)):
 def run(ply_path, chunk_dir, out_dir, scaffold_dir=None, align=False) -> dict:
     """Read, select, build, (align,) write; -> figures of the run (rows read / kept, N, read / write seconds, build ms
     and, with ``align``, align ms from device events)."""
-    from gaussian_hierarchy._C import write_hierarchy
     from .hierarchy import align_hierarchy_gpu, build_hierarchy_gpu
-    if not torch.cuda.is_available():
-        raise RuntimeError("hgs.create_hierarchy builds on the GPU; no GPU is visible")
+    require_gpu("create_hierarchy")
     t0 = time.perf_counter()
     scene = ply.read_ply(ply_path)
     rows = select_rows(scene.means3D, read_skybox_count(ply_path, scaffold_dir), read_chunk_bounds(chunk_dir))
@@ -98,20 +99,16 @@ def run(ply_path, chunk_dir, out_dir, scaffold_dir=None, align=False) -> dict:
     stats = {}
     if align:
         align_hierarchy_gpu(h, stats)
-    t1 = time.perf_counter()
-    os.makedirs(out_dir, exist_ok=True)
     out_path = os.path.join(out_dir, "hierarchy.hier")
-    write_hierarchy(out_path, h.xyz, h.shs, h.alpha, h.log_scales, h.rots, h.nodes, h.boxes)
+    write_s = write_output(out_path, h)
     return dict(rows_read=scene.P, rows_kept=int(rows.numel()), nodes=h.num_nodes, build_ms=ev[0].elapsed_time(ev[1]),
-                align_ms=stats.get("align_ms"), read_s=t_read, write_s=time.perf_counter() - t1, path=out_path)
+                align_ms=stats.get("align_ms"), read_s=t_read, write_s=write_s, path=out_path)
 
 
 def main(argv=None) -> int:
     argv, flags = split_flags(sys.argv[1:] if argv is None else list(argv))
     if len(argv) not in (3, 4):
-        print("usage: python -m hgs.create_hierarchy [--align] <point_cloud.ply> <chunk dir> <out dir> [<scaffold dir>]",
-              file=sys.stderr)
-        return 2
+        return usage_exit(USAGE)
     r = run(*argv, align="--align" in flags)
     aligned = f", align {r['align_ms']:.2f} ms" if r["align_ms"] is not None else ""
     print(f"create_hierarchy: read {r['rows_read']} rows, kept {r['rows_kept']}, N = {r['nodes']} nodes, "

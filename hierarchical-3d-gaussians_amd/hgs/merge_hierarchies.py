@@ -28,6 +28,7 @@ import time
 
 import torch
 
+from ._hier_command import check_exit, require_gpu, usage_exit, write_output
 from .create_hierarchy import read_chunk_bounds, select_rows, split_flags
 
 USAGE = ("usage: python -m hgs.merge_hierarchies [--align] <trained chunks dir> <root type> <chunks dir> <output .hier> "
@@ -61,10 +62,8 @@ def count_drifted(h, node_counts, bounds):
 
 def run(trained_dir, chunks_dir, out_path, names, align=False) -> dict:
     """Read, merge, (align,) write; -> figures of the run."""
-    from gaussian_hierarchy._C import write_hierarchy
     from .hierarchy import merge_hierarchies_gpu, read_hier_header
-    if not torch.cuda.is_available():
-        raise RuntimeError("hgs.merge_hierarchies merges on the GPU; no GPU is visible")
+    require_gpu("merge_hierarchies")
     paths = [chunk_file(trained_dir, n)[0] for n in names]
     headers = [read_hier_header(p) for p in paths]
     bounds = [read_chunk_bounds(os.path.join(chunks_dir, n)) for n in names]
@@ -75,26 +74,21 @@ def run(trained_dir, chunks_dir, out_path, names, align=False) -> dict:
     t_merge = time.perf_counter() - t0
     node_counts = [hd[1] for hd in headers]
     drifted = count_drifted(h, node_counts, bounds)
-    t1 = time.perf_counter()
-    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-    write_hierarchy(out_path, h.xyz, h.shs, h.alpha, h.log_scales, h.rots, h.nodes, h.boxes)
+    write_s = write_output(out_path, h)
     return dict(chunks=len(names), nodes=node_counts, merged=h.num_nodes,
                 skybox_dropped=sum(hd[0] - hd[1] for hd in headers), drifted=drifted,
                 bounded=sum(b is not None for b in bounds), merge_ms=stats["merge_ms"], align_ms=stats.get("align_ms"),
-                read_s=stats["read_s"],
-                merge_s=t_merge, write_s=time.perf_counter() - t1, path=out_path)
+                read_s=stats["read_s"], merge_s=t_merge, write_s=write_s, path=out_path)
 
 
 def main(argv=None) -> int:
     argv, flags = split_flags(sys.argv[1:] if argv is None else list(argv))
     if len(argv) < 5:
-        print(USAGE, file=sys.stderr)
-        return 2
+        return usage_exit(USAGE)
     trained_dir, root_type, chunks_dir, out_path, names = argv[0], argv[1], argv[2], argv[3], argv[4:]
     if root_type != "0":
-        print(f"merge_hierarchies: root type {root_type!r} is not supported (0 only, what full_train.py passes)\n{USAGE}",
-              file=sys.stderr)
-        return 2
+        return usage_exit(USAGE, f"merge_hierarchies: root type {root_type!r} is not supported (0 only, what "
+                                 f"full_train.py passes)")
     missing = [n for n in names if chunk_file(trained_dir, n)[0] is None]
     if missing:
         print(f"merge_hierarchies: no hierarchy.hier_opt or hierarchy.hier under {trained_dir} for chunk(s) "
@@ -107,8 +101,7 @@ def main(argv=None) -> int:
     try:
         r = run(trained_dir, chunks_dir, out_path, names, align="--align" in flags)
     except ChunkValidationError as e:
-        print(f"merge_hierarchies: {e}; nothing written", file=sys.stderr)
-        return 1
+        return check_exit("merge_hierarchies", e)
     aligned = f", align {r['align_ms']:.2f} ms" if r["align_ms"] is not None else ""
     print(f"merge_hierarchies: {r['chunks']} chunks of {'/'.join(str(n) for n in r['nodes'])} nodes, merged N = "
           f"{r['merged']} nodes, dropped {r['skybox_dropped']} skybox rows, {r['drifted']} leaves outside their chunk "

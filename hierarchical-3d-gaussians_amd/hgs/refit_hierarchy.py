@@ -20,88 +20,55 @@ status 1.  ``anchors.bin`` and ``exposure.json`` beside the input hold indices a
 not touch: they are copied beside the output (said so when they exist)."""
 from __future__ import annotations
 
-import os
-import shutil
+import dataclasses
 import sys
-import time
 
-import torch
+from ._hier_command import (carry_side_files, check_exit, missing_path, read_input, upload, usage_exit, walk_args,
+                            write_output)
 
 USAGE = "usage: python -m hgs.refit_hierarchy <in.hier> <out.hier> [--leaf cube|ellipsoid|keep] [--half]"
-SIDE_FILES = ("anchors.bin", "exposure.json")
 LEAF_MODES = ("cube", "ellipsoid", "keep")
+OPTIONS = {"--leaf": 1, "--half": 0}
 
 
 def parse_args(argv):
-    """-> (in_path, out_path, leaf, half) or None for a usage error."""
-    pos, leaf, half = [], "cube", False
-    i = 0
-    while i < len(argv):
-        a = argv[i]
-        if a == "--leaf":
-            if i + 1 >= len(argv) or argv[i + 1] not in LEAF_MODES:
-                return None
-            leaf, i = argv[i + 1], i + 2
-        elif a == "--half":
-            half, i = True, i + 1
-        elif a.startswith("--"):
-            return None
-        else:
-            pos.append(a)
-            i += 1
-    if len(pos) != 2:
+    """-> (in_path, out_path, leaf, half) or None for a usage error.  The last --leaf wins."""
+    walked = walk_args(argv, OPTIONS)
+    if walked is None:
         return None
-    return pos[0], pos[1], leaf, half
+    pos, seen = walked
+    leaves = [v[0] for v in seen["--leaf"]]
+    if len(pos) != 2 or any(v not in LEAF_MODES for v in leaves):
+        return None
+    return pos[0], pos[1], leaves[-1] if leaves else "cube", bool(seen["--half"])
 
 
 def run(in_path, out_path, leaf="cube", half=False) -> dict:
     """Read, refit, write; -> figures of the run."""
-    from gaussian_hierarchy._C import _boxes_nested, load_hierarchy, write_hierarchy
-    from .hierarchy import Hierarchy, refit_boxes_gpu
-    if not torch.cuda.is_available():
-        raise RuntimeError("hgs.refit_hierarchy refits on the GPU; no GPU is visible")
-    t0 = time.perf_counter()
-    host = Hierarchy(*load_hierarchy(in_path))
-    t_read = time.perf_counter() - t0
-    N, G = host.num_nodes, int(host.xyz.shape[0])
-    if N < 1 or G < N:
-        raise ValueError(f"{in_path}: G = {G} rows, N = {N} nodes; 1 <= N <= G expected")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    names = ("xyz", "shs", "alpha", "log_scales", "rots", "nodes", "boxes")
-    h = Hierarchy(*(getattr(host, k).to(dev).contiguous() for k in names))
+    from gaussian_hierarchy._C import _boxes_nested
+    from .hierarchy import refit_boxes_gpu
+    host, N, G, read_s = read_input("refit_hierarchy", in_path)
+    h = upload(host)
     nested_in = _boxes_nested(h.nodes, h.boxes)
     stats = {}
     refit_boxes_gpu(h, leaf, inplace=True, stats=stats)
     nested_out = _boxes_nested(h.nodes, h.boxes)
-    t1 = time.perf_counter()
-    out_dir = os.path.dirname(os.path.abspath(out_path))
-    os.makedirs(out_dir, exist_ok=True)
-    write_hierarchy(out_path, *(getattr(host, k) for k in names[:6]), h.boxes.cpu(), half=half)
-    in_dir = os.path.dirname(os.path.abspath(in_path))
-    beside = [f for f in SIDE_FILES if os.path.exists(os.path.join(in_dir, f))]
-    for f in beside:
-        if in_dir != out_dir:
-            shutil.copyfile(os.path.join(in_dir, f), os.path.join(out_dir, f))
+    write_s = write_output(out_path, dataclasses.replace(host, boxes=h.boxes), half)
+    beside, same_dir = carry_side_files(in_path, out_path)
     return dict(nodes=N, tail=G - N, leaf=leaf, levels=stats["levels"], leaves=stats["leaves"], nested_in=nested_in,
-                nested_out=nested_out, refit_ms=stats["refit_ms"], read_s=t_read, write_s=time.perf_counter() - t1,
-                beside=beside, same_dir=in_dir == out_dir, path=out_path)
+                nested_out=nested_out, refit_ms=stats["refit_ms"], read_s=read_s, write_s=write_s, beside=beside,
+                same_dir=same_dir, path=out_path)
 
 
 def main(argv=None) -> int:
-    argv = sys.argv[1:] if argv is None else list(argv)
-    parsed = parse_args(argv)
-    if parsed is None:
-        print(USAGE, file=sys.stderr)
-        return 2
-    if not os.path.exists(parsed[0]):
-        print(f"refit_hierarchy: {parsed[0]} does not exist\n{USAGE}", file=sys.stderr)
-        return 2
+    parsed = parse_args(sys.argv[1:] if argv is None else list(argv))
+    if parsed is None or missing_path("refit_hierarchy", parsed[0]):
+        return usage_exit(USAGE)
     from .hierarchy import HierarchyRefitError
     try:
         r = run(*parsed)
     except HierarchyRefitError as e:
-        print(f"refit_hierarchy: {parsed[0]}: {e.check} (node {e.node}): {e}; nothing written", file=sys.stderr)
-        return 1
+        return check_exit("refit_hierarchy", f"{parsed[0]}: {e.check} (node {e.node}): {e}")
     yes = lambda b: "nested" if b else "did NOT nest"
     print(f"refit_hierarchy: N = {r['nodes']} nodes on {r['levels']} levels, {r['leaves']} leaves (--leaf {r['leaf']}), "
           f"{r['tail']} rows behind the nodes left alone; the input's boxes {yes(r['nested_in'])}, the output's "

@@ -23,18 +23,17 @@ device time, read and write seconds."""
 from __future__ import annotations
 
 import math
-import os
-import shutil
 import sys
-import time
 
 import numpy as np
-import torch
+
+from ._hier_command import carry_side_files, missing_path, read_input, upload, usage_exit, walk_args, write_output
 
 USAGE = ("usage: python -m hgs.transform_hierarchy <in.hier> <out.hier> [--scale S] [--quat w x y z | --axis-angle ax ay az "
          "deg | --matrix <16 numbers, row-major>] [--translate x y z] [--invert] [--half] [--refit cube|ellipsoid|keep]   (at least one of --scale, "
          "--quat, --axis-angle, --matrix, --translate)")
-SIDE_FILES = ("anchors.bin", "exposure.json")
+OPTIONS = {"--scale": 1, "--quat": 4, "--axis-angle": 4, "--matrix": 16, "--translate": 3, "--refit": 1, "--invert": 0,
+           "--half": 0}
 REFIT_MODES = ("cube", "ellipsoid", "keep")
 MATRIX_TOL = 1e-6     # how far a typed matrix may be from a similarity; its rotation is then the nearest one (SVD)
 
@@ -68,44 +67,21 @@ def similarity_from_matrix(m):
 def parse_args(argv):
     """-> dict(in_path, out_path, R or None, quat or None, scale, translate, invert, half, refit or None), None for a
     usage error; a --matrix that is not a similarity raises ``NotASimilarity``."""
-    pos, scale, quat, axis_angle, matrix, translate, invert, half = [], None, None, None, None, None, False, False
-    refit = None
-    take = lambda i, n: [float(x) for x in argv[i + 1:i + 1 + n]] if len(argv) >= i + 1 + n else None
-    i = 0
+    walked = walk_args(argv, OPTIONS)
+    if walked is None:
+        return None
+    pos, seen = walked
+    last = lambda name: ([[float(x) for x in vals] for vals in seen[name]] or [None])[-1]     # the last occurrence wins
     try:
-        while i < len(argv):
-            a = argv[i]
-            width = {"--scale": 1, "--quat": 4, "--axis-angle": 4, "--matrix": 16, "--translate": 3}.get(a)
-            if width is not None:
-                vals = take(i, width)
-                if vals is None:
-                    return None
-                if a == "--scale":
-                    scale = vals[0]
-                elif a == "--quat":
-                    quat = vals
-                elif a == "--axis-angle":
-                    axis_angle = vals
-                elif a == "--matrix":
-                    matrix = vals
-                else:
-                    translate = vals
-                i += 1 + width
-            elif a == "--invert":
-                invert, i = True, i + 1
-            elif a == "--half":
-                half, i = True, i + 1
-            elif a == "--refit":
-                if i + 1 >= len(argv) or argv[i + 1] not in REFIT_MODES:
-                    return None
-                refit, i = argv[i + 1], i + 2
-            elif a.startswith("--"):
-                return None
-            else:
-                pos.append(a)
-                i += 1
+        scale, quat, axis_angle, matrix, translate = (last(k) for k in ("--scale", "--quat", "--axis-angle", "--matrix",
+                                                                        "--translate"))
     except ValueError:
         return None
+    refits = [v[0] for v in seen["--refit"]]
+    if any(v not in REFIT_MODES for v in refits):
+        return None
+    scale, refit = None if scale is None else scale[0], refits[-1] if refits else None
+    invert, half = bool(seen["--invert"]), bool(seen["--half"])
     given = [x is not None for x in (quat, axis_angle, matrix)]
     if len(pos) != 2 or sum(given) > 1 or (matrix is not None and (scale is not None or translate is not None)):
         return None
@@ -138,52 +114,28 @@ def build_similarity(p):
 
 def run(p) -> dict:
     """Read, transform, write; -> figures of the run."""
-    from gaussian_hierarchy._C import load_hierarchy, write_hierarchy
-    from .hierarchy import Hierarchy, refit_boxes_gpu, transform_hierarchy_gpu
-    if not torch.cuda.is_available():
-        raise RuntimeError("hgs.transform_hierarchy transforms on the GPU; no GPU is visible")
+    from .hierarchy import refit_boxes_gpu, transform_hierarchy_gpu
     sim = build_similarity(p)
-    in_path, out_path = p["in_path"], p["out_path"]
-    t0 = time.perf_counter()
-    host = Hierarchy(*load_hierarchy(in_path))
-    t_read = time.perf_counter() - t0
-    N, G = host.num_nodes, int(host.xyz.shape[0])
-    if N < 1 or G < N:
-        raise ValueError(f"{in_path}: G = {G} rows, N = {N} nodes; 1 <= N <= G expected")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    names = ("xyz", "shs", "alpha", "log_scales", "rots", "nodes", "boxes")
-    h = Hierarchy(*(getattr(host, k).to(dev).contiguous() for k in names))
+    host, N, G, read_s = read_input("transform_hierarchy", p["in_path"])
+    h = upload(host)
     stats = {}
     transform_hierarchy_gpu(h, sim, inplace=True, stats=stats)
     if p.get("refit"):
         refit_boxes_gpu(h, p["refit"], inplace=True, stats=stats)
-    t1 = time.perf_counter()
-    out_dir = os.path.dirname(os.path.abspath(out_path))
-    os.makedirs(out_dir, exist_ok=True)
-    write_hierarchy(out_path, *(getattr(h, k).cpu() for k in names), half=p["half"])
-    in_dir = os.path.dirname(os.path.abspath(in_path))
-    beside = [f for f in SIDE_FILES if os.path.exists(os.path.join(in_dir, f))]
-    for f in beside:
-        if in_dir != out_dir:
-            shutil.copyfile(os.path.join(in_dir, f), os.path.join(out_dir, f))
+    write_s = write_output(p["out_path"], h, p["half"])
+    beside, same_dir = carry_side_files(p["in_path"], p["out_path"])
     return dict(nodes=N, tail=G - N, sim=sim, transform_ms=stats["transform_ms"], refit=p.get("refit"),
-                refit_ms=stats.get("refit_ms"), read_s=t_read,
-                write_s=time.perf_counter() - t1, beside=beside, same_dir=in_dir == out_dir, path=out_path)
+                refit_ms=stats.get("refit_ms"), read_s=read_s, write_s=write_s, beside=beside, same_dir=same_dir,
+                path=p["out_path"])
 
 
 def main(argv=None) -> int:
-    argv = sys.argv[1:] if argv is None else list(argv)
     try:
-        p = parse_args(argv)
+        p = parse_args(sys.argv[1:] if argv is None else list(argv))
     except NotASimilarity as e:
-        print(f"transform_hierarchy: --matrix is refused: {e}\n{USAGE}", file=sys.stderr)
-        return 2
-    if p is None:
-        print(USAGE, file=sys.stderr)
-        return 2
-    if not os.path.exists(p["in_path"]):
-        print(f"transform_hierarchy: {p['in_path']} does not exist\n{USAGE}", file=sys.stderr)
-        return 2
+        return usage_exit(USAGE, f"transform_hierarchy: --matrix is refused: {e}")
+    if p is None or missing_path("transform_hierarchy", p["in_path"]):
+        return usage_exit(USAGE)
     r = run(p)
     sim = r["sim"]
     fmt = lambda v: " ".join(f"{x:.9g}" for x in np.asarray(v).reshape(-1))

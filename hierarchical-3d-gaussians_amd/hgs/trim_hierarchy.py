@@ -17,44 +17,30 @@ seconds.  A hierarchy that fails a check is named with the check and the node, n
 ``anchors.bin`` and ``exposure.json`` beside the input are neither copied nor remapped (said so when they exist)."""
 from __future__ import annotations
 
-import os
 import sys
-import time
 
-import torch
+from ._hier_command import (check_exit, missing_path, read_input, side_files_beside, upload, usage_exit, walk_args,
+                            with_tail, write_output)
 
 USAGE = ("usage: python -m hgs.trim_hierarchy <in.hier> <out.hier> [--min-extent E] [--max-nodes K] "
          "[--roi x0 y0 z0 x1 y1 z1]   (at least one option)")
-SIDE_FILES = ("anchors.bin", "exposure.json")
+OPTIONS = {"--min-extent": 1, "--max-nodes": 1, "--roi": 6}
 
 
 def parse_args(argv):
-    """-> (in_path, out_path, min_extent, max_nodes, roi) or None for a usage error (no option at all included)."""
-    pos, min_extent, max_nodes, roi = [], None, None, None
-    i = 0
-    try:
-        while i < len(argv):
-            a = argv[i]
-            if a == "--min-extent":
-                min_extent = float(argv[i + 1])
-                i += 2
-            elif a == "--max-nodes":
-                max_nodes = int(argv[i + 1])
-                i += 2
-            elif a == "--roi":
-                vals = argv[i + 1:i + 7]
-                if len(vals) != 6:
-                    return None
-                v = [float(x) for x in vals]
-                roi = (tuple(v[:3]), tuple(v[3:]))
-                i += 7
-            elif a.startswith("--"):
-                return None
-            else:
-                pos.append(a)
-                i += 1
-    except (IndexError, ValueError):
+    """-> (in_path, out_path, min_extent, max_nodes, roi) or None for a usage error (no option at all included).  The
+    last occurrence of an option wins."""
+    walked = walk_args(argv, OPTIONS)
+    if walked is None:
         return None
+    pos, seen = walked
+    # every occurrence is converted (a bad one is a usage error even when a later one replaces it); absent: None(s)
+    last = lambda name, conv: ([[conv(x) for x in vals] for vals in seen[name]] or [[None] * OPTIONS[name]])[-1]
+    try:
+        (min_extent,), (max_nodes,), roi = last("--min-extent", float), last("--max-nodes", int), last("--roi", float)
+    except ValueError:
+        return None
+    roi = None if roi[0] is None else (tuple(roi[:3]), tuple(roi[3:]))
     if len(pos) != 2 or (min_extent is None and max_nodes is None and roi is None):
         return None
     if (min_extent is not None and min_extent != min_extent) or (max_nodes is not None and max_nodes < 1):
@@ -66,46 +52,25 @@ def parse_args(argv):
 
 def run(in_path, out_path, min_extent=0.0, max_nodes=None, roi=None) -> dict:
     """Read, trim, write; -> figures of the run."""
-    from gaussian_hierarchy._C import load_hierarchy, write_hierarchy
-    from .hierarchy import Hierarchy, trim_hierarchy_gpu
-    if not torch.cuda.is_available():
-        raise RuntimeError("hgs.trim_hierarchy trims on the GPU; no GPU is visible")
-    t0 = time.perf_counter()
-    host = Hierarchy(*load_hierarchy(in_path))
-    t_read = time.perf_counter() - t0
-    N, G = host.num_nodes, int(host.xyz.shape[0])
-    if N < 1 or G < N:
-        raise ValueError(f"{in_path}: G = {G} rows, N = {N} nodes; 1 <= N <= G expected")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    names = ("xyz", "shs", "alpha", "log_scales", "rots")
-    h = Hierarchy(*(getattr(host, k)[:N].to(dev).contiguous() for k in names), host.nodes.to(dev).contiguous(),
-                  host.boxes.to(dev).contiguous())
+    from .hierarchy import trim_hierarchy_gpu
+    host, N, G, read_s = read_input("trim_hierarchy", in_path)
     stats = {}
-    r = trim_hierarchy_gpu(h, min_extent, roi, max_nodes, stats)
-    rows = [torch.cat([getattr(r.hierarchy, k).cpu(), getattr(host, k)[N:]]) for k in names]
-    t1 = time.perf_counter()
-    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-    write_hierarchy(out_path, *rows, r.hierarchy.nodes.cpu(), r.hierarchy.boxes.cpu())
-    beside = [f for f in SIDE_FILES if os.path.exists(os.path.join(os.path.dirname(os.path.abspath(in_path)), f))]
+    r = trim_hierarchy_gpu(upload(host, rows=N), min_extent, roi, max_nodes, stats)
+    write_s = write_output(out_path, with_tail(r.hierarchy, host, N) + [r.hierarchy.nodes, r.hierarchy.boxes])
     return dict(nodes=N, kept=r.hierarchy.num_nodes, stubs=r.stubs, min_extent=r.min_extent, tail=G - N,
-                trim_ms=stats["trim_ms"], read_s=t_read, write_s=time.perf_counter() - t1, beside=beside, path=out_path)
+                trim_ms=stats["trim_ms"], read_s=read_s, write_s=write_s, beside=side_files_beside(in_path),
+                path=out_path)
 
 
 def main(argv=None) -> int:
-    argv = sys.argv[1:] if argv is None else list(argv)
-    parsed = parse_args(argv)
-    if parsed is None:
-        print(USAGE, file=sys.stderr)
-        return 2
-    if not os.path.exists(parsed[0]):
-        print(f"trim_hierarchy: {parsed[0]} does not exist\n{USAGE}", file=sys.stderr)
-        return 2
+    parsed = parse_args(sys.argv[1:] if argv is None else list(argv))
+    if parsed is None or missing_path("trim_hierarchy", parsed[0]):
+        return usage_exit(USAGE)
     from .hierarchy import HierarchyTrimError
     try:
         r = run(*parsed)
     except HierarchyTrimError as e:
-        print(f"trim_hierarchy: {parsed[0]}: {e.check} (node {e.node}): {e}; nothing written", file=sys.stderr)
-        return 1
+        return check_exit("trim_hierarchy", f"{parsed[0]}: {e.check} (node {e.node}): {e}")
     print(f"trim_hierarchy: N = {r['nodes']} -> {r['kept']} nodes ({r['stubs']} stubs), min_extent {r['min_extent']:.9g} "
           f"used, {r['tail']} rows behind the nodes carried through, trim {r['trim_ms']:.2f} ms on the device (read "
           f"{r['read_s']:.2f} s, write {r['write_s']:.2f} s) -> {r['path']}", flush=True)

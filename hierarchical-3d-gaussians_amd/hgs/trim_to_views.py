@@ -25,17 +25,16 @@ and write seconds.  A hierarchy that fails a check is named with the check and t
 from __future__ import annotations
 
 import json
-import os
 import sys
-import time
 
-import torch
-
-from .trim_hierarchy import SIDE_FILES
+from ._hier_command import (check_exit, missing_path, read_input, side_files_beside, upload, usage_exit, walk_args,
+                            with_tail, write_output)
 
 USAGE = ("usage: python -m hgs.trim_to_views <in.hier> <out.hier> (--cameras <cameras.json> | --view x y z ... | "
          "--view-box x0 y0 z0 x1 y1 z1 ...) [--pad R] (--tau T | --tau-px PX --tanfovx X --width W) [--min-extent E] "
          "[--max-nodes K] [--roi x0 y0 z0 x1 y1 z1]")
+SINGLE = ("--cameras", "--pad", "--tau", "--tau-px", "--tanfovx", "--width", "--min-extent", "--max-nodes")
+OPTIONS = {**dict.fromkeys(SINGLE, 1), "--view": 3, "--view-box": 6, "--roi": 6}     # SINGLE and --roi: refused twice
 
 
 def tau_from_pixels(px, tanfovx, width):
@@ -63,43 +62,20 @@ def read_camera_positions(path):
 def parse_args(argv):
     """-> dict(in_path, out_path, cameras, views, view_boxes, pad, tau, min_extent, max_nodes, roi) or None for a usage
     error.  ``tau`` is resolved from --tau-px here."""
-    pos, views, view_boxes = [], [], []
-    one = dict.fromkeys(("--cameras", "--pad", "--tau", "--tau-px", "--tanfovx", "--width", "--min-extent", "--max-nodes"))
-    roi = None
-    i = 0
+    walked = walk_args(argv, OPTIONS)
+    if walked is None or any(len(walked[1][k]) > 1 for k in SINGLE + ("--roi",)):
+        return None
+    pos, seen = walked
+    one = {k: seen[k][0][0] if seen[k] else None for k in SINGLE}
     try:
-        while i < len(argv):
-            a = argv[i]
-            if a in one:
-                if one[a] is not None:
-                    return None
-                one[a] = argv[i + 1]
-                i += 2
-            elif a in ("--view", "--view-box", "--roi"):
-                n = 3 if a == "--view" else 6
-                vals = argv[i + 1:i + 1 + n]
-                if len(vals) != n:
-                    return None
-                v = [float(x) for x in vals]
-                if a == "--view":
-                    views.append(tuple(v))
-                elif a == "--view-box":
-                    view_boxes.append(tuple(v))
-                elif roi is None:
-                    roi = (tuple(v[:3]), tuple(v[3:]))
-                else:
-                    return None
-                i += 1 + n
-            elif a.startswith("--"):
-                return None
-            else:
-                pos.append(a)
-                i += 1
+        views, view_boxes, rois = ([tuple(float(x) for x in vals) for vals in seen[k]]
+                                   for k in ("--view", "--view-box", "--roi"))
         num = {k: (None if one[k] is None else float(one[k])) for k in ("--pad", "--tau", "--tau-px", "--tanfovx",
                                                                         "--width", "--min-extent")}
         max_nodes = None if one["--max-nodes"] is None else int(one["--max-nodes"])
-    except (IndexError, ValueError):
+    except ValueError:
         return None
+    roi = (rois[0][:3], rois[0][3:]) if rois else None
     if len(pos) != 2 or (one["--cameras"] is None and not views and not view_boxes):
         return None
     if any(x is not None and x != x for x in num.values()) or any(x != x for v in views + view_boxes for x in v):
@@ -132,53 +108,29 @@ def regions_of(cameras=None, views=(), view_boxes=(), pad=0.0):
 
 def run(in_path, out_path, regions, tau, min_extent=0.0, max_nodes=None, roi=None) -> dict:
     """Read, trim, write; -> figures of the run."""
-    from gaussian_hierarchy._C import load_hierarchy, write_hierarchy
-    from .hierarchy import Hierarchy, trim_to_views_gpu
-    if not torch.cuda.is_available():
-        raise RuntimeError("hgs.trim_to_views trims on the GPU; no GPU is visible")
-    t0 = time.perf_counter()
-    host = Hierarchy(*load_hierarchy(in_path))
-    t_read = time.perf_counter() - t0
-    N, G = host.num_nodes, int(host.xyz.shape[0])
-    if N < 1 or G < N:
-        raise ValueError(f"{in_path}: G = {G} rows, N = {N} nodes; 1 <= N <= G expected")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    names = ("xyz", "shs", "alpha", "log_scales", "rots")
-    h = Hierarchy(*(getattr(host, k)[:N].to(dev).contiguous() for k in names), host.nodes.to(dev).contiguous(),
-                  host.boxes.to(dev).contiguous())
+    from .hierarchy import trim_to_views_gpu
+    host, N, G, read_s = read_input("trim_to_views", in_path)
     stats = {}
-    r = trim_to_views_gpu(h, regions, tau, min_extent, roi, max_nodes, stats)
-    rows = [torch.cat([getattr(r.hierarchy, k).cpu(), getattr(host, k)[N:]]) for k in names]
-    t1 = time.perf_counter()
-    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-    write_hierarchy(out_path, *rows, r.hierarchy.nodes.cpu(), r.hierarchy.boxes.cpu())
-    beside = [f for f in SIDE_FILES if os.path.exists(os.path.join(os.path.dirname(os.path.abspath(in_path)), f))]
+    r = trim_to_views_gpu(upload(host, rows=N), regions, tau, min_extent, roi, max_nodes, stats)
+    write_s = write_output(out_path, with_tail(r.hierarchy, host, N) + [r.hierarchy.nodes, r.hierarchy.boxes])
     return dict(nodes=N, kept=r.hierarchy.num_nodes, stubs=r.stubs, regions=int(regions[0].shape[0]), tau=r.tau,
                 tail=G - N, reach_ms=stats["reach_ms"], plan_ms=stats["plan_ms"], apply_ms=stats["apply_ms"],
-                read_s=t_read, write_s=time.perf_counter() - t1, beside=beside, path=out_path)
+                read_s=read_s, write_s=write_s, beside=side_files_beside(in_path), path=out_path)
 
 
 def main(argv=None) -> int:
-    argv = sys.argv[1:] if argv is None else list(argv)
-    a = parse_args(argv)
-    if a is None:
-        print(USAGE, file=sys.stderr)
-        return 2
-    for path in (a["in_path"], a["cameras"]):
-        if path is not None and not os.path.exists(path):
-            print(f"trim_to_views: {path} does not exist\n{USAGE}", file=sys.stderr)
-            return 2
+    a = parse_args(sys.argv[1:] if argv is None else list(argv))
+    if a is None or missing_path("trim_to_views", a["in_path"], a["cameras"]):
+        return usage_exit(USAGE)
     try:
         regions = regions_of(a["cameras"], a["views"], a["view_boxes"], a["pad"])
     except (ValueError, OSError) as e:
-        print(f"trim_to_views: {e}\n{USAGE}", file=sys.stderr)
-        return 2
+        return usage_exit(USAGE, f"trim_to_views: {e}")
     from .hierarchy import HierarchyTrimError
     try:
         r = run(a["in_path"], a["out_path"], regions, a["tau"], a["min_extent"], a["max_nodes"], a["roi"])
     except HierarchyTrimError as e:
-        print(f"trim_to_views: {a['in_path']}: {e.check} (node {e.node}): {e}; nothing written", file=sys.stderr)
-        return 1
+        return check_exit("trim_to_views", f"{a['in_path']}: {e.check} (node {e.node}): {e}")
     print(f"trim_to_views: N = {r['nodes']} -> {r['kept']} nodes ({r['stubs']} stubs), {r['regions']} view regions, tau "
           f"{r['tau']:.9g} used, {r['tail']} rows behind the nodes carried through, reach {r['reach_ms']:.2f} ms, plan "
           f"{r['plan_ms']:.2f} ms, apply {r['apply_ms']:.2f} ms on the device (read {r['read_s']:.2f} s, write "
