@@ -892,6 +892,69 @@ int hgs_hier_refit(const hgs_hier_view* in, float* boxes_out, int32_t leaf_mode,
   return launch_hier_refit(*in, boxes_out, leaf_mode, tmp, report, static_cast<hipStream_t>(stream));
 }
 
+size_t hgs_hier_prune_tmp_bytes(int64_t N) {
+  if (N < 1 || N > kHierMaxNodes) return 0;
+  return hier_prune_tmp_bytes(N);
+}
+
+int hgs_hier_prune_plan(const hgs_hier_view* in, const hgs_hier_prune_args* args, const uint8_t* remove, void* tmp,
+                        hgs_hier_prune_report* report, hgs_stream_t stream, int device) {
+  if (!in || !args || !report) { set_error("null argument"); return HGS_ERR_INVALID; }
+  int rc = check_hier_view(in, "input");
+  if (rc) return rc;
+  if (args->remove_boxes < 0 || args->remove_boxes > HGS_HIER_PRUNE_MAX_BOXES) {
+    set_error("bad criteria: %d remove boxes, 0 .. %d expected", args->remove_boxes, HGS_HIER_PRUNE_MAX_BOXES);
+    return HGS_ERR_INVALID;
+  }
+  bool nan = (args->use_min_opacity && std::isnan(args->min_opacity)) || (args->use_max_scale && std::isnan(args->log_max_scale));
+  for (int b = 0; b < args->remove_boxes; ++b)
+    for (int a = 0; a < 3; ++a) nan = nan || std::isnan(args->remove_lo[b][a]) || std::isnan(args->remove_hi[b][a]);
+  for (int a = 0; a < 3 && args->use_keep_box; ++a) nan = nan || std::isnan(args->keep_lo[a]) || std::isnan(args->keep_hi[a]);
+  if (nan) { set_error("bad criteria: a box bound, min_opacity or log_max_scale is NaN"); return HGS_ERR_INVALID; }
+  if ((rc = check_hier_tmp(tmp))) return rc;
+  for (int k = 0; k < 6; ++k) report->first_bad[k] = -1;
+  report->levels = report->root_dead = 0;
+  report->kept = report->removed_leaves = report->dead = report->dirty = report->single_child = report->children_sum = 0;
+  HGS_HIP(hipSetDevice(device));
+  return launch_hier_prune_plan(*in, *args, remove, tmp, report, static_cast<hipStream_t>(stream), device);
+}
+
+int hgs_hier_prune_apply(const hgs_hier_view* in, const hgs_hier_view* out, const void* tmp, int32_t remerge,
+                         int32_t* old_of_new, int32_t* new_of_old, hgs_stream_t stream, int device) {
+  if (!in || !out) { set_error("null argument"); return HGS_ERR_INVALID; }
+  int rc = check_hier_view(in, "input");
+  if (!rc) rc = check_hier_view(out, "output");
+  if (rc) return rc;
+  if (in->M != out->M) { set_error("bad sizes: input M=%d != output M=%d", in->M, out->M); return HGS_ERR_INVALID; }
+  if (!tmp || !old_of_new || !new_of_old) { set_error("null argument"); return HGS_ERR_INVALID; }
+  if ((rc = check_hier_tmp(tmp))) return rc;
+  if (((uintptr_t)old_of_new | (uintptr_t)new_of_old) & 3u) { set_error("old_of_new / new_of_old must be 4-byte aligned"); return HGS_ERR_INVALID; }
+  if (remerge < HGS_HIER_PRUNE_REMERGE_NONE || remerge > HGS_HIER_PRUNE_REMERGE_ALL) {
+    set_error("bad remerge mode %d: 0 (none), 1 (dirty) or 2 (all) expected", remerge);
+    return HGS_ERR_INVALID;
+  }
+  int64_t planned_N = 0, kept = 0;
+  if (!hier_prune_planned(device, tmp, &planned_N, &kept)) {
+    set_error("no successful hgs_hier_prune_plan on this device and tmp");
+    return HGS_ERR_INVALID;
+  }
+  if (in->N != planned_N) { set_error("bad sizes: input N=%lld, the plan was made for N=%lld", (long long)in->N, (long long)planned_N); return HGS_ERR_INVALID; }
+  if (out->N != kept) { set_error("bad sizes: output N=%lld != the plan's kept count %lld", (long long)out->N, (long long)kept); return HGS_ERR_INVALID; }
+  // no output array overlaps its input array (the rows the input shows: N of them)
+  const size_t nin = (size_t)in->N, nout = (size_t)out->N;
+  const struct { const void* a; const void* b; size_t row; const char* name; } pairs[7] = {
+      {in->xyz, out->xyz, 12, "xyz"}, {in->shs, out->shs, 12 * (size_t)in->M, "shs"}, {in->alpha, out->alpha, 4, "alpha"},
+      {in->log_scales, out->log_scales, 12, "log_scales"}, {in->rots, out->rots, 16, "rots"},
+      {in->nodes, out->nodes, 28, "nodes"}, {in->boxes, out->boxes, 32, "boxes"}};
+  for (const auto& pr : pairs) {
+    const uintptr_t a = (uintptr_t)pr.a, b = (uintptr_t)pr.b;
+    if (a < b + nout * pr.row && b < a + nin * pr.row) { set_error("output %s overlaps input %s", pr.name, pr.name); return HGS_ERR_INVALID; }
+  }
+  HGS_HIP(hipSetDevice(device));
+  return launch_hier_prune_apply(*in, *out, tmp, remerge, old_of_new, new_of_old, shs16_ok(in, out),
+                                 static_cast<hipStream_t>(stream), device);
+}
+
 size_t hgs_ssim_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W) {
   if (!ssim_sizes_ok(N, C, H, W)) return 0;
   return ssim_tmp_bytes(N, C, H, W);

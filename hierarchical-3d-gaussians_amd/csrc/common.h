@@ -338,6 +338,15 @@ int launch_hier_transform(const hgs_hier_view& in, const hgs_hier_view& out, con
 size_t hier_refit_tmp_bytes(int64_t N);
 int launch_hier_refit(const hgs_hier_view& in, float* boxes_out, int32_t mode, void* tmp, hgs_hier_refit_report* report,
                       hipStream_t s);
+// leaf removal and re-merge (hier_prune.hip): sizes, pointers, alignment, overlap, the criteria and the mode checked by
+// the caller (1 <= N <= 2^31 - 1).  hier_prune_planned: what the last successful plan on (device, tmp) found (host
+// memory); remove: nullptr or a device byte per node; shs16 as for the trimmer
+size_t hier_prune_tmp_bytes(int64_t N);
+bool hier_prune_planned(int device, const void* tmp, int64_t* N, int64_t* kept);
+int launch_hier_prune_plan(const hgs_hier_view& in, const hgs_hier_prune_args& args, const uint8_t* remove, void* tmp,
+                           hgs_hier_prune_report* report, hipStream_t s, int device);
+int launch_hier_prune_apply(const hgs_hier_view& in, const hgs_hier_view& out, const void* tmp, int32_t remerge,
+                            int32_t* old_of_new, int32_t* new_of_old, bool shs16, hipStream_t s, int device);
 // fused SSIM loss (ssim.hip): ssim_sizes_ok sets the error message; the launches expect sizes it accepted
 bool ssim_sizes_ok(int32_t N, int32_t C, int32_t H, int32_t W);
 size_t ssim_tmp_bytes(int32_t N, int32_t C, int32_t H, int32_t W);

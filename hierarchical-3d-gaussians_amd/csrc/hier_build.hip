@@ -14,6 +14,7 @@
 // (2^d nodes), level D has 2^D nodes of length 1 or 2 (c = P - 2^D of length 2) and level D + 1 the 2c leaves under
 // them.  On level D the ranges tile [0, P) in order, so the number of length-2 nodes in front of node i is l_i - i:
 // its children's place, no prefix sum.
+#include "hier_merge_rule.h"   // the eigen tail of the merge, shared with hier_prune.hip
 #include "hier_nodes.h"
 
 namespace hgs {
@@ -202,75 +203,6 @@ __global__ __launch_bounds__(kHbThreads) void hb_level_kernel(BuildIn in, BuildO
   write_node(in, out, c0 + 1, depth, (int32_t)pid, mid, r.y, c0 + 1 - child_first, mixed, next_first);
 }
 
-// One Jacobi rotation zeroing a[p][q] (r: the third index); v accumulates the rotations (columns = eigenvectors).
-template <int p, int q, int r>
-__device__ __forceinline__ void jacobi_rotate(double (&a)[3][3], double (&v)[3][3]) {
-  const double apq = a[p][q];
-  if (apq == 0.0) return;
-  const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-  const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-  a[p][p] -= t * apq;
-  a[q][q] += t * apq;
-  a[p][q] = a[q][p] = 0.0;
-  const double arp = a[r][p], arq = a[r][q];
-  a[r][p] = a[p][r] = c * arp - s * arq;
-  a[r][q] = a[q][r] = s * arp + c * arq;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double vp = v[k][p], vq = v[k][q];
-    v[k][p] = c * vp - s * vq;
-    v[k][q] = s * vp + c * vq;
-  }
-}
-
-// Eigen-pairs i < j in ascending order (a conditional swap of the values and of the columns of v).
-template <int i, int j>
-__device__ __forceinline__ void order_pair(double (&lam)[3], double (&v)[3][3]) {
-  const bool sw = lam[j] < lam[i];
-  const double li = lam[i], lj = lam[j];
-  lam[i] = sw ? lj : li;
-  lam[j] = sw ? li : lj;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double a = v[k][i], b = v[k][j];
-    v[k][i] = sw ? b : a;
-    v[k][j] = sw ? a : b;
-  }
-}
-
-// Column k of v with its largest-magnitude component (the first of equal ones) positive.
-template <int k>
-__device__ __forceinline__ void orient_column(double (&v)[3][3]) {
-  const double a0 = fabs(v[0][k]), a1 = fabs(v[1][k]), a2 = fabs(v[2][k]);
-  const double lead = (a0 >= a1 && a0 >= a2) ? v[0][k] : (a1 >= a2 ? v[1][k] : v[2][k]);
-  if (lead < 0.0) {
-#pragma unroll
-    for (int r = 0; r < 3; ++r) v[r][k] = -v[r][k];
-  }
-}
-
-// Unit quaternion (w, x, y, z) of the proper rotation m (the spec's _quat_from_rot).
-__device__ __forceinline__ float4 quat_from_rot(const double (&m)[3][3]) {
-  const double tr = m[0][0] + m[1][1] + m[2][2];
-  double q[4];
-  if (tr > 0.0) {
-    const double s = sqrt(fmax(tr + 1.0, 1e-20)) * 2.0;
-    q[0] = 0.25 * s; q[1] = (m[2][1] - m[1][2]) / s; q[2] = (m[0][2] - m[2][0]) / s; q[3] = (m[1][0] - m[0][1]) / s;
-  } else if (m[0][0] >= m[1][1] && m[0][0] >= m[2][2]) {
-    const double s = sqrt(fmax(1.0 + m[0][0] - m[1][1] - m[2][2], 1e-20)) * 2.0;
-    q[0] = (m[2][1] - m[1][2]) / s; q[1] = 0.25 * s; q[2] = (m[0][1] + m[1][0]) / s; q[3] = (m[0][2] + m[2][0]) / s;
-  } else if (m[1][1] >= m[2][2]) {
-    const double s = sqrt(fmax(1.0 + m[1][1] - m[0][0] - m[2][2], 1e-20)) * 2.0;
-    q[0] = (m[0][2] - m[2][0]) / s; q[1] = (m[0][1] + m[1][0]) / s; q[2] = 0.25 * s; q[3] = (m[1][2] + m[2][1]) / s;
-  } else {
-    const double s = sqrt(fmax(1.0 + m[2][2] - m[0][0] - m[1][1], 1e-20)) * 2.0;
-    q[0] = (m[1][0] - m[0][1]) / s; q[1] = (m[0][2] + m[2][0]) / s; q[2] = (m[1][2] + m[2][1]) / s; q[3] = 0.25 * s;
-  }
-  const double inv = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  return make_float4((float)(q[0] * inv), (float)(q[1] * inv), (float)(q[2] * inv), (float)(q[3] * inv));
-}
-
 // One thread per node of level d: an interior node merges its two children (already final).
 __global__ __launch_bounds__(kHbThreads) void hb_merge_kernel(BuildOut out, int64_t first, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * kHbThreads + threadIdx.x;
@@ -328,35 +260,12 @@ __global__ __launch_bounds__(kHbThreads) void hb_merge_kernel(BuildOut out, int6
     bo[0] = make_float4(mn[0], mn[1], mn[2], e);
     bo[1] = make_float4(mx[0], mx[1], mx[2], 0.0f);
   }
-  // rotation and scales: eigen-decomposition of the merged covariance (cyclic Jacobi)
-  double A[3][3] = {{cv[0], cv[1], cv[2]}, {cv[1], cv[3], cv[4]}, {cv[2], cv[4], cv[5]}};
-  double V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-  for (int sweep = 0; sweep < 16; ++sweep) {
-    const double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]);
-    const double diag = fabs(A[0][0]) + fabs(A[1][1]) + fabs(A[2][2]);
-    if (!(off > 1e-18 * diag)) break;
-    jacobi_rotate<0, 1, 2>(A, V);
-    jacobi_rotate<0, 2, 1>(A, V);
-    jacobi_rotate<1, 2, 0>(A, V);
-  }
-  // one parametrisation of the (sign- and order-ambiguous) eigen-decomposition: eigenvalues ascending, as numpy's
-  // eigh; every eigenvector's largest component positive; column 0 negated if that left an improper rotation
-  double lam[3] = {A[0][0], A[1][1], A[2][2]};
-  order_pair<0, 1>(lam, V);
-  order_pair<1, 2>(lam, V);
-  order_pair<0, 1>(lam, V);
-  orient_column<0>(V);
-  orient_column<1>(V);
-  orient_column<2>(V);
-  const double det = V[0][0] * (V[1][1] * V[2][2] - V[1][2] * V[2][1]) - V[0][1] * (V[1][0] * V[2][2] - V[1][2] * V[2][0]) +
-                     V[0][2] * (V[1][0] * V[2][1] - V[1][1] * V[2][0]);
-  if (det < 0.0) {
+  // rotation and scales: the eigen tail of hier_merge_rule.h (cyclic Jacobi, one parametrisation of the decomposition)
+  float ls[3], q[4];
+  merge_cov_to_row(cv, ls, q);
 #pragma unroll
-    for (int r = 0; r < 3; ++r) V[r][0] = -V[r][0];
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) out.log_scales[id * 3 + a] = (float)log(sqrt(fmax(lam[a], 1e-12)));
-  reinterpret_cast<float4*>(out.rots)[id] = quat_from_rot(V);
+  for (int a = 0; a < 3; ++a) out.log_scales[id * 3 + a] = ls[a];
+  reinterpret_cast<float4*>(out.rots)[id] = make_float4(q[0], q[1], q[2], q[3]);
 }
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kHbThreads - 1) / kHbThreads); }

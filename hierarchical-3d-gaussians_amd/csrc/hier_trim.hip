@@ -23,6 +23,7 @@
 //              set is a run of the old order (under an extent floor it is nearly a prefix of the BFS order).
 //
 // Rows at index >= N of the input (a skybox tail) are not read; rows at index >= N' of the output are not written.
+#include "hier_gather.h"   // the maps kernel and the row copy, shared with hier_prune.hip
 #include "hier_nodes.h"
 #include "lod_cut.h"   // the workgroup sums and the launcher of the chained scan (the cut rules in it are not used here)
 
@@ -32,9 +33,7 @@
 namespace hgs {
 namespace {
 
-constexpr int kHtThreads = 256;
-constexpr int kHtRows = 128;            // output rows per workgroup of the gather
-constexpr uint32_t kKeep = 1u, kTest = 2u;   // bits of a node's flag byte
+constexpr uint32_t kTest = 2u;   // bit 1 of a node's flag byte (bit 0: kKeep of hier_gather.h)
 
 // Device half of the report (the kept and stub counts are the two words behind the scanned workgroup sums).
 struct HtResult {
@@ -103,33 +102,6 @@ __global__ __launch_bounds__(1024) void ht_scan_kernel(uint32_t* __restrict__ su
                                                        const uint32_t* __restrict__ block_stubs, int n,
                                                        unsigned long long* __restrict__ chain, int c_off, int chunks) {
   scan_sums_and_unculled_total(sums, block_stubs, n, chain, c_off, chunks);
-}
-
-// One thread per old node: its new index from the scanned workgroup sums, both maps.
-__global__ __launch_bounds__(kHtThreads) void ht_maps_kernel(const uint8_t* __restrict__ flags,
-                                                             const uint32_t* __restrict__ block_sums, int32_t N,
-                                                             int32_t kept, int32_t* __restrict__ old_of_new,
-                                                             int32_t* __restrict__ new_of_old) {
-  const int64_t i = (int64_t)blockIdx.x * kHtThreads + threadIdx.x;
-  const bool keep = i < N && (flags[i] & kKeep) != 0u;
-  const uint32_t pos = block_sums[blockIdx.x] + block_exclusive_offset(keep ? 1u : 0u);
-  if (i < N) {
-    new_of_old[i] = keep ? (int32_t)pos : -1;
-    if (keep && pos < (uint32_t)kept) old_of_new[pos] = (int32_t)i;
-  }
-}
-
-// rows [r0, r0 + rows) of a tensor of `ppr` pieces of type T per row <- the rows src[0 .. rows) of `in`
-template <typename T>
-__device__ __forceinline__ void ht_copy_rows(T* __restrict__ out, const T* __restrict__ in, const int32_t* src,
-                                             int64_t r0, uint32_t rows, uint32_t ppr) {
-  T* o = out + r0 * ppr;
-  const uint32_t L = rows * ppr;
-#pragma unroll 4
-  for (uint32_t u = threadIdx.x; u < L; u += kHtThreads) {
-    const uint32_t jl = u / ppr, k = u - jl * ppr;
-    o[u] = in[(int64_t)src[jl] * ppr + k];
-  }
 }
 
 // One workgroup per kHtRows output rows.  S: 16-byte pieces of an shs row (0: shs goes in W 4-byte pieces).

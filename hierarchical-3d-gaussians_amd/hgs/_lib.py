@@ -95,6 +95,22 @@ class HierRefitReport(C.Structure):
 
 HIER_REFIT_KEEP, HIER_REFIT_CUBE, HIER_REFIT_ELLIPSOID = 0, 1, 2
 
+HIER_PRUNE_MAX_BOXES = 16
+HIER_PRUNE_REMERGE_NONE, HIER_PRUNE_REMERGE_DIRTY, HIER_PRUNE_REMERGE_ALL = 0, 1, 2
+
+
+class HierPruneArgs(C.Structure):
+    _fields_ = [("remove_boxes", C.c_int32), ("use_keep_box", C.c_int32), ("use_min_opacity", C.c_int32),
+                ("use_max_scale", C.c_int32), ("remove_lo", (C.c_float * 3) * HIER_PRUNE_MAX_BOXES),
+                ("remove_hi", (C.c_float * 3) * HIER_PRUNE_MAX_BOXES), ("keep_lo", C.c_float * 3),
+                ("keep_hi", C.c_float * 3), ("min_opacity", C.c_float), ("log_max_scale", C.c_float)]
+
+
+class HierPruneReport(C.Structure):
+    _fields_ = [("first_bad", C.c_int32 * 6), ("levels", C.c_int32), ("root_dead", C.c_int32), ("kept", C.c_int64),
+                ("removed_leaves", C.c_int64), ("dead", C.c_int64), ("dirty", C.c_int64), ("single_child", C.c_int64),
+                ("children_sum", C.c_int64)]
+
 
 class ResidRows(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("means3D", "shs", "opacities", "scales", "rotations")]
@@ -198,6 +214,10 @@ SIGNATURES = {
     "hgs_hier_transform": (C.c_int, [C.POINTER(HierView), C.POINTER(HierView), C.POINTER(HierTransformArgs), _P, C.c_int]),
     "hgs_hier_refit_tmp_bytes": (C.c_size_t, [C.c_int64]),
     "hgs_hier_refit": (C.c_int, [C.POINTER(HierView), _P, C.c_int32, _P, C.POINTER(HierRefitReport), _P, C.c_int]),
+    "hgs_hier_prune_tmp_bytes": (C.c_size_t, [C.c_int64]),
+    "hgs_hier_prune_plan": (C.c_int, [C.POINTER(HierView), C.POINTER(HierPruneArgs), _P, _P, C.POINTER(HierPruneReport), _P,
+                                      C.c_int]),
+    "hgs_hier_prune_apply": (C.c_int, [C.POINTER(HierView), C.POINTER(HierView), _P, C.c_int32, _P, _P, _P, C.c_int]),
     "hgs_ssim_tmp_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "hgs_ssim_fwd": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int]),
     "hgs_ssim_bwd": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,

@@ -17,6 +17,9 @@ granularity.  ``transform_hierarchy`` (the numpy spec) and ``transform_hierarchy
 rotations, scales, boxes and SH bands follow; ``transform_camera`` moves a camera with it.  ``refit_boxes`` (the numpy
 spec) and ``refit_boxes_gpu`` (the same rule on the device, behind ``python -m hgs.refit_hierarchy`` and ``--refit`` on the
 transform command) derive every box again from the rows: leaves first, parents as unions of their children.
+``prune_hierarchy`` (the numpy spec) and ``prune_hierarchy_gpu`` (the same rule on the device, behind
+``python -m hgs.prune_hierarchy``) take leaves out -- boxes, a keep box, an opacity floor, a scale ceiling, a mask --, drop
+what dies with them and re-merge only the ancestors that changed.
 Layout = DESIGN.md '.hier layout':
 
   one Gaussian per node, Gaussian index == node index (``start`` = node id)
@@ -1672,3 +1675,333 @@ def refit_boxes_gpu(h: Hierarchy, leaf="cube", inplace=False, stats=None, report
         # which is what the cached "do these boxes nest?" answer of gaussian_hierarchy._C is keyed on
         h.boxes.reshape(-1)[:0].zero_()
     return h if inplace else Hierarchy(h.xyz, h.shs, h.alpha, h.log_scales, h.rots, h.nodes, boxes_out)
+
+
+# ---- leaf removal: take leaves out, drop what dies with them, re-merge the ancestors that changed -------------------------
+# This project's own rule (DESIGN.md section 4 "Removing leaves (f-21)").  hgs_hier_prune_report.first_bad, in the order
+# they are reported: the three layout checks and the three depth checks of the refit
+PRUNE_CHECKS = REFIT_CHECKS[:6]
+PRUNE_CHILDREN_SUM = REFIT_CHILDREN_SUM
+PRUNE_ROOT_DEAD = "every leaf would be removed"
+PRUNE_REMERGE = {"none": 0, "dirty": 1, "all": 2}      # hgs_hier_prune_apply's remerge
+PRUNE_MAX_BOXES = 16
+PRUNE_MAX_NODES = (1 << 31) - 1
+
+
+class HierarchyPruneError(HierarchyCheckError):
+    """A hierarchy ``prune_hierarchy`` / ``prune_hierarchy_gpu`` rejected (nothing was written): ``check`` (what failed,
+    one of PRUNE_CHECKS, PRUNE_CHILDREN_SUM or PRUNE_ROOT_DEAD) and ``node`` (the first offending node; None for the
+    children sum, 0 for the root)."""
+
+
+@dataclass
+class PruneResult:
+    hierarchy: Hierarchy        # the N' alive nodes, in ascending old order
+    old_of_new: torch.Tensor    # int32 [N']
+    new_of_old: torch.Tensor    # int32 [N], -1 at dead nodes
+    removed_leaves: int         # leaves a criterion removed
+    dead: int                   # N - N': the removed leaves and the nodes all of whose leaves were removed
+    dirty: int                  # alive nodes with a dead or dirty child: their boxes, and by ``remerge`` their rows, changed
+    single_child: int           # alive nodes left with exactly one child (such chains are not spliced)
+
+
+def _as_f32(v, shape, what):
+    a = np.asarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float32)
+    if a.shape != shape or np.isnan(a).any():
+        raise ValueError(f"{what}: {shape} numbers expected (no NaN)")
+    return a
+
+
+def prune_criteria(N, remove_boxes=None, keep_box=None, min_opacity=None, max_scale=None, remove=None):
+    """The criteria of ``prune_hierarchy`` as the numbers both the spec and the device compare: ``boxes`` float32 [k,2,3]
+    (k <= 16 closed boxes (lo, hi)), ``keep`` float32 [2,3] or None, ``min_opacity`` float32 or None, ``log_max_scale``
+    = float32(log(S)) or None -- the logarithm is taken once, here --, ``remove`` uint8 numpy [N] or a uint8 device
+    tensor [N] or None.  NaN bounds, more than 16 boxes and S <= 0 are refused."""
+    boxes = np.zeros((0, 2, 3), dtype=np.float32)
+    if remove_boxes is not None:
+        k = len(remove_boxes)
+        if k > PRUNE_MAX_BOXES:
+            raise ValueError(f"{k} remove boxes; at most {PRUNE_MAX_BOXES} expected")
+        if k:
+            boxes = np.stack([_as_f32(np.stack([np.asarray(b[0], dtype=np.float64), np.asarray(b[1], dtype=np.float64)]),
+                                      (2, 3), "a remove box (lo[3], hi[3])") for b in remove_boxes])
+    keep = None if keep_box is None else _as_f32(np.stack([np.asarray(keep_box[0], dtype=np.float64),
+                                                            np.asarray(keep_box[1], dtype=np.float64)]), (2, 3),
+                                                  "keep_box (lo[3], hi[3])")
+    A = None if min_opacity is None else np.float32(min_opacity)
+    if A is not None and np.isnan(A):
+        raise ValueError("min_opacity is NaN")
+    L = None
+    if max_scale is not None:
+        S = float(max_scale)
+        if not S > 0.0:
+            raise ValueError(f"max_scale = {max_scale}; a positive number expected")
+        L = np.float32(np.log(np.float64(S)))
+    if remove is not None:
+        if torch.is_tensor(remove) and remove.is_cuda:
+            remove = remove.reshape(-1).to(torch.uint8).contiguous()
+        else:
+            remove = (np.asarray(remove.detach().cpu().numpy() if torch.is_tensor(remove) else remove).reshape(-1) != 0) \
+                .astype(np.uint8)
+        if int(remove.shape[0]) != N:
+            raise ValueError(f"remove has {int(remove.shape[0])} entries; N = {N} expected")
+    return dict(boxes=boxes, keep=keep, min_opacity=A, log_max_scale=L, remove=remove)
+
+
+def _inside(x, box):
+    with np.errstate(invalid="ignore"):
+        return ((x >= box[0][None, :]) & (x <= box[1][None, :])).all(1)
+
+
+def prune_removed(xyz, alpha, log_scales, crit):
+    """Step 1 of the rule at every row of float32 numpy (xyz [n,3], alpha [n], log_scales [n,3]) -> bool [n]; the caller
+    masks it with count_children == 0.  float32 comparisons only; a NaN mean is in no box."""
+    n = xyz.shape[0]
+    r = np.zeros(n, dtype=bool)
+    for b in crit["boxes"]:
+        r |= _inside(xyz, b)
+    if crit["keep"] is not None:
+        r |= ~_inside(xyz, crit["keep"])
+    with np.errstate(invalid="ignore"):
+        if crit["min_opacity"] is not None:
+            r |= ~(alpha >= crit["min_opacity"])
+        if crit["log_max_scale"] is not None:
+            r |= ~(log_scales.max(axis=1) <= crit["log_max_scale"])          # (np.max propagates a NaN)
+    if crit["remove"] is not None:
+        rm = crit["remove"]
+        r |= (rm.cpu().numpy() if torch.is_tensor(rm) else rm) != 0
+    return r
+
+
+def _children_of(ids, sc, cc):
+    """-> (kids, starts): the children of ``ids`` one after another, and where each node's run starts (for reduceat)."""
+    starts = np.concatenate([[0], np.cumsum(cc[ids])[:-1]])
+    kids = np.repeat(sc[ids] - starts, cc[ids]) + np.arange(int(cc[ids].sum()))
+    return kids, starts
+
+
+def merge_rows(xyz, shs, alpha, log_scales, rots, counts, weights=None):
+    """The merge rule of an interior node generalised to k children ("Interior nodes"; the float64
+    numpy statement of csrc/hier_merge_rule.h).  The children's rows are float32 numpy arrays, node after node: node j
+    owns the next ``counts[j]`` rows.  w_c = ``weights`` (float64, one per child row: what ``prune_hierarchy`` carries
+    up from the leaves) or, without them, alpha_c exp(ls_c0) exp(ls_c1) exp(ls_c2) of the row; f_c = w_c / max(sum w_c, 1e-30);
+    mean = sum f_c x_c; covariance = sum f_c (R_c diag(s_c^2) R_c^T + d_c d_c^T) with R_c = _rot_from_quat of the
+    stored quaternion; SH and opacity = f-weighted averages, opacity clipped to [0, 1]; eigenvalues ascending and
+    clamped at 1e-12, every eigenvector's largest component (the first of equal ones) positive, column 0 negated if
+    the frame is improper.  Every sum runs over a node's children left to right.
+    -> dict of float64 arrays: xyz [n,3], shs [n,W], alpha [n], log_scales [n,3], rots [n,4], cov [n,3,3]."""
+    counts = np.asarray(counts, dtype=np.int64)
+    n = counts.shape[0]
+    first = np.concatenate([[0], np.cumsum(counts)[:-1]]) if n else np.zeros(0, dtype=np.int64)
+    x = np.asarray(xyz, dtype=np.float32).reshape(-1, 3).astype(np.float64)
+    sh = np.asarray(shs, dtype=np.float32).reshape(x.shape[0], -1).astype(np.float64)
+    al = np.asarray(alpha, dtype=np.float32).reshape(-1).astype(np.float64)
+    ls = np.asarray(log_scales, dtype=np.float32).reshape(-1, 3).astype(np.float64)
+    q = np.asarray(rots, dtype=np.float32).reshape(-1, 4).astype(np.float64)
+    with np.errstate(all="ignore"):
+        s = np.exp(ls)
+        w = al * ((s[:, 0] * s[:, 1]) * s[:, 2]) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+        R = _rot_from_quat(q)
+        C = (R * (s * s)[:, None, :]) @ R.transpose(0, 2, 1)
+        kmax = int(counts.max()) if n else 0
+        slot = lambda j: (counts > j, np.where(counts > j, first + j, first))     # (a node without slot j: f = 0 there)
+        total = np.zeros(n)
+        for j in range(kmax):
+            m, c = slot(j)
+            total = total + np.where(m, w[c], 0.0)
+        ws = np.maximum(total, 1e-30)
+        mu, op, shm = np.zeros((n, 3)), np.zeros(n), np.zeros((n, sh.shape[1]))
+        for j in range(kmax):
+            m, c = slot(j)
+            f = np.where(m, w[c] / ws, 0.0)
+            mu = mu + f[:, None] * x[c]
+            op = op + f * al[c]
+            shm = shm + f[:, None] * sh[c]
+        cov = np.zeros((n, 3, 3))
+        for j in range(kmax):
+            m, c = slot(j)
+            f = np.where(m, w[c] / ws, 0.0)
+            d = x[c] - mu
+            cov = cov + f[:, None, None] * (C[c] + d[:, :, None] * d[:, None, :])
+        evals, evecs = np.linalg.eigh(cov) if n else (np.zeros((0, 3)), np.zeros((0, 3, 3)))
+        evals = np.maximum(evals, 1e-12)
+        lead = np.argmax(np.abs(evecs), axis=1)                      # per column, the first of equal ones
+        sign = np.where(np.take_along_axis(evecs, lead[:, None, :], axis=1)[:, 0, :] < 0, -1.0, 1.0)
+        evecs = evecs * sign[:, None, :]
+        flip = np.linalg.det(evecs) < 0
+        evecs[flip, :, 0] *= -1
+        quat = _quat_from_rot(evecs) if n else np.zeros((0, 4))
+    return dict(xyz=mu, shs=shm, alpha=np.clip(op, 0.0, 1.0), log_scales=np.log(np.sqrt(evals)), rots=quat, cov=cov, weight=ws)
+
+
+def prune_hierarchy(h: Hierarchy, *, remove_boxes=None, keep_box=None, min_opacity=None, max_scale=None, remove=None,
+                    remerge="dirty") -> PruneResult:
+    """Remove leaves from a hierarchy, drop every node all of whose leaves went, and re-merge the ancestors that changed
+    (the numpy spec, float64 where it computes rows; ``prune_hierarchy_gpu`` is the same rule on the device).  This
+    project's own rule.
+    A node without children is REMOVED iff a given criterion holds, all in float32: its mean lies in one of the closed
+    ``remove_boxes`` [(lo[3], hi[3]), ...] (at most 16; a NaN coordinate is in no box); its mean does not lie in
+    ``keep_box`` (lo[3], hi[3]); not (alpha >= ``min_opacity``); not (max(log_scales) <= float32(log(``max_scale``)));
+    ``remove`` (uint8 [N]) is nonzero at it.  Bottom-up, a leaf is ALIVE iff it is not removed and a node with children
+    iff one of its children is; an alive node with children is DIRTY iff one of its children is dead or dirty.  The
+    alive nodes keep their ascending order: depth, count_leafs and count_merged kept, parent / start / start_children
+    renumbered, count_children = the surviving children (a node left with one child stays).  Leaves and clean nodes
+    are bit copies.  A dirty node's box is the union of its surviving children's final boxes (extent = its largest edge,
+    boxes[n,1,3] copied), in every ``remerge`` mode; its row is ``merge_rows`` of its surviving children's final
+    float32 rows, deepest level first, with the weights the builder carries: a leaf weighs alpha s0 s1 s2 of its row
+    (s = exp(log_scales), double), a node with children the sum of its surviving children's weights, clamped at 1e-30
+    -- the sum over its surviving leaves, not alpha s0 s1 s2 of its own merged row.  ``remerge="none"`` keeps the dirty rows (a topology-only prune);
+    ``remerge="all"`` recomputes the row of every alive node with children (clean ones keep their boxes).  Rows at
+    index >= N are not the function's business: the result has G = N' rows.  Removing nothing returns the input's bits.
+    Refused with ``HierarchyPruneError`` (check, first offending node), before anything is computed: the six checks of
+    PRUNE_CHECKS, a count_children sum other than N - 1, and a dead root.  -> PruneResult (host tensors)."""
+    if remerge not in PRUNE_REMERGE:
+        raise ValueError(f"remerge = {remerge!r}; one of {', '.join(PRUNE_REMERGE)} expected")
+    nodes = h.nodes.detach().cpu().numpy().astype(np.int32)
+    N, G = nodes.shape[0], int(h.xyz.shape[0])
+    if N < 1 or G < N or N > PRUNE_MAX_NODES:
+        raise ValueError(f"G = {G} rows, N = {N} nodes; 1 <= N <= G, N <= 2^31 - 1 expected")
+    crit = prune_criteria(N, remove_boxes, keep_box, min_opacity, max_scale, remove)
+    np32 = lambda v: v.detach().cpu().numpy().astype(np.float32)
+    rows = {k: np32(getattr(h, k))[:N].copy() for k in ("xyz", "shs", "alpha", "log_scales", "rots")}
+    boxes = np32(h.boxes).reshape(-1, 2, 4).copy()
+    assert boxes.shape[0] == N
+    first_bad, children_sum = refit_first_bad(nodes, np.zeros((N, 3), np.float32), np.zeros((N, 3), np.float32))
+    refuse = lambda check, node: HierarchyPruneError(check, node, f"not a hierarchy that can be pruned: {check} (first "
+                                                                  f"offending node {node}); nothing was written")
+    _raise_first_bad(PRUNE_CHECKS, first_bad[:6], refuse)
+    if children_sum != N - 1:
+        raise HierarchyPruneError(PRUNE_CHILDREN_SUM, None, f"not a hierarchy that can be pruned: count_children sums to "
+                                                            f"{children_sum} over {N} nodes; nothing was written")
+    depth, sc, cc = nodes[:, 0].astype(np.int64), nodes[:, 5].astype(np.int64), nodes[:, 6].astype(np.int64)
+    # ---- 1-3: removed, alive, dirty
+    removed = (cc == 0) & prune_removed(rows["xyz"], rows["alpha"].reshape(-1), rows["log_scales"], crit)
+    alive = (cc == 0) & ~removed
+    dirty = np.zeros(N, dtype=bool)
+    surviving, first_alive = np.zeros(N, dtype=np.int64), np.zeros(N, dtype=np.int64)
+    for d in range(int(depth.max()) - 1, -1, -1):              # children before parents
+        ids = np.nonzero((depth == d) & (cc > 0))[0]
+        if ids.size == 0:
+            continue
+        kids, starts = _children_of(ids, sc, cc)
+        a = alive[kids]
+        n = np.add.reduceat(a.astype(np.int64), starts)
+        alive[ids] = n > 0
+        dirty[ids] = (n > 0) & np.logical_or.reduceat(~a | dirty[kids], starts)
+        surviving[ids] = n
+        first_alive[ids] = np.minimum.reduceat(np.where(a, kids, N), starts)
+    if not alive[0]:
+        raise HierarchyPruneError(PRUNE_ROOT_DEAD, 0, f"{PRUNE_ROOT_DEAD} ({int(removed.sum())} of {N} nodes are leaves a "
+                                                      f"criterion removes); nothing was written")
+    # ---- 4: topology
+    old = np.nonzero(alive)[0]
+    K = old.size
+    new_of_old = np.full(N, -1, dtype=np.int32)
+    new_of_old[old] = np.arange(K, dtype=np.int32)
+    out = nodes[old].copy()
+    out[:, 1] = np.where(old == 0, -1, new_of_old[np.maximum(nodes[old, 1], 0)])
+    out[:, 2] = np.arange(K, dtype=np.int32)
+    inner = cc[old] > 0
+    out[inner, 5] = new_of_old[first_alive[old[inner]]]
+    out[inner, 6] = surviving[old[inner]]
+    # ---- 5, 6: rows and boxes, deepest level first, from the children's FINAL float32 rows
+    r = {k: v[old] for k, v in rows.items()}
+    b = boxes[old]
+    odepth, osc, occ, odirty = out[:, 0].astype(np.int64), out[:, 5].astype(np.int64), out[:, 6].astype(np.int64), dirty[old]
+    with np.errstate(all="ignore"):
+        sl = np.exp(r["log_scales"].astype(np.float64))
+        weight = np.where(occ == 0, r["alpha"].reshape(K).astype(np.float64) * ((sl[:, 0] * sl[:, 1]) * sl[:, 2]), 0.0)
+    for d in range(int(odepth.max()) - 1, -1, -1):
+        level = (odepth == d) & (occ > 0)
+        ids = np.nonzero(level)[0]
+        if ids.size and remerge != "none":                     # the carried weights, at clean nodes too
+            kids, _ = _children_of(ids, osc, occ)
+            total, first = np.zeros(ids.size), osc[ids]
+            for j in range(int(occ[ids].max())):
+                total = total + np.where(occ[ids] > j, weight[np.where(occ[ids] > j, first + j, first)], 0.0)
+            weight[ids] = np.maximum(total, 1e-30)
+        ids = np.nonzero(level & odirty)[0]
+        if ids.size:
+            kids, starts = _children_of(ids, osc, occ)
+            lo = np.minimum.reduceat(b[kids, 0, :3], starts, axis=0)
+            hi = np.maximum.reduceat(b[kids, 1, :3], starts, axis=0)
+            b[ids, 0, :3], b[ids, 1, :3] = lo, hi
+            b[ids, 0, 3] = _box_extent(lo, hi)
+        ids = np.nonzero(level & {"none": np.zeros(K, dtype=bool), "dirty": odirty, "all": np.ones(K, dtype=bool)}[remerge])[0]
+        if ids.size:
+            kids, _ = _children_of(ids, osc, occ)
+            m = merge_rows(r["xyz"][kids], r["shs"][kids], r["alpha"][kids], r["log_scales"][kids], r["rots"][kids], occ[ids],
+                           weight[kids])
+            for k in ("xyz", "log_scales", "rots"):
+                r[k][ids] = m[k].astype(np.float32)
+            r["shs"][ids] = m["shs"].astype(np.float32).reshape((ids.size,) + r["shs"].shape[1:])
+            r["alpha"][ids] = m["alpha"].astype(np.float32).reshape((ids.size,) + r["alpha"].shape[1:])
+    t = torch.from_numpy
+    ph = Hierarchy(xyz=t(r["xyz"]), shs=t(r["shs"]), alpha=t(r["alpha"]), log_scales=t(r["log_scales"]), rots=t(r["rots"]),
+                   nodes=t(out), boxes=t(b).reshape((K,) + tuple(h.boxes.shape[1:])))
+    return PruneResult(ph, t(old.astype(np.int32)), t(new_of_old), int(removed.sum()), int(N - K), int(dirty.sum()),
+                       int((occ == 1).sum()))
+
+
+def prune_hierarchy_gpu(h: Hierarchy, *, remove_boxes=None, keep_box=None, min_opacity=None, max_scale=None, remove=None,
+                        remerge="dirty", align=False, stats=None) -> PruneResult:
+    """``prune_hierarchy`` on the GPU (csrc/hier_prune.hip: hgs_hier_prune_plan, then N' rows are allocated, then
+    hgs_hier_prune_apply).  ``h``: contiguous device tensors (float32 rows of G >= N, int32 nodes [N,7], boxes
+    [N,2,4]); it is not modified, and rows behind the N nodes are not read.  ``remove``: uint8 or bool [N], host or
+    device.  The records, the boxes, both maps, the counts and every row that is copied equal the spec's bit for bit; a
+    re-merged row agrees with it within the builder's bounds (mean, SH, opacity 1e-5; covariance 1e-5 Frobenius): the
+    frame of a near-isotropic covariance is free.  Re-merged rows come in the builder's canonical frame, not their
+    parents': ``align=True`` runs ``align_hierarchy_gpu`` on the result.  A hierarchy that fails a check, or all of whose
+    leaves would go, raises ``HierarchyPruneError`` naming the check and the node; nothing has been allocated or written
+    then.  Two host waits (the level sizes and the checks; the counts), the rest is asynchronous on the current stream.
+    ``stats`` (a dict, optional) receives ``prune_ms`` (device events around plan, the allocation and apply), its parts
+    ``plan_ms`` and ``apply_ms``, and ``levels``.  No CPU fallback: raises without libhgs.so or a GPU."""
+    lib, _ = _need_gpu("prune_hierarchy_gpu", "prune_hierarchy")
+    if remerge not in PRUNE_REMERGE:
+        raise ValueError(f"remerge = {remerge!r}; one of {', '.join(PRUNE_REMERGE)} expected")
+    G, N, M = _tensor_sizes(h)
+    if N < 1 or G < N or N > PRUNE_MAX_NODES:
+        raise ValueError(f"G = {G} rows, N = {N} nodes; 1 <= N <= G, N <= 2^31 - 1 expected")
+    dev = _device_rows(h, _ROWS, "prune_hierarchy_gpu")
+    crit = prune_criteria(N, remove_boxes, keep_box, min_opacity, max_scale, remove)
+    args = _lib.HierPruneArgs(len(crit["boxes"]), 0 if crit["keep"] is None else 1, 0 if crit["min_opacity"] is None else 1,
+                              0 if crit["log_max_scale"] is None else 1)
+    for k, bx in enumerate(crit["boxes"]):
+        args.remove_lo[k][:], args.remove_hi[k][:] = [float(x) for x in bx[0]], [float(x) for x in bx[1]]
+    if crit["keep"] is not None:
+        args.keep_lo[:], args.keep_hi[:] = [float(x) for x in crit["keep"][0]], [float(x) for x in crit["keep"][1]]
+    args.min_opacity = 0.0 if crit["min_opacity"] is None else float(crit["min_opacity"])
+    args.log_max_scale = 0.0 if crit["log_max_scale"] is None else float(crit["log_max_scale"])
+    mask = crit["remove"]
+    if mask is not None:
+        mask = (mask if torch.is_tensor(mask) else torch.from_numpy(mask)).to(dev).contiguous()
+    p = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev), _device_events(stats, "prune_ms") as ev:
+        tmp = torch.empty(lib.hgs_hier_prune_tmp_bytes(N), dtype=torch.uint8, device=dev)
+        rep = _lib.HierPruneReport()
+        rep.first_bad[:] = [-1] * 6              # (a call that fails its size checks does not fill the report)
+        vin, stream = _hier_view(h, G, N, M), _stream(dev)
+        rc = lib.hgs_hier_prune_plan(C.byref(vin), C.byref(args), p(mask), p(tmp), C.byref(rep), stream, dev.index or 0)
+        if rc != 0:
+            msg = (lib.hgs_last_error() or b"?").decode()
+            _raise_first_bad(PRUNE_CHECKS, rep.first_bad,
+                             lambda check, node: HierarchyPruneError(check, node, f"hgs_hier_prune_plan: {msg}"))
+            if rc == 1 and "count_children sums to" in msg:
+                raise HierarchyPruneError(PRUNE_CHILDREN_SUM, None, f"hgs_hier_prune_plan: {msg}")
+            if rc == 1 and rep.root_dead:
+                raise HierarchyPruneError(PRUNE_ROOT_DEAD, 0, f"hgs_hier_prune_plan: {msg}")
+            raise _lib.HgsError(f"hgs_hier_prune_plan failed (code {rc}): {msg}", rc)
+        n = int(rep.kept)
+        out = _empty_hierarchy(dev, n, h.shs.shape[1:], h.alpha.shape[1:])
+        old_of_new, new_of_old = (torch.empty(m, dtype=torch.int32, device=dev) for m in (n, N))
+        mid = torch.cuda.Event(enable_timing=True)
+        mid.record()
+        _lib.check(lib.hgs_hier_prune_apply(C.byref(vin), C.byref(_hier_view(out, n, n, M)), p(tmp), PRUNE_REMERGE[remerge],
+                                            p(old_of_new), p(new_of_old), stream, dev.index or 0), "hgs_hier_prune_apply")
+    if stats is not None:
+        stats["plan_ms"], stats["apply_ms"], stats["levels"] = ev[0].elapsed_time(mid), mid.elapsed_time(ev[1]), int(rep.levels)
+    if align:
+        align_hierarchy_gpu(out)
+    out.boxes = out.boxes.reshape((n,) + tuple(h.boxes.shape[1:]))
+    return PruneResult(out, old_of_new, new_of_old, int(rep.removed_leaves), int(rep.dead), int(rep.dirty),
+                       int(rep.single_child))

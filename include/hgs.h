@@ -747,6 +747,80 @@ int hgs_hier_refit(const hgs_hier_view* in, float* boxes_out, int32_t leaf_mode,
                    hgs_stream_t stream, int device);
 
 /* ---------------------------------------------------------------------------
+ * Removing leaves from a hierarchy on the device and re-merging their ancestors: the rule of
+ * hgs.hierarchy.prune_hierarchy (this project's own rule).  Input: a hierarchy
+ * in this project's layout, G >= N; rows at index >= N are not read.
+ *   removed  a node with count_children == 0 is removed iff a criterion of `args` holds, all in float32:
+ *            its mean lies inside one of the remove_boxes closed boxes (a NaN coordinate is never inside); use_keep_box
+ *            and its mean is not inside [keep_lo, keep_hi]; use_min_opacity and not (alpha >= min_opacity);
+ *            use_max_scale and not (max_k log_scales_k <= log_max_scale) -- the caller passes the LOGARITHM, rounded to
+ *            float32 once; `remove` (NULL, or a device uint8 [N]) is nonzero at the node.  Entries of `remove` at nodes
+ *            with children are ignored.
+ *   alive    bottom-up: a leaf iff it is not removed, a node with children iff one of its children is.  Dead nodes are
+ *            dropped; a dead node 0 refuses the call ("every leaf would be removed").
+ *   dirty    an alive node with children one of whose children is dead or dirty.
+ *   records  the N' alive nodes in ascending old order (surviving children stay contiguous): depth, count_leafs and
+ *            count_merged kept; parent = new_of_old[parent] (-1 at node 0), start = the new index, start_children =
+ *            new_of_old[first surviving child], count_children = the surviving children (1 is allowed: such chains are
+ *            not spliced); a node without children keeps its record but parent and start.
+ *   rows     leaves and clean nodes: rows and boxes bit for bit.  A dirty node: its box is the union of its surviving
+ *            children's FINAL boxes, boxes[n,0,3] the largest edge (a float32 subtraction), boxes[n,1,3] copied -- in
+ *            every re-merge mode; its row, deepest level first, from its surviving children's final float32 rows:
+ *            w_c = the weight the builder carries: alpha_c exp(ls_c0) exp(ls_c1) exp(ls_c2) of a child without
+ *            children, max(sum of its surviving children's weights, 1e-30) of a child with children (the sum over its
+ *            surviving leaves, not the product of its own merged row); f_c = w_c / max(sum_c w_c, 1e-30); mean = sum f_c x_c;
+ *            covariance = sum f_c (R_c diag(s_c^2) R_c^T + d_c d_c^T), d_c = x_c - mean, R_c the matrix of the stored
+ *            quaternion (w,x,y,z); SH and opacity = the f-weighted averages, opacity clipped to [0, 1]; scales and
+ *            rotation = the builder's cyclic Jacobi solve and parametrisation (eigenvalues ascending, clamped at 1e-12,
+ *            each axis' largest component positive, column 0 negated if improper).  All in double, one rounding.
+ *   remerge  HGS_HIER_PRUNE_REMERGE_DIRTY: as above; _NONE: dirty nodes keep their rows (boxes are still unions): a
+ *            topology-only prune; _ALL: every alive node with children gets its row again (clean ones keep their boxes).
+ * hgs_hier_prune_tmp_bytes: host only (no GPU needed); 0 for an N outside [1, 2^31 - 1].
+ * hgs_hier_prune_plan: the checks of hgs_hier_refit_report [0..5] and the count_children sum, the level lists, the
+ * removal test, alive and dirty bottom-up (one launch per depth), a scan; TWO host waits; the second reads `report`.  A
+ * failed check or a dead root returns HGS_ERR_INVALID with the check and the node in the message and in `report`; no
+ * output exists yet, so none is touched.  tmp: hgs_hier_prune_tmp_bytes(N) of device memory, 256-byte aligned; it
+ * carries the plan to the apply call.
+ * hgs_hier_prune_apply: asynchronous on `stream` (the plan's, or one ordered behind it).  out: N = report.kept, G >= N,
+ * the same M, memory that does not overlap the input's.  old_of_new int32 [N'], new_of_old int32 [N] (-1 at the dead).
+ * Both check sizes, pointers and alignment before any HIP call (as hgs_hier_trim_plan / _apply do); more than 16 remove
+ * boxes, a NaN bound or threshold and a remerge outside {0, 1, 2} are refused; apply refuses a (device, tmp) pair without
+ * a successful plan, an in->N other than the plan's, an out->N other than its kept count, and an output array that
+ * overlaps its input array. */
+#define HGS_HIER_PRUNE_MAX_BOXES 16
+#define HGS_HIER_PRUNE_REMERGE_NONE 0
+#define HGS_HIER_PRUNE_REMERGE_DIRTY 1
+#define HGS_HIER_PRUNE_REMERGE_ALL 2
+typedef struct hgs_hier_prune_args {
+  int32_t remove_boxes;     /* how many of remove_lo / remove_hi are in use: 0 .. 16 */
+  int32_t use_keep_box;
+  int32_t use_min_opacity;
+  int32_t use_max_scale;
+  float remove_lo[HGS_HIER_PRUNE_MAX_BOXES][3];
+  float remove_hi[HGS_HIER_PRUNE_MAX_BOXES][3];
+  float keep_lo[3];
+  float keep_hi[3];
+  float min_opacity;
+  float log_max_scale;      /* float32(log(S)) */
+} hgs_hier_prune_args;
+typedef struct hgs_hier_prune_report {
+  int32_t first_bad[6];   /* first offending node per check, -1 if none: hgs_hier_refit_report's [0] .. [5] */
+  int32_t levels;         /* depths in use */
+  int32_t root_dead;      /* != 0: every leaf would be removed (the call is refused) */
+  int64_t kept;           /* N': alive nodes */
+  int64_t removed_leaves; /* leaves a criterion removes */
+  int64_t dead;           /* N - N' */
+  int64_t dirty;          /* alive nodes with a dead or dirty child */
+  int64_t single_child;   /* alive nodes left with exactly one child */
+  int64_t children_sum;   /* N - 1, or the call is refused */
+} hgs_hier_prune_report;
+size_t hgs_hier_prune_tmp_bytes(int64_t N);
+int hgs_hier_prune_plan(const hgs_hier_view* in, const hgs_hier_prune_args* args, const uint8_t* remove, void* tmp,
+                        hgs_hier_prune_report* report, hgs_stream_t stream, int device);
+int hgs_hier_prune_apply(const hgs_hier_view* in, const hgs_hier_view* out, const void* tmp, int32_t remerge,
+                         int32_t* old_of_new, int32_t* new_of_old, hgs_stream_t stream, int device);
+
+/* ---------------------------------------------------------------------------
  * Fused SSIM loss (hgs.loss.ssim): the standard SSIM of the reference's loss -- an 11-tap
  * Gaussian window (sigma 1.5, normalised to sum 1) applied separably, zero padding, C1 = 0.01^2, C2 = 0.03^2 -- of
  * img1 against img2, both float32 [N,C,H,W] contiguous on the device, and its gradient with respect to img1.
