@@ -206,24 +206,13 @@ def test_million_leaf_hierarchy_cut_and_render(gpu):
         print(f"tau={tau_px}px: cut {n} of {G} nodes, mean colour {float(color.mean()):.4f}")
 
 
-@pytest.mark.parametrize("skybox", [0, 37])
-def test_in_op_lod_interpolation_matches_python_glue(gpu, skybox):
-    """SURVEY §8 f-1: render_indices / parent_indices passed NON-empty to the op must reproduce exactly what
-    render_post's Python block (gaussian_renderer/__init__.py:199-234, restated here in torch) feeds it,
-    forward and backward (gradients land on node AND parent rows) -- including the skybox rows the reference appends
-    from the TAIL of the arrays with weight 1 / 1 sibling (:220-234; RasterContext.skybox_points here)."""
+def in_op_lod_against_python_glue(gpu, h, cam, skybox, n, ri, pi, w, ns):
+    """The body of test_in_op_lod_interpolation_matches_python_glue behind its cut: ``h`` a host hierarchy, ``ri``,
+    ``pi``, ``w``, ``ns`` device tensors of G = N + skybox entries whose first ``n`` hold a cut of it (also called by
+    tests/test_hier_chain_gpu.py on a pruned hierarchy)."""
     import diff_gaussian_rasterization as dgr
     import parity as pa
-    from gaussian_hierarchy._C import expand_to_size, get_interpolation_weights
-    h, cam, nodes, boxes = _setup(4000, gpu, seed=9)
-    Gh = h.xyz.shape[0]
-    G = Gh + skybox
-    ri = torch.zeros(G, dtype=torch.int32, device=gpu); pi = torch.zeros_like(ri); ni = torch.zeros_like(ri)
-    w = torch.zeros(G, device=gpu); ns = torch.zeros(G, dtype=torch.int32, device=gpu)
-    tau = (2 * (4 + 0.5)) * cam.tanfovx / (0.5 * cam.image_width)
-    n = expand_to_size(nodes, boxes, tau, cam.camera_center.to(gpu), torch.zeros(3), ri, pi, ni)
-    assert 0 < n < Gh
-    get_interpolation_weights(ni[:n], tau, nodes, boxes, cam.camera_center.cpu(), torch.zeros(3), w, ns)
+    G = h.xyz.shape[0] + skybox
     gc, gd = synth.upstream_grads(cam.image_height, cam.image_width)
     gc = gc.to(gpu)
     sky = synth.make_scene(max(skybox, 1), cam, seed=77, s_px=(6.0, 20.0), z_range=(25.0, 40.0))   # far, large
@@ -277,6 +266,25 @@ def test_in_op_lod_interpolation_matches_python_glue(gpu, skybox):
         assert float(gb[~touched].abs().sum()) == 0.0
         if skybox:
             assert float(gb[sk].abs().sum()) > 0.0
+
+
+@pytest.mark.parametrize("skybox", [0, 37])
+def test_in_op_lod_interpolation_matches_python_glue(gpu, skybox):
+    """SURVEY §8 f-1: render_indices / parent_indices passed NON-empty to the op must reproduce exactly what
+    render_post's Python block (gaussian_renderer/__init__.py:199-234, restated here in torch) feeds it,
+    forward and backward (gradients land on node AND parent rows) -- including the skybox rows the reference appends
+    from the TAIL of the arrays with weight 1 / 1 sibling (:220-234; RasterContext.skybox_points here)."""
+    from gaussian_hierarchy._C import expand_to_size, get_interpolation_weights
+    h, cam, nodes, boxes = _setup(4000, gpu, seed=9)
+    Gh = h.xyz.shape[0]
+    G = Gh + skybox
+    ri = torch.zeros(G, dtype=torch.int32, device=gpu); pi = torch.zeros_like(ri); ni = torch.zeros_like(ri)
+    w = torch.zeros(G, device=gpu); ns = torch.zeros(G, dtype=torch.int32, device=gpu)
+    tau = (2 * (4 + 0.5)) * cam.tanfovx / (0.5 * cam.image_width)
+    n = expand_to_size(nodes, boxes, tau, cam.camera_center.to(gpu), torch.zeros(3), ri, pi, ni)
+    assert 0 < n < Gh
+    get_interpolation_weights(ni[:n], tau, nodes, boxes, cam.camera_center.cpu(), torch.zeros(3), w, ns)
+    in_op_lod_against_python_glue(gpu, h, cam, skybox, n, ri, pi, w, ns)
 
 
 @pytest.mark.parametrize("order", ["as_emitted", "shuffled"])
