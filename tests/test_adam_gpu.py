@@ -70,9 +70,14 @@ def test_million_rows_against_oracle_and_throughput(gpu):
             p, m, v = ao.adam_rows(p, grads[k].numpy(), m, v, it + 1, rel.numpy(), lr=ac.LRS[k], eps=ac.EPS)
         assert ac.rel_err(params[k].detach().cpu().numpy(), p) <= TOL, k
         assert ac.rel_err(opt.state[params[k]]["exp_avg_sq"].cpu().numpy(), v) <= TOL, k
-    # untouched rows are bit-identical to their initial values
-    untouched = (~keep).nonzero().flatten()[:1000]
-    assert torch.equal(params["f_rest"].detach().cpu()[untouched], init["f_rest"][untouched])
+    # every untouched row of every parameter and of both moments is bit-identical to its initial value
+    untouched = (~keep).nonzero().flatten().to(gpu)
+    assert 0 < untouched.numel() < P
+    for k in ac.KEYS:
+        bits = lambda t: t[untouched].view(torch.int32)
+        assert torch.equal(bits(params[k].detach()), bits(init[k].to(gpu))), k
+        for moment in ("exp_avg", "exp_avg_sq"):                 # (their initial value: +0.0)
+            assert not bits(opt.state[params[k]][moment]).any(), (k, moment)
 
     # throughput of one fused step (rows listed / masked / dense) vs the bytes it has to move
     def timed(fn, n=20):
