@@ -697,35 +697,79 @@ static int check_hier_view(const hgs_hier_view* v, const char* side) {
   return HGS_OK;
 }
 
-int hgs_hier_trim_plan(const hgs_hier_view* in, const hgs_hier_trim_args* args, void* tmp, hgs_hier_trim_report* report,
-                       hgs_stream_t stream, int device) {
-  if (!in || !args || !report) { set_error("null argument"); return HGS_ERR_INVALID; }
+// The two trim plan calls.  keyed: key has to be there and aligned, and key_floor a number.
+static int hier_trim_plan(const hgs_hier_view* in, const hgs_hier_trim_args* args, bool keyed, const float* key,
+                          float key_floor, void* tmp, hgs_hier_trim_report* report, hgs_stream_t stream, int device) {
+  if (!in || !args || !report || (keyed && !key)) { set_error("null argument"); return HGS_ERR_INVALID; }
   int rc = check_hier_view(in, "input");
   if (rc) return rc;
-  bool nan = std::isnan(args->min_extent);
+  if (keyed && ((uintptr_t)key & 3u)) { set_error("key must be 4-byte aligned"); return HGS_ERR_INVALID; }
+  bool nan = std::isnan(args->min_extent) || (keyed && std::isnan(key_floor));
   for (int a = 0; a < 3 && args->use_roi; ++a) nan = nan || std::isnan(args->roi_lo[a]) || std::isnan(args->roi_hi[a]);
-  if (nan) { set_error("min_extent or a region bound is NaN"); return HGS_ERR_INVALID; }
-  if ((rc = check_hier_tmp(tmp))) return rc;
-  for (int k = 0; k < 4; ++k) report->first_bad[k] = -1;
-  report->kept = report->stubs = 0;
-  HGS_HIP(hipSetDevice(device));
-  return launch_hier_trim_plan(*in, *args, nullptr, 0.0f, tmp, report, static_cast<hipStream_t>(stream), device);
-}
-
-int hgs_hier_trim_plan_keyed(const hgs_hier_view* in, const hgs_hier_trim_args* args, const float* key, float key_floor,
-                             void* tmp, hgs_hier_trim_report* report, hgs_stream_t stream, int device) {
-  if (!in || !args || !report || !key) { set_error("null argument"); return HGS_ERR_INVALID; }
-  int rc = check_hier_view(in, "input");
-  if (rc) return rc;
-  if ((uintptr_t)key & 3u) { set_error("key must be 4-byte aligned"); return HGS_ERR_INVALID; }
-  bool nan = std::isnan(args->min_extent) || std::isnan(key_floor);
-  for (int a = 0; a < 3 && args->use_roi; ++a) nan = nan || std::isnan(args->roi_lo[a]) || std::isnan(args->roi_hi[a]);
-  if (nan) { set_error("min_extent, key_floor or a region bound is NaN"); return HGS_ERR_INVALID; }
+  if (nan) {
+    set_error(keyed ? "min_extent, key_floor or a region bound is NaN" : "min_extent or a region bound is NaN");
+    return HGS_ERR_INVALID;
+  }
   if ((rc = check_hier_tmp(tmp))) return rc;
   for (int k = 0; k < 4; ++k) report->first_bad[k] = -1;
   report->kept = report->stubs = 0;
   HGS_HIP(hipSetDevice(device));
   return launch_hier_trim_plan(*in, *args, key, key_floor, tmp, report, static_cast<hipStream_t>(stream), device);
+}
+
+int hgs_hier_trim_plan(const hgs_hier_view* in, const hgs_hier_trim_args* args, void* tmp, hgs_hier_trim_report* report,
+                       hgs_stream_t stream, int device) {
+  return hier_trim_plan(in, args, false, nullptr, 0.0f, tmp, report, stream, device);
+}
+
+int hgs_hier_trim_plan_keyed(const hgs_hier_view* in, const hgs_hier_trim_args* args, const float* key, float key_floor,
+                             void* tmp, hgs_hier_trim_report* report, hgs_stream_t stream, int device) {
+  return hier_trim_plan(in, args, true, key, key_floor, tmp, report, stream, device);
+}
+
+// What hgs_hier_trim_apply and hgs_hier_prune_apply check in common, in the order they always had: first the views, M,
+// tmp and the maps ...
+static int check_hier_apply_args(const hgs_hier_view* in, const hgs_hier_view* out, const void* tmp,
+                                 const int32_t* old_of_new, const int32_t* new_of_old) {
+  if (!in || !out) { set_error("null argument"); return HGS_ERR_INVALID; }
+  int rc = check_hier_view(in, "input");
+  if (!rc) rc = check_hier_view(out, "output");
+  if (rc) return rc;
+  if (in->M != out->M) { set_error("bad sizes: input M=%d != output M=%d", in->M, out->M); return HGS_ERR_INVALID; }
+  if (!tmp || !old_of_new || !new_of_old) { set_error("null argument"); return HGS_ERR_INVALID; }
+  if ((rc = check_hier_tmp(tmp))) return rc;
+  if (((uintptr_t)old_of_new | (uintptr_t)new_of_old) & 3u) { set_error("old_of_new / new_of_old must be 4-byte aligned"); return HGS_ERR_INVALID; }
+  return HGS_OK;
+}
+
+// ... then (behind prune's mode check) the sizes against the plan's.  planned: the tool's lookup; plan_call: its name.
+static int check_hier_apply_plan(const hgs_hier_view* in, const hgs_hier_view* out, const void* tmp, int device,
+                                 bool (*planned)(int, const void*, int64_t*, int64_t*), const char* plan_call) {
+  int64_t planned_N = 0, kept = 0;
+  if (!planned(device, tmp, &planned_N, &kept)) {
+    set_error("no successful %s on this device and tmp", plan_call);
+    return HGS_ERR_INVALID;
+  }
+  if (in->N != planned_N) { set_error("bad sizes: input N=%lld, the plan was made for N=%lld", (long long)in->N, (long long)planned_N); return HGS_ERR_INVALID; }
+  if (out->N != kept) { set_error("bad sizes: output N=%lld != the plan's kept count %lld", (long long)out->N, (long long)kept); return HGS_ERR_INVALID; }
+  return HGS_OK;
+}
+
+// The first of the seven arrays of `out` that overlaps its array of `in` -> its name; nullptr: none does.  g_*: the rows
+// of the five arrays of Gaussians, n_*: the rows of nodes and boxes.  same_ok: an output array may BE its input array.
+static const char* overlapping_hier_array(const hgs_hier_view* in, size_t g_in, size_t n_in, const hgs_hier_view* out,
+                                          size_t g_out, size_t n_out, bool same_ok) {
+  const struct { const void* a; const void* b; size_t row; bool node; const char* name; } pairs[7] = {
+      {in->xyz, out->xyz, 12, false, "xyz"}, {in->shs, out->shs, 12 * (size_t)in->M, false, "shs"},
+      {in->alpha, out->alpha, 4, false, "alpha"}, {in->log_scales, out->log_scales, 12, false, "log_scales"},
+      {in->rots, out->rots, 16, false, "rots"}, {in->nodes, out->nodes, 28, true, "nodes"},
+      {in->boxes, out->boxes, 32, true, "boxes"}};
+  for (const auto& pr : pairs) {
+    const uintptr_t a = (uintptr_t)pr.a, b = (uintptr_t)pr.b;
+    if (same_ok && a == b) continue;
+    if (a < b + (pr.node ? n_out : g_out) * pr.row && b < a + (pr.node ? n_in : g_in) * pr.row) return pr.name;
+  }
+  return nullptr;
 }
 
 size_t hgs_hier_reach_tmp_bytes(int64_t N, int64_t C) {
@@ -747,21 +791,9 @@ int hgs_hier_reach(const float* boxes, int64_t N, const float* regions, int64_t 
 
 int hgs_hier_trim_apply(const hgs_hier_view* in, const hgs_hier_view* out, const void* tmp, int32_t* old_of_new,
                         int32_t* new_of_old, hgs_stream_t stream, int device) {
-  if (!in || !out) { set_error("null argument"); return HGS_ERR_INVALID; }
-  int rc = check_hier_view(in, "input");
-  if (!rc) rc = check_hier_view(out, "output");
+  int rc = check_hier_apply_args(in, out, tmp, old_of_new, new_of_old);
+  if (!rc) rc = check_hier_apply_plan(in, out, tmp, device, hier_trim_planned, "hgs_hier_trim_plan");
   if (rc) return rc;
-  if (in->M != out->M) { set_error("bad sizes: input M=%d != output M=%d", in->M, out->M); return HGS_ERR_INVALID; }
-  if (!tmp || !old_of_new || !new_of_old) { set_error("null argument"); return HGS_ERR_INVALID; }
-  if ((rc = check_hier_tmp(tmp))) return rc;
-  if (((uintptr_t)old_of_new | (uintptr_t)new_of_old) & 3u) { set_error("old_of_new / new_of_old must be 4-byte aligned"); return HGS_ERR_INVALID; }
-  int64_t planned_N = 0, kept = 0;
-  if (!hier_trim_planned(device, tmp, &planned_N, &kept)) {
-    set_error("no successful hgs_hier_trim_plan on this device and tmp");
-    return HGS_ERR_INVALID;
-  }
-  if (in->N != planned_N) { set_error("bad sizes: input N=%lld, the plan was made for N=%lld", (long long)in->N, (long long)planned_N); return HGS_ERR_INVALID; }
-  if (out->N != kept) { set_error("bad sizes: output N=%lld != the plan's kept count %lld", (long long)out->N, (long long)kept); return HGS_ERR_INVALID; }
   HGS_HIP(hipSetDevice(device));
   return launch_hier_trim_apply(*in, *out, tmp, old_of_new, new_of_old, shs16_ok(in, out), static_cast<hipStream_t>(stream));
 }
@@ -848,16 +880,9 @@ int hgs_hier_transform(const hgs_hier_view* in, const hgs_hier_view* out, const 
   if (in->M != 1 && in->M != 4 && in->M != 9 && in->M != 16) { set_error("bad sizes: M=%d not in {1, 4, 9, 16} (whole SH bands only)", in->M); return HGS_ERR_INVALID; }
   // every output array is its input array (in place) or does not overlap it
   const size_t G = (size_t)in->G, N = (size_t)in->N;
-  const struct { const void* a; const void* b; size_t bytes; const char* name; } pairs[7] = {
-      {in->xyz, out->xyz, G * 12, "xyz"}, {in->shs, out->shs, G * 12 * (size_t)in->M, "shs"}, {in->alpha, out->alpha, G * 4, "alpha"},
-      {in->log_scales, out->log_scales, G * 12, "log_scales"}, {in->rots, out->rots, G * 16, "rots"},
-      {in->nodes, out->nodes, N * 28, "nodes"}, {in->boxes, out->boxes, N * 32, "boxes"}};
-  for (const auto& pr : pairs) {
-    const uintptr_t a = (uintptr_t)pr.a, b = (uintptr_t)pr.b;
-    if (a != b && a < b + pr.bytes && b < a + pr.bytes) {
-      set_error("output %s overlaps input %s without being the same array", pr.name, pr.name);
-      return HGS_ERR_INVALID;
-    }
+  if (const char* name = overlapping_hier_array(in, G, N, out, G, N, true)) {
+    set_error("output %s overlaps input %s without being the same array", name, name);
+    return HGS_ERR_INVALID;
   }
   rc = check_transform_args(args);
   if (rc) return rc;
@@ -921,34 +946,18 @@ int hgs_hier_prune_plan(const hgs_hier_view* in, const hgs_hier_prune_args* args
 
 int hgs_hier_prune_apply(const hgs_hier_view* in, const hgs_hier_view* out, const void* tmp, int32_t remerge,
                          int32_t* old_of_new, int32_t* new_of_old, hgs_stream_t stream, int device) {
-  if (!in || !out) { set_error("null argument"); return HGS_ERR_INVALID; }
-  int rc = check_hier_view(in, "input");
-  if (!rc) rc = check_hier_view(out, "output");
+  int rc = check_hier_apply_args(in, out, tmp, old_of_new, new_of_old);
   if (rc) return rc;
-  if (in->M != out->M) { set_error("bad sizes: input M=%d != output M=%d", in->M, out->M); return HGS_ERR_INVALID; }
-  if (!tmp || !old_of_new || !new_of_old) { set_error("null argument"); return HGS_ERR_INVALID; }
-  if ((rc = check_hier_tmp(tmp))) return rc;
-  if (((uintptr_t)old_of_new | (uintptr_t)new_of_old) & 3u) { set_error("old_of_new / new_of_old must be 4-byte aligned"); return HGS_ERR_INVALID; }
   if (remerge < HGS_HIER_PRUNE_REMERGE_NONE || remerge > HGS_HIER_PRUNE_REMERGE_ALL) {
     set_error("bad remerge mode %d: 0 (none), 1 (dirty) or 2 (all) expected", remerge);
     return HGS_ERR_INVALID;
   }
-  int64_t planned_N = 0, kept = 0;
-  if (!hier_prune_planned(device, tmp, &planned_N, &kept)) {
-    set_error("no successful hgs_hier_prune_plan on this device and tmp");
-    return HGS_ERR_INVALID;
-  }
-  if (in->N != planned_N) { set_error("bad sizes: input N=%lld, the plan was made for N=%lld", (long long)in->N, (long long)planned_N); return HGS_ERR_INVALID; }
-  if (out->N != kept) { set_error("bad sizes: output N=%lld != the plan's kept count %lld", (long long)out->N, (long long)kept); return HGS_ERR_INVALID; }
+  if ((rc = check_hier_apply_plan(in, out, tmp, device, hier_prune_planned, "hgs_hier_prune_plan"))) return rc;
   // no output array overlaps its input array (the rows the input shows: N of them)
   const size_t nin = (size_t)in->N, nout = (size_t)out->N;
-  const struct { const void* a; const void* b; size_t row; const char* name; } pairs[7] = {
-      {in->xyz, out->xyz, 12, "xyz"}, {in->shs, out->shs, 12 * (size_t)in->M, "shs"}, {in->alpha, out->alpha, 4, "alpha"},
-      {in->log_scales, out->log_scales, 12, "log_scales"}, {in->rots, out->rots, 16, "rots"},
-      {in->nodes, out->nodes, 28, "nodes"}, {in->boxes, out->boxes, 32, "boxes"}};
-  for (const auto& pr : pairs) {
-    const uintptr_t a = (uintptr_t)pr.a, b = (uintptr_t)pr.b;
-    if (a < b + nout * pr.row && b < a + nin * pr.row) { set_error("output %s overlaps input %s", pr.name, pr.name); return HGS_ERR_INVALID; }
+  if (const char* name = overlapping_hier_array(in, nin, nin, out, nout, nout, false)) {
+    set_error("output %s overlaps input %s", name, name);
+    return HGS_ERR_INVALID;
   }
   HGS_HIP(hipSetDevice(device));
   return launch_hier_prune_apply(*in, *out, tmp, remerge, old_of_new, new_of_old, shs16_ok(in, out),

@@ -7,12 +7,14 @@
 //   levels     ha_check_kernel: one thread per node validates the row's depth / parent columns (first offending node per
 //              check), writes the depth as a sort key and counts the nodes per depth; sort_pairs32 (8 bits, stable) turns
 //              the keys into the level lists; ONE host wait reads the counts and the checks.  Nothing has been written
-//              to the hierarchy at that point: an invalid one is returned untouched.
+//              to the hierarchy at that point: an invalid one is returned untouched.  The workspace, the sort, the number
+//              of levels and the launch per depth are the host half of hier_levels.h; the checks are this rule's own.
 //   align      ha_level_kernel, one launch per depth 1, 2, ..: one thread per node reads its parent column, its 7 floats
 //              and the parent's quaternion (written by the previous launch), and writes its 7 floats if they change.
 //              Arithmetic in double, contraction off, every sum in the spec's order: the choice and the bits are the spec's.
 //
 // Any numbering works (the builder's BFS, the merger's chunks side by side): only depth and parent are read.
+#include "hier_levels.h"   // the host half of the level walk; the check kernel here is this rule's own
 #include "hier_nodes.h"
 
 #pragma clang fp contract(off)
@@ -20,9 +22,7 @@
 namespace hgs {
 namespace {
 
-constexpr int kHaThreads = 256;
-constexpr int kMaxDepth = 255;
-constexpr int kLevels = kMaxDepth + 1;
+constexpr int kHaThreads = kLevelThreads;
 
 // Device half of the report, read back with the level counts in one copy.
 struct HaResult {
@@ -97,7 +97,6 @@ __global__ __launch_bounds__(kHaThreads) void ha_check_kernel(const int32_t* __r
   const uint32_t c = bins[threadIdx.x];
   if (c) atomicAdd(&res->counts[threadIdx.x], c);
 }
-static_assert(kHaThreads == kLevels, "one thread per depth bin");
 
 // One thread per node of one depth: the rule.  `level` = this depth's slice of the depth-sorted node ids.
 __global__ __launch_bounds__(kHaThreads) void ha_level_kernel(const uint32_t* __restrict__ level, int32_t count,
@@ -142,44 +141,29 @@ __global__ __launch_bounds__(kHaThreads) void ha_level_kernel(const uint32_t* __
   }
 }
 
-struct HaTmp {
-  HaResult* res;
-  uint32_t* keys;
-  uint32_t* keys_sorted;
-  uint32_t* order;
-  void* sort_tmp;
-};
-
-HaTmp carve_ha_tmp(Carver& c, int64_t N) {
-  HaTmp t;
-  t.res = c.take<HaResult>(1);
-  t.keys = c.take<uint32_t>((size_t)N);
-  t.keys_sorted = c.take<uint32_t>((size_t)N);
-  t.order = c.take<uint32_t>((size_t)N);
-  t.sort_tmp = c.take<char>(sort_tmp_bytes((uint32_t)N));   // nested: the sort's own slack included
-  return t;
-}
+using HaTmp = LevelListsTmp<HaResult>;
 
 }  // namespace
 
 size_t hier_align_tmp_bytes(int64_t N) {
   Carver c(nullptr);
-  carve_ha_tmp(c, N);
+  HaTmp t;
+  carve_level_lists(c, N, t);
   return c.bytes(0);   // this workspace never had a slack block of its own (the nested sort's is its last)
 }
 
 int launch_hier_align(const int32_t* nodes, int64_t N, float* log_scales, float* rots, void* tmp,
                       hgs_hier_align_report* report, hipStream_t s) {
   Carver c(tmp);
-  const HaTmp t = carve_ha_tmp(c, N);
+  HaTmp t;
+  carve_level_lists(c, N, t);
   // ---- checks, keys and level counts; the level lists
   HGS_HIP(hipMemsetAsync(t.res->counts, 0, sizeof(t.res->counts), s));
   HGS_HIP(hipMemsetAsync(t.res->first_bad, 0xff, sizeof(HaResult) - sizeof(t.res->counts), s));
   const unsigned blocks = (unsigned)((N + kHaThreads - 1) / kHaThreads);
   hipLaunchKernelGGL(ha_check_kernel, dim3(blocks), dim3(kHaThreads), 0, s, nodes, (int32_t)N, t.keys, t.res);
   HGS_LAUNCH_CHECK("ha_check", s, false);
-  int rc = sort_pairs32(t.keys, nullptr, t.keys_sorted, t.order, t.sort_tmp, (uint32_t)N, nullptr, 8, s, false);
-  if (rc) return rc;
+  if (int rc = sort_level_lists(t, N, s)) return rc;
   // ---- the one host wait
   HaResult host;
   HGS_HIP(hipMemcpyAsync(&host, t.res, sizeof(host), hipMemcpyDeviceToHost, s));
@@ -187,8 +171,7 @@ int launch_hier_align(const int32_t* nodes, int64_t N, float* log_scales, float*
   first_bad_from_minima(host.first_bad, 3, report->first_bad);
   first_bad_from_minima(&host.second_root, 1, &report->first_bad[3]);
   report->roots = (int32_t)host.counts[0];
-  int levels = 0;
-  while (levels < kLevels && host.counts[levels]) ++levels;
+  const int levels = level_count(host.counts);
   report->levels = levels;
   report->reserved[0] = report->reserved[1] = 0;
   static const char* const what[4] = {"depth outside [0, 255]", "parent outside [0, N) at a node of depth > 0",
@@ -203,15 +186,7 @@ int launch_hier_align(const int32_t* nodes, int64_t N, float* log_scales, float*
   }
   // (every node of depth d > 0 has a parent of depth d - 1, so the depths in use are 0 .. levels - 1 without a gap)
   // ---- one launch per level, top-down
-  int64_t first = host.counts[0];
-  for (int d = 1; d < levels; ++d) {
-    const int64_t count = host.counts[d];
-    hipLaunchKernelGGL(ha_level_kernel, dim3((unsigned)((count + kHaThreads - 1) / kHaThreads)), dim3(kHaThreads), 0, s,
-                       t.order + first, (int32_t)count, nodes, log_scales, rots);
-    HGS_LAUNCH_CHECK("ha_level", s, false);
-    first += count;
-  }
-  return HGS_OK;
+  return launch_levels_down(ha_level_kernel, "ha_level", s, t.order, host.counts, levels, nodes, log_scales, rots);
 }
 
 }  // namespace hgs

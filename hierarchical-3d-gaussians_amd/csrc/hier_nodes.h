@@ -1,6 +1,7 @@
-// What the hierarchy tools share, each ONCE: the node record, the merger's three layout checks (run by hier_merge.hip and
-// hier_trim.hip, restated in numpy by hgs.hierarchy.layout_check_masks), the seven row pointers of a hierarchy, the host
-// half of a "first offending node per check" report.  Plain C++: tests/test_hier_nodes_on_host.py compiles it with g++.
+// What the hierarchy tools share, each ONCE: the node record, the merger's three layout checks (run by hier_merge.hip,
+// hier_trim.hip and, through hier_levels.h, hier_refit.hip and hier_prune.hip; restated in numpy by
+// hgs.hierarchy.layout_check_masks) and their sentences, the seven row pointers of a hierarchy, the host half of a
+// "first offending node per check" report.  Plain C++: tests/test_hier_nodes_on_host.py compiles it with g++.
 #pragma once
 #include "common.h"
 
@@ -35,6 +36,10 @@ __host__ __device__ __forceinline__ uint32_t node_layout(const int32_t* __restri
   return (bad_row ? kBadRow : 0u) | (bad_children ? kBadChildren : 0u) | (bad_parent ? kBadParent : 0u) |
          (parent_in_range ? kParentInRange : 0u);
 }
+// What the three checks say in an error text (hier_trim.hip, and hier_levels.h for hier_refit.hip and hier_prune.hip).
+constexpr const char* kLayoutChecks[3] = {"start != node index or count_leafs + count_merged != 1",
+                                          "children range outside [1, N)",
+                                          "parent outside [0, N) or not claiming the node (node 0: parent != -1)"};
 
 // The seven arrays of an hgs_hier_view as kernel arguments: read-only (HierRowsIn) and writable (HierRows).
 template <typename F, typename I>

@@ -10,8 +10,9 @@
 //              boxes and its row the w-weighted moment match of their final float32 rows, deepest level first
 //              (hier_merge_rule.h: the builder's merge generalised to k children); w is the weight the builder carries:
 //              alpha s0 s1 s2 of a leaf's row, at a node with children the sum of its surviving children's weights.
-//   plan       hp_plan_kernel: refit's plan walk (hier_levels.h: the six checks, the depth keys, the per-depth counts)
-//              with the removal test at every leaf, whose verdict is the leaf's flag byte; sort_pairs32 (8 bits, stable)
+//   plan       hp_plan_kernel: the plan walk of hier_levels.h, the one text hier_refit.hip runs too (the six checks, the
+//              depth keys, the per-depth counts, the reduce tail), with the removal test at every leaf, whose verdict is
+//              the leaf's flag byte; the host half of that header for what follows: sort_pairs32 (8 bits, stable)
 //              gives the level lists; the FIRST host wait reads the checks and the level counts.  hp_mark_kernel, one
 //              launch per depth from the deepest level with children up: one thread per node walks its children's flag
 //              bytes and leaves its own, its first surviving child and the surviving count (in the sort's key arrays,
@@ -34,31 +35,19 @@
 #include "hier_levels.h"
 #include "hier_merge_rule.h"
 #include "hier_nodes.h"
-#include "hier_refit_rule.h"   // the union and the extent of a box
 #include "lod_cut.h"           // the workgroup sums and the launcher of the chained scan
-
-#include <mutex>
-#include <vector>
 
 namespace hgs {
 namespace {
 
-constexpr int kHpThreads = 256;
-constexpr int kHpPlanBlocks = 2048;     // the plan's grid at most (hier_refit.hip: kHrPlanBlocks)
+constexpr int kHpThreads = kLevelThreads;
 constexpr uint32_t kDirty = 2u;         // bit 1 of a node's flag byte (bit 0: kKeep of hier_gather.h = alive)
-constexpr int kRootSlot = kLevelChecks; // minima[6]: the smallest node of depth 0
 
-// Device half of the report, read back in one copy at each of the two waits.
-struct HpResult {
-  uint32_t counts[kLevels];          // nodes per depth
-  uint32_t removed;                  // leaves a criterion removed
+// Device half of the report, read back in one copy at each of the two waits.  tally: the leaves a criterion removed.
+struct HpResult : LevelResult {
   uint32_t dirty;                    // alive nodes with a dead or dirty child
   uint32_t single;                   // alive nodes left with one child
-  uint32_t pad;
-  unsigned long long children_sum;   // over the nodes whose children range passed its check
-  uint32_t minima[kLevelChecks + 2]; // unsigned minima, kNone = none: the six checks, [6] the smallest node of depth 0
 };
-constexpr size_t kHpZeroBytes = offsetof(HpResult, minima);
 
 // is the point x inside the closed box [lo, hi]?  (a NaN coordinate is never inside)
 __device__ __forceinline__ bool hp_inside(const float x[3], const float lo[3], const float hi[3]) {
@@ -82,19 +71,15 @@ __device__ __forceinline__ bool hp_removed(const HierRowsIn& in, int64_t i, cons
   return r;
 }
 
-// One thread per node, kHpPlanBlocks workgroups at most that walk the nodes in strides: the checks, the depth as the sort
-// key, the per-depth counts, the children sum (hier_levels.h), and at a leaf the removal test: flags[i] = alive.  A node
-// with children gets its flag from hp_mark_kernel.
+// One thread per node, kLevelPlanBlocks workgroups at most that walk the nodes in strides: the plan walk of hier_levels.h
+// (the checks, the depth as the sort key, the per-depth counts, the children sum) with the removed leaves as its tally:
+// at a leaf the removal test, flags[i] = alive.  A node with children gets its flag from hp_mark_kernel.
 __global__ __launch_bounds__(kHpThreads) void hp_plan_kernel(HierRowsIn in, int32_t N, hgs_hier_prune_args a,
                                                              const uint8_t* __restrict__ remove,
                                                              uint32_t* __restrict__ keys, uint8_t* __restrict__ flags,
                                                              HpResult* __restrict__ res) {
-  __shared__ uint32_t bins[kLevels];
-  __shared__ uint32_t s_removed;
-  __shared__ unsigned long long s_children;
-  bins[threadIdx.x] = 0;            // kHpThreads == kLevels
-  if (threadIdx.x == 0) { s_removed = 0; s_children = 0; }
-  __syncthreads();
+  __shared__ LevelPlanLds lds;
+  level_plan_begin(lds);
   const int lane = threadIdx.x & 63;
   unsigned long long children = 0;
   uint32_t removed = 0;
@@ -104,7 +89,7 @@ __global__ __launch_bounds__(kHpThreads) void hp_plan_kernel(HierRowsIn in, int3
     bool counted = false;
     if (i < N) {
       int64_t cc;
-      key = level_check_node(in.nodes, i, N, res->minima, kRootSlot, children, &counted, &cc);
+      key = level_check_node(in.nodes, i, N, res->minima, children, &counted, &cc);
       uint8_t f = 0;
       if (cc == 0) {
         const bool r = hp_removed(in, i, a, remove);
@@ -114,25 +99,10 @@ __global__ __launch_bounds__(kHpThreads) void hp_plan_kernel(HierRowsIn in, int3
       flags[i] = f;
       keys[i] = key;
     }
-    level_count_depths(bins, key, counted, lane);
+    level_count_depths(lds.bins, key, counted, lane);
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    children += __shfl_down(children, o);
-    removed += __shfl_down(removed, o);
-  }
-  if (lane == 0) {
-    if (children) atomicAdd(&s_children, children);
-    if (removed) atomicAdd(&s_removed, removed);
-  }
-  __syncthreads();
-  const uint32_t c = bins[threadIdx.x];
-  if (c) atomicAdd(&res->counts[threadIdx.x], c);
-  if (threadIdx.x == 0) {
-    if (s_removed) atomicAdd(&res->removed, s_removed);
-    if (s_children) atomicAdd(&res->children_sum, s_children);
-  }
+  level_plan_end(lds, children, removed, lane, res);
 }
-static_assert(kHpThreads == kLevels, "one thread per depth bin");
 
 // One thread per node of one depth: alive and dirty from its children's flag bytes (written by the plan at leaves, by
 // the previous launch at nodes with children), its first surviving child and the surviving count.
@@ -213,9 +183,7 @@ __global__ __launch_bounds__(kHtThreads) void hp_gather_kernel(HierRowsIn in, Hi
                                                                uint32_t S, uint32_t W) {
   __shared__ int32_t src[kHtRows];
   const int64_t r0 = (int64_t)blockIdx.x * kHtRows;
-  const uint32_t rows = (uint32_t)min((int64_t)kHtRows, (int64_t)kept - r0);
-  if (threadIdx.x < rows) src[threadIdx.x] = old_of_new[r0 + threadIdx.x];
-  __syncthreads();
+  const uint32_t rows = ht_stage_rows(src, old_of_new, r0, kept);
   ht_copy_tensors(in, out, src, r0, rows, S, W);
   // the node records, one thread per int: depth, count_leafs and count_merged kept; parent, start and start_children
   // renumbered (the first SURVIVING child); count_children = the surviving children; a leaf keeps its own
@@ -256,20 +224,8 @@ __global__ __launch_bounds__(kHpThreads) void hp_remerge_kernel(const uint32_t* 
   if (cc <= 0) return;
   const int64_t sc = out.nodes[id * kNodeInts + 5];
   const bool dirty = (fl & kDirty) != 0u;
-  if (dirty) {        // the union of the children's final boxes; boxes[n,1,3] stays (the gather copied it)
-    const float4* kids = reinterpret_cast<const float4*>(out.boxes) + sc * 2;
-    float4 mn = kids[0], mx = kids[1];
-    float lo[3] = {mn.x, mn.y, mn.z}, hi[3] = {mx.x, mx.y, mx.z};
-    for (int32_t c = 1; c < cc; ++c) {
-      mn = kids[2 * c];
-      mx = kids[2 * c + 1];
-      const float clo[3] = {mn.x, mn.y, mn.z}, chi[3] = {mx.x, mx.y, mx.z};
-      refit_union(lo, hi, clo, chi);
-    }
-    const float own = reinterpret_cast<const float4*>(out.boxes)[id * 2 + 1].w;
-    reinterpret_cast<float4*>(out.boxes)[id * 2 + 0] = make_float4(lo[0], lo[1], lo[2], refit_extent(lo, hi));
-    reinterpret_cast<float4*>(out.boxes)[id * 2 + 1] = make_float4(hi[0], hi[1], hi[2], own);
-  }
+  // the union of the children's final boxes; boxes[n,1,3] stays (the gather copied it)
+  if (dirty) level_box_from_children(out.boxes, id, sc, cc, out.boxes);
   if (mode == HGS_HIER_PRUNE_REMERGE_NONE) return;
   // ---- walk 1, at clean nodes too: the weights the builder carries.  A leaf weighs alpha s0 s1 s2 of its row, a node
   // with children the clamped sum of its surviving children's weights (its own thread left it in wts one launch ago).
@@ -329,12 +285,9 @@ __global__ __launch_bounds__(kHpThreads) void hp_remerge_kernel(const uint32_t* 
   }
 }
 
-struct HpTmp : SumsTmp {
-  HpResult* res;
-  uint32_t* keys;          // [N] the depth keys; after the sort: every node's first surviving child
-  uint32_t* keys_sorted;   // [N] the sorted keys; after the sort: every node's count of surviving children
-  uint32_t* order;         // [N] the level lists
-  void* sort_tmp;
+// The level lists, and behind them this tool's own.  After the sort `keys` holds every node's first surviving child and
+// `keys_sorted` its count of surviving children.
+struct HpTmp : SumsTmp, LevelListsTmp<HpResult> {
   uint8_t* flags;          // [N]
   double* wts;             // [N] the weight a node carries: the sum over its surviving leaves (apply; by OUTPUT row)
   double* shr;             // [N] a child's share of its parent's weight (apply; by OUTPUT row)
@@ -342,11 +295,7 @@ struct HpTmp : SumsTmp {
 
 HpTmp carve_hp_tmp(Carver& c, int64_t N) {
   HpTmp t;
-  t.res = c.take<HpResult>(1);
-  t.keys = c.take<uint32_t>((size_t)N);
-  t.keys_sorted = c.take<uint32_t>((size_t)N);
-  t.order = c.take<uint32_t>((size_t)N);
-  t.sort_tmp = c.take<char>(sort_tmp_bytes((uint32_t)N));   // nested: the sort's own slack included
+  carve_level_lists(c, N, t);
   t.flags = c.take<uint8_t>((size_t)N);
   t.wts = c.take<double>((size_t)N);
   t.shr = c.take<double>((size_t)N);
@@ -363,22 +312,7 @@ struct HpPlan {
   int levels;
   uint32_t counts[kLevels];
 };
-constexpr size_t kHpMaxPlans = 64;
-std::mutex g_hp_mutex;
-std::vector<HpPlan> g_hp_plans;   // oldest first
-
-void forget_plan(int device, const void* tmp) {
-  std::lock_guard<std::mutex> lock(g_hp_mutex);
-  for (size_t k = 0; k < g_hp_plans.size(); ++k)
-    if (g_hp_plans[k].device == device && g_hp_plans[k].tmp == tmp) { g_hp_plans.erase(g_hp_plans.begin() + k); break; }
-}
-
-bool find_plan(int device, const void* tmp, HpPlan* out) {
-  std::lock_guard<std::mutex> lock(g_hp_mutex);
-  for (const HpPlan& p : g_hp_plans)
-    if (p.device == device && p.tmp == tmp) { *out = p; return true; }
-  return false;
-}
+PlanBook<HpPlan> g_hp_plans;
 
 }  // namespace
 
@@ -390,7 +324,7 @@ size_t hier_prune_tmp_bytes(int64_t N) {
 
 bool hier_prune_planned(int device, const void* tmp, int64_t* N, int64_t* kept) {
   HpPlan p;
-  if (!find_plan(device, tmp, &p)) return false;
+  if (!g_hp_plans.find(device, tmp, &p)) return false;
   *N = p.N;
   *kept = p.kept;
   return true;
@@ -398,53 +332,33 @@ bool hier_prune_planned(int device, const void* tmp, int64_t* N, int64_t* kept) 
 
 int launch_hier_prune_plan(const hgs_hier_view& in, const hgs_hier_prune_args& args, const uint8_t* remove, void* tmp,
                            hgs_hier_prune_report* report, hipStream_t s, int device) {
-  forget_plan(device, tmp);
+  g_hp_plans.forget(device, tmp);
   const int64_t N = in.N;
   Carver c(tmp);
   const HpTmp t = carve_hp_tmp(c, N);
   int32_t* const first_alive = reinterpret_cast<int32_t*>(t.keys);
   int32_t* const surviving = reinterpret_cast<int32_t*>(t.keys_sorted);
   // ---- checks, keys, counts, the leaves' verdicts; the level lists
-  HGS_HIP(hipMemsetAsync(t.res, 0, kHpZeroBytes, s));
-  HGS_HIP(hipMemsetAsync(t.res->minima, 0xff, sizeof(t.res->minima), s));
-  const dim3 grid((unsigned)((N + kHpThreads - 1) / kHpThreads)), block(kHpThreads);
-  const dim3 plan_grid(grid.x < (unsigned)kHpPlanBlocks ? grid.x : (unsigned)kHpPlanBlocks);
-  hipLaunchKernelGGL(hp_plan_kernel, plan_grid, block, 0, s, HierRowsIn::of(in), (int32_t)N, args, remove, t.keys, t.flags,
-                     t.res);
-  HGS_LAUNCH_CHECK("hp_plan", s, false);
-  int rc = sort_pairs32(t.keys, nullptr, t.keys_sorted, t.order, t.sort_tmp, (uint32_t)N, nullptr, 8, s, false);
+  int rc = clear_level_result(t.res, s);
   if (rc) return rc;
+  const dim3 grid((unsigned)((N + kHpThreads - 1) / kHpThreads)), block(kHpThreads);
+  hipLaunchKernelGGL(hp_plan_kernel, level_plan_grid(N), block, 0, s, HierRowsIn::of(in), (int32_t)N, args, remove, t.keys,
+                     t.flags, t.res);
+  HGS_LAUNCH_CHECK("hp_plan", s, false);
+  if ((rc = sort_level_lists(t, N, s))) return rc;
   // ---- the first host wait
   HpResult host;
   HGS_HIP(hipMemcpyAsync(&host, t.res, sizeof(host), hipMemcpyDeviceToHost, s));
   HGS_HIP(wait_stream(s));
   first_bad_from_minima(host.minima, kLevelChecks, report->first_bad);
-  int levels = 0;
-  while (levels < kLevels && host.counts[levels]) ++levels;
+  const int levels = level_count(host.counts);
   report->levels = levels;
   report->children_sum = (int64_t)host.children_sum;
-  report->removed_leaves = (int64_t)host.removed;
-  static const char* const what[kLevelChecks] = {
-      "start != node index or count_leafs + count_merged != 1", "children range outside [1, N)",
-      "parent outside [0, N) or not claiming the node (node 0: parent != -1)", "depth outside [0, 255]",
-      "depth is not the parent's depth + 1 (without a parent in [0, N): depth != 0)", "more than one node of depth 0"};
-  if (fail_on_first_bad(report->first_bad, what, kLevelChecks,
-                        "not a hierarchy that can be pruned: %s (first offending node %d); nothing was written"))
-    return HGS_ERR_INVALID;
-  if (report->children_sum != N - 1) {
-    set_error("not a hierarchy that can be pruned: count_children sums to %lld over %lld nodes, N - 1 expected (two nodes "
-              "claim the same children); nothing was written", (long long)report->children_sum, (long long)N);
-    return HGS_ERR_INVALID;
-  }
-  // ---- alive and dirty, one launch per level, bottom-up (the deepest level holds leaves alone)
-  int64_t first = N - host.counts[levels - 1];
-  for (int d = levels - 2; d >= 0; --d) {
-    const int64_t count = host.counts[d];
-    first -= count;
-    hipLaunchKernelGGL(hp_mark_kernel, dim3((unsigned)((count + kHpThreads - 1) / kHpThreads)), block, 0, s, t.order + first,
-                       (int32_t)count, in.nodes, t.flags, first_alive, surviving);
-    HGS_LAUNCH_CHECK("hp_mark", s, false);
-  }
+  report->removed_leaves = (int64_t)host.tally;
+  if ((rc = level_plan_verdict(report->first_bad, nullptr, report->children_sum, N, "pruned"))) return rc;
+  // ---- alive and dirty, one launch per level, bottom-up
+  rc = launch_levels_up(hp_mark_kernel, "hp_mark", s, t.order, host.counts, levels, N, in.nodes, t.flags, first_alive, surviving);
+  if (rc) return rc;
   // ---- the alive sums and their scan, the counts
   const int nblk = (int)grid.x;
   hipLaunchKernelGGL(hp_count_kernel, grid, block, 0, s, in.nodes, (int32_t)N, t.flags, surviving, t.block_sums, t.chain,
@@ -476,16 +390,14 @@ int launch_hier_prune_plan(const hgs_hier_view& in, const hgs_hier_prune_args& a
   p.kept = (int64_t)kept;
   p.levels = levels;
   for (int d = 0; d < kLevels; ++d) p.counts[d] = host.counts[d];
-  std::lock_guard<std::mutex> lock(g_hp_mutex);
-  if (g_hp_plans.size() >= kHpMaxPlans) g_hp_plans.erase(g_hp_plans.begin());
-  g_hp_plans.push_back(p);
+  g_hp_plans.add(p);
   return HGS_OK;
 }
 
 int launch_hier_prune_apply(const hgs_hier_view& in, const hgs_hier_view& out, const void* tmp, int32_t remerge,
                             int32_t* old_of_new, int32_t* new_of_old, bool shs16, hipStream_t s, int device) {
   HpPlan p;
-  if (!find_plan(device, tmp, &p)) { set_error("no successful hgs_hier_prune_plan on this device and tmp"); return HGS_ERR_INVALID; }
+  if (!g_hp_plans.find(device, tmp, &p)) { set_error("no successful hgs_hier_prune_plan on this device and tmp"); return HGS_ERR_INVALID; }
   const int64_t N = in.N, kept = out.N;
   Carver c(const_cast<void*>(tmp));
   const HpTmp t = carve_hp_tmp(c, N);
@@ -502,15 +414,8 @@ int launch_hier_prune_apply(const hgs_hier_view& in, const hgs_hier_view& out, c
   // ---- boxes and rows of the dirty nodes, one launch per level, bottom-up.  Nothing to do where nothing died and no row
   // is asked for again.
   if (kept == N && remerge != HGS_HIER_PRUNE_REMERGE_ALL) return HGS_OK;
-  int64_t first = N - p.counts[p.levels - 1];
-  for (int d = p.levels - 2; d >= 0; --d) {
-    const int64_t count = p.counts[d];
-    first -= count;
-    hipLaunchKernelGGL(hp_remerge_kernel, dim3((unsigned)((count + kHpThreads - 1) / kHpThreads)), dim3(kHpThreads), 0, s,
-                       t.order + first, (int32_t)count, t.flags, new_of_old, HierRows::of(out), W, remerge, t.wts, t.shr);
-    HGS_LAUNCH_CHECK("hp_remerge", s, false);
-  }
-  return HGS_OK;
+  return launch_levels_up(hp_remerge_kernel, "hp_remerge", s, t.order, p.counts, p.levels, N, t.flags, new_of_old,
+                          HierRows::of(out), W, remerge, t.wts, t.shr);
 }
 
 }  // namespace hgs

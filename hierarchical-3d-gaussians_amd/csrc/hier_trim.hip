@@ -23,12 +23,9 @@
 //              set is a run of the old order (under an extent floor it is nearly a prefix of the BFS order).
 //
 // Rows at index >= N of the input (a skybox tail) are not read; rows at index >= N' of the output are not written.
-#include "hier_gather.h"   // the maps kernel and the row copy, shared with hier_prune.hip
+#include "hier_gather.h"   // the maps kernel, the row copy and the plan book, shared with hier_prune.hip
 #include "hier_nodes.h"
 #include "lod_cut.h"   // the workgroup sums and the launcher of the chained scan (the cut rules in it are not used here)
-
-#include <mutex>
-#include <vector>
 
 namespace hgs {
 namespace {
@@ -112,16 +109,8 @@ __global__ __launch_bounds__(kHtThreads) void ht_gather_kernel(HierRowsIn in, Hi
                                                                uint32_t S, uint32_t W) {
   __shared__ int32_t src[kHtRows];
   const int64_t r0 = (int64_t)blockIdx.x * kHtRows;
-  const uint32_t rows = (uint32_t)min((int64_t)kHtRows, (int64_t)kept - r0);
-  if (threadIdx.x < rows) src[threadIdx.x] = old_of_new[r0 + threadIdx.x];
-  __syncthreads();
-  if (S) ht_copy_rows(reinterpret_cast<float4*>(out.shs), reinterpret_cast<const float4*>(in.shs), src, r0, rows, S);
-  else ht_copy_rows(out.shs, in.shs, src, r0, rows, W);
-  ht_copy_rows(reinterpret_cast<float4*>(out.boxes), reinterpret_cast<const float4*>(in.boxes), src, r0, rows, 2u);
-  ht_copy_rows(reinterpret_cast<float4*>(out.rots), reinterpret_cast<const float4*>(in.rots), src, r0, rows, 1u);
-  ht_copy_rows(out.xyz, in.xyz, src, r0, rows, 3u);
-  ht_copy_rows(out.log_scales, in.log_scales, src, r0, rows, 3u);
-  ht_copy_rows(out.alpha, in.alpha, src, r0, rows, 1u);
+  const uint32_t rows = ht_stage_rows(src, old_of_new, r0, kept);
+  ht_copy_tensors(in, out, src, r0, rows, S, W);
   // the node records, one thread per int: depth kept, parent / start / start_children renumbered, a stub takes a
   // leaf's record, a leaf keeps its own
   int32_t* o = out.nodes + r0 * kNodeInts;
@@ -161,15 +150,7 @@ HtTmp carve_ht_tmp(Carver& c, int64_t N) {
 
 // What the last successful plan on (device, tmp) found: the apply call checks its sizes against it on the host.
 struct HtPlan { int device; const void* tmp; int64_t N; int64_t kept; };
-constexpr size_t kHtMaxPlans = 64;
-std::mutex g_ht_mutex;
-std::vector<HtPlan> g_ht_plans;   // oldest first
-
-void forget_plan(int device, const void* tmp) {
-  std::lock_guard<std::mutex> lock(g_ht_mutex);
-  for (size_t k = 0; k < g_ht_plans.size(); ++k)
-    if (g_ht_plans[k].device == device && g_ht_plans[k].tmp == tmp) { g_ht_plans.erase(g_ht_plans.begin() + k); break; }
-}
+PlanBook<HtPlan> g_ht_plans;
 
 }  // namespace
 
@@ -180,16 +161,17 @@ size_t hier_trim_tmp_bytes(int64_t N) {
 }
 
 bool hier_trim_planned(int device, const void* tmp, int64_t* N, int64_t* kept) {
-  std::lock_guard<std::mutex> lock(g_ht_mutex);
-  for (const HtPlan& p : g_ht_plans)
-    if (p.device == device && p.tmp == tmp) { *N = p.N; *kept = p.kept; return true; }
-  return false;
+  HtPlan p;
+  if (!g_ht_plans.find(device, tmp, &p)) return false;
+  *N = p.N;
+  *kept = p.kept;
+  return true;
 }
 
 // key == nullptr: the plain plan; else the keyed one (key float [N] on the device, key_floor)
 int launch_hier_trim_plan(const hgs_hier_view& in, const hgs_hier_trim_args& args, const float* key, float key_floor,
                           void* tmp, hgs_hier_trim_report* report, hipStream_t s, int device) {
-  forget_plan(device, tmp);
+  g_ht_plans.forget(device, tmp);
   const int64_t N = in.N;
   Carver c(tmp);
   const HtTmp t = carve_ht_tmp(c, N);
@@ -216,17 +198,14 @@ int launch_hier_trim_plan(const hgs_hier_view& in, const hgs_hier_trim_args& arg
   report->kept = (int64_t)totals[0];
   report->stubs = (int64_t)totals[1];
   static const char* const what[4] = {
-      "start != node index or count_leafs + count_merged != 1", "children range outside [1, N)",
-      "parent outside [0, N) or not claiming the node (node 0: parent != -1)",
+      kLayoutChecks[0], kLayoutChecks[1], kLayoutChecks[2],
       "a kept node under a dropped parent (the boxes do not nest, or the extents grow downwards)"};
   if (fail_on_first_bad(report->first_bad, what, 4,
                         key ? "not a hierarchy that can be trimmed to views: %s (first offending node %d; "
                               "hgs.refit_hierarchy makes the boxes nest); nothing was written"
                             : "not a hierarchy that can be trimmed: %s (first offending node %d); nothing was written"))
     return HGS_ERR_INVALID;
-  std::lock_guard<std::mutex> lock(g_ht_mutex);
-  if (g_ht_plans.size() >= kHtMaxPlans) g_ht_plans.erase(g_ht_plans.begin());
-  g_ht_plans.push_back(HtPlan{device, tmp, N, (int64_t)totals[0]});
+  g_ht_plans.add(HtPlan{device, tmp, N, (int64_t)totals[0]});
   return HGS_OK;
 }
 

@@ -167,6 +167,27 @@ def test_the_second_scan_chunk(gpu):
     assert_within_builders_bounds("second chunk", sub, ref, np.ones(n, dtype=bool))
 
 
+@pytest.mark.parametrize("P", (262_145, 300_000))
+def test_the_plan_walks_second_trip(gpu, P):
+    """The plan kernel's grid is capped at 2048 workgroups of 256 threads: above 524 288 nodes a workgroup goes through
+    its loop a second time, with its sums in registers and its depth bins in LDS from the first.  262 145 leaves are
+    524 289 nodes (the second trip holds ONE node), 300 000 leaves are 599 999 nodes (many workgroups make the trip, the
+    last of them partly filled).  Built on the device; one remove box over a corner of the scene, the re-merge of the
+    dirty nodes.  The numpy spec at 599 999 nodes takes 0.4 s on the CPU host these tests were written on."""
+    h = host(hierarchy.build_hierarchy_on_device(P, CAM, gpu, seed=3))
+    N = h.num_nodes
+    assert N == 2 * P - 1 and N > 2048 * 256
+    x = h.xyz.numpy()[h.nodes.numpy()[:, 6] == 0]
+    box = (tuple(float(v) for v in x.min(0)), tuple(float(v) for v in np.quantile(x, 0.4, axis=0)))
+    want = hierarchy.prune_hierarchy(h, remove_boxes=[box], remerge="dirty")
+    print(f"{P} leaves: removed {want.removed_leaves}, dead {want.dead}, dirty {want.dirty}, single {want.single_child}")
+    assert 0 < want.removed_leaves < P // 4 and want.dirty > 0
+    stats = {}
+    got = run_case(gpu, h, want, remove_boxes=[box], stats=stats)
+    assert stats["levels"] == int(h.nodes[:, 0].max()) + 1
+    assert got.hierarchy.num_nodes == N - want.dead
+
+
 def parents_of_leaves(nodes):
     nd = np.asarray(nodes)
     has_inner_child = np.zeros(nd.shape[0], dtype=bool)

@@ -20,7 +20,7 @@ from test_hier_merge_gpu import _chunk
 from test_hier_refit_cpu import (CORRUPTION_NAMES, MODES, built, chain, corruptions, merged, nested_np, perturbed2000,
                                  stale_boxes, wide)
 from test_hier_transform_gpu import _oracle_lod_render
-from test_hier_trim_cpu import ARRAYS, VIEWS, bits, clone, scene2000
+from test_hier_trim_cpu import ARRAYS, CAM, VIEWS, bits, clone, scene2000
 from test_hier_trim_gpu import _gpu_cuts, _render
 
 pytestmark = pytest.mark.gpu
@@ -157,6 +157,32 @@ def test_interiors_are_exact_and_leaves_within_one_ulp(gpu, name):
         again.inputs_untouched(but=("boxes",))
         again.out_untouched()
         assert torch.equal(bits(again.boxes(inplace=True)), bits(out)), (name, mode, "in place differs from out of place")
+
+
+# ---- the plan kernel's second trip ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("P", (262_145, 300_000))
+def test_the_plan_walks_second_trip(gpu, P):
+    """The plan kernel's grid is capped at 2048 workgroups of 256 threads: above 524 288 nodes a workgroup goes through
+    its loop a second time, with its sums in registers and its depth bins in LDS from the first.  262 145 leaves are
+    524 289 nodes (the second trip holds ONE node: the other 255 lanes of that workgroup, and every other workgroup's, have
+    none); 300 000 leaves are 599 999 nodes (many workgroups make the trip, the last of them partly filled).  Built on the
+    device; waves straddle level boundaries at both sizes.  The numpy spec at 599 999 nodes takes 0.2 s (keep) and 0.3 s
+    (cube) on the CPU host these tests were written on, the union of the device's own leaf boxes as much again."""
+    d = hierarchy.build_hierarchy_on_device(P, CAM, gpu, seed=3)
+    h = to_host(d)
+    nodes = h.nodes.numpy()
+    N = h.num_nodes
+    assert N == 2 * P - 1 and N > 2048 * 256
+    first = np.flatnonzero(np.diff(nodes[:, 0])) + 1           # where a level begins (BFS order)
+    assert (first % 64 != 0).any(), "no wave straddles a level boundary"
+    for mode in ("keep", "cube"):
+        rep, stats = _lib.HierRefitReport(), {}
+        out = hierarchy.refit_boxes_gpu(d, mode, stats=stats, report=rep)
+        assert list(rep.first_bad) == [-1] * 7
+        assert rep.levels == stats["levels"] == int(nodes[:, 0].max()) + 1 == np.unique(nodes[:, 0]).size
+        assert rep.leaves == stats["leaves"] == int((nodes[:, 6] == 0).sum()) and rep.children_sum == N - 1
+        worst, differing, coords = check_against_spec(h, out.boxes.cpu().reshape(N, 2, 4), mode, (P, mode))
+        print(f"{P} leaves, {mode}: leaves {worst} ulp at most, {differing} of {coords} coordinates differ")
 
 
 # ---- keep on what the device built and merged ----------------------------------------------------------------------------

@@ -205,8 +205,8 @@ def test_sort_bytes_keep_their_closed_form():
 
 
 def test_hierarchy_and_knn_bytes_keep_their_closed_forms():
-    """Each ends in a nested sort scratch of _sort(n) bytes (the sort's own slack included); hier_align has no slack of
-    its own, the other two have."""
+    """Build, align and knn end in a nested sort scratch of _sort(n) bytes (the sort's own slack included); hier_align
+    has no slack of its own, the other two have.  Refit, trim, prune and reach: no slack of their own either."""
     lib = _lib.lib()
     HA_RESULT, MOM_DOUBLES, RUN = (256 + 8) * 4, 10, 256
     for P in (1, 2, 255, 256, 257, 1_048_577):
@@ -216,6 +216,25 @@ def test_hierarchy_and_knn_bytes_keep_their_closed_forms():
         assert lib.hgs_hier_align_tmp_bytes(P) == up(HA_RESULT) + 3 * up(P * 4) + _sort(P), P
     assert lib.hgs_hier_build_tmp_bytes(0) == 0 and lib.hgs_hier_build_tmp_bytes((1 << 30) + 1) == 0
     assert lib.hgs_hier_align_tmp_bytes(0) == 0 and lib.hgs_hier_align_tmp_bytes(1 << 31) == 0
+    # refit, trim, prune and reach, read off their carve functions (none has a slack block of its own): the level lists
+    # of hier_levels.h behind the tool's device report, a flag byte per node, prune's two doubles per node, and the
+    # workgroup sums of lod_cut.h's carve_sums with their scan chain
+    LEVEL_RESULT = (256 + 2) * 4 + 8 + 8 * 4                   # counts, tally, pad; children_sum; minima
+    HP_RESULT, HT_RESULT = LEVEL_RESULT + 2 * 4, 4 * 4
+    lists = lambda result, N: up(result) + 3 * up(N * 4) + _sort(N)
+    sums = lambda nblk, cull: up((nblk + (2 if cull else 1)) * 4) + (up(nblk * 4) if cull else 0) + up(_scan_chunks(nblk) * 8)
+    for N in (1, 2, 255, 256, 257, 524_288, 524_289, 50_000_000, (1 << 31) - 1):
+        nblk = (N + 255) // 256
+        assert lib.hgs_hier_align_tmp_bytes(N) == lists(HA_RESULT, N), N
+        assert lib.hgs_hier_refit_tmp_bytes(N) == lists(LEVEL_RESULT, N), N
+        assert lib.hgs_hier_trim_tmp_bytes(N) == up(HT_RESULT) + up(N) + sums(nblk, True), N
+        assert lib.hgs_hier_prune_tmp_bytes(N) == lists(HP_RESULT, N) + up(N) + 2 * up(N * 8) + sums(nblk, False), N
+        for Cn in (1, 255, 256, 257, 1 << 24):
+            assert lib.hgs_hier_reach_tmp_bytes(N, Cn) == up(N * 4), (N, Cn)
+        assert lib.hgs_hier_reach_tmp_bytes(N, 0) == 0 and lib.hgs_hier_reach_tmp_bytes(N, (1 << 24) + 1) == 0
+    for size in (lib.hgs_hier_refit_tmp_bytes, lib.hgs_hier_trim_tmp_bytes, lib.hgs_hier_prune_tmp_bytes):
+        assert size(0) == 0 and size(1 << 31) == 0
+    assert lib.hgs_hier_reach_tmp_bytes(0, 1) == 0 and lib.hgs_hier_reach_tmp_bytes(1 << 31, 1) == 0
     for P in (0, 1, 255, 256, 257, 2560, 2561, 1_000_003):
         p = max(P, 1)
         assert lib.hgs_knn_tmp_bytes(P) == (up(8 * 4) + 2 * up(p * 8) + 2 * up(p * 4) + up(p * 16) +
