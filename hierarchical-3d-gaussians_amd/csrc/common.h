@@ -121,6 +121,15 @@ struct BwdWs {
   static BwdWs carve_from(void* base, uint32_t L, int32_t P) { Carver c(base); return layout(c, L, P); }
 };
 
+// Scratch of the contribution statistics (contrib.hip): one 16-byte record per (tile, Gaussian) instance, in emission
+// order like BwdWs::inst_grads; written whole by the tile kernel, so it needs no clearing
+struct ContribWs {
+  float* inst;             // [L,4] (largest weight, sum of weights, pixel count as bits, 0)
+  static ContribWs layout(Carver& c, uint32_t L);      // contrib.hip
+  static size_t bytes(uint32_t L) { Carver c(nullptr); layout(c, L); return c.bytes(kAlign); }
+  static ContribWs carve_from(void* base, uint32_t L) { Carver c(base); return layout(c, L); }
+};
+
 inline int grid_x(int W) { return (W + kTile - 1) / kTile; }
 inline int grid_y(int H) { return (H + kTile - 1) / kTile; }
 inline int tile_bits(int T) {
@@ -262,6 +271,10 @@ int launch_render_fwd(const hgs_raster_args& a, const GeomWs& g, const BinWs& b,
 int launch_render_bwd(const hgs_raster_args& a, const GeomWs& g, const BinWs& b, const ImgWs& im,
                       const float* out_color, const float* out_invdepth, const float* dL_dcolor,
                       const float* dL_dinvdepth, float* inst_grads, hipStream_t s);
+// per-Gaussian blending statistics of the forward whose workspaces g / b are (contrib.hip); L: what w was carved with
+int launch_raster_contrib(const hgs_raster_args& a, const GeomWs& g, const BinWs& b, const ContribWs& w, uint32_t L,
+                          const uint8_t* pixel_mask, const int32_t* slot_of_row, int64_t n_slots, float* wmax,
+                          double* wsum, int64_t* count, hipStream_t s);
 // L: the frame's instance count (a frame of long runs sums them with kernels of their own in front of K8a; w.inst_grads
 // is consumed: they leave every segment's sums over the segment's first records)
 int launch_preprocess_bwd(const hgs_raster_args& a, const GeomWs& g, const BwdWs& w, const hgs_raster_grads& out, uint32_t L,

@@ -586,6 +586,49 @@ def raster_views(call):
     }
 
 
+def raster_contributions(call, wmax, wsum, count, slot_of_row=None, pixel_mask=None):
+    """Blending statistics of the forward that returned ``call`` (hgs_raster_contrib),
+    accumulated IN PLACE into ``wmax`` float32, ``wsum`` float64 and ``count`` int64, all [S] on the forward's device:
+    per op row blended at a counted pixel, the largest weight alpha * T, the sum of the weights and the number of
+    pixels, into slot ``slot_of_row[row]`` (int32 [P]; default: the row itself; negative or >= S: the row is ignored;
+    the non-negative entries must be distinct).  ``pixel_mask``: uint8 [H*W] (or [H, W]), non-zero = counted.  Entries
+    of rows that are blended nowhere keep their bits: zero-fill once, call once per view."""
+    lib = _lib.lib()
+    dev, P = call.device, call.P
+    for t, name, dtype in ((wmax, "wmax", torch.float32), (wsum, "wsum", torch.float64), (count, "count", torch.int64)):
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != dev:
+            raise RuntimeError(f"{name} must be a tensor on the forward's device {dev}")
+        if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous():
+            raise RuntimeError(f"{name} must be a contiguous 1-D {dtype} tensor (it is written in place)")
+    S = int(wmax.numel())
+    if S < 1 or wsum.numel() != S or count.numel() != S:
+        raise RuntimeError(f"wmax / wsum / count must have the same length >= 1 (got {S}, {wsum.numel()}, {count.numel()})")
+    if slot_of_row is None:
+        if S < P:
+            raise RuntimeError(f"{S} slots for {P} op rows: pass slot_of_row, or arrays of at least {P} entries")
+    else:
+        if not torch.is_tensor(slot_of_row) or slot_of_row.device != dev or slot_of_row.dtype != torch.int32:
+            raise RuntimeError(f"slot_of_row must be an int32 tensor on {dev}")
+        if slot_of_row.numel() != P:
+            raise RuntimeError(f"slot_of_row must hold one entry per op row ({P}), got {slot_of_row.numel()}")
+        slot_of_row = slot_of_row.contiguous()
+    if pixel_mask is not None:
+        if not torch.is_tensor(pixel_mask) or pixel_mask.device != dev or pixel_mask.dtype != torch.uint8:
+            raise RuntimeError(f"pixel_mask must be a uint8 tensor on {dev}")
+        if pixel_mask.numel() != call.W * call.H:
+            raise RuntimeError(f"pixel_mask must hold H * W = {call.W * call.H} entries, got {pixel_mask.numel()}")
+        pixel_mask = pixel_mask.contiguous()
+    if P == 0 or call.L == 0:
+        return
+    # the instance scratch comes from the arena like every other workspace (uninitialised: the tile kernel writes
+    # every record)
+    tmp = _arena(int(lib.hgs_raster_contrib_tmp_bytes(call.L_ws)), dev)
+    p = _lib.ptr
+    _lib.check(lib.hgs_raster_contrib(C.byref(call.args), call.p_geom, call.p_bin, call.p_img, call.L_ws,
+                                      p(pixel_mask), p(slot_of_row), S, p(wmax), p(wsum), p(count), p(tmp),
+                                      _stream(dev), dev.index or 0), "hgs_raster_contrib")
+
+
 def mark_visible(means3D, viewmatrix, projmatrix):
     """Frustum test used by the upstream API (z > 0.2 in view space)."""
     means3D = _require_gpu(means3D, "means3D")

@@ -214,6 +214,35 @@ int hgs_raster_bwd(const hgs_raster_args* a, const void* geom_ws, const void* bi
                    const float* dL_dcolor, const float* dL_dinvdepth,
                    const hgs_raster_grads* grads, hgs_stream_t stream, int device);
 
+/* Per-Gaussian blending statistics of ONE forward whose workspaces are intact: for every
+ * row i < P of the op that the forward blended into at least one counted pixel, with s = slot_of_row[i],
+ *     wmax[s]  = max(wmax[s], largest w = alpha * T_before over the counted pixels)     float32
+ *     wsum[s] += sum of w over the counted pixels                                        float64
+ *     count[s] += number of counted pixels the row is blended at                         int64
+ * and every other entry of the three [n_slots] device arrays keeps its bits: zero-fill once, call once per view.
+ * "Blended" is K6's decision on the same records in the same float32 expressions (list membership, exponent clamped
+ * at 0, alpha = min(0.99, o G) >= 1/255, pixel not stopped, T after it >= 1e-4); o is the opacity K1 stored, so the
+ * default per-Gaussian LOD remap is included.  Stands in for nothing upstream; in this library it replaces the
+ * colour-gradient trick (render with colors_precomp, back-propagate ones through hgs_raster_bwd, read one channel of
+ * dL_dcolors), which yields wsum alone at the cost of the whole backward.
+ *   pixel_mask   NULL (all pixels) or device uint8 [H*W], non-zero = counted
+ *   slot_of_row  NULL (identity; then n_slots >= P) or device int32 [P]; a negative entry ignores the row, and so does
+ *                an entry >= n_slots (bounded in the kernel: never written through).  PRECONDITION: the entries in
+ *                [0, n_slots) are distinct (true of the render_indices of any LOD cut) -- slots are updated with plain
+ *                read-modify-writes.
+ *   tmp          hgs_raster_contrib_tmp_bytes(L) bytes of device scratch, uninitialised; L as for hgs_raster_bwd (the
+ *                L_cap of a single-call forward; a forward that returned HGS_ERR_CAPACITY must have been completed by
+ *                stage 2 first).
+ * Asynchronous on `stream`, no host wait, no atomics: the same inputs give the same bits on every run.  L == 0 or
+ * P == 0 returns HGS_OK and writes nothing.  Refused with HGS_ERR_INVALID before any HIP call (hgs_last_error names
+ * it): what the forward's argument check refuses, lod_per_pixel != 0 (not built), a null output, n_slots < 1,
+ * n_slots < P without slot_of_row, a null workspace or tmp.  lod_half_rows is ALLOWED: the call reads the float32
+ * records, lists and offsets of the forward and none of its attribute rows. */
+size_t hgs_raster_contrib_tmp_bytes(uint32_t L);
+int hgs_raster_contrib(const hgs_raster_args* a, const void* geom_ws, const void* bin_ws, const void* img_ws,
+                       uint32_t L, const uint8_t* pixel_mask, const int32_t* slot_of_row, int64_t n_slots,
+                       float* wmax, double* wsum, int64_t* count, void* tmp, hgs_stream_t stream, int device);
+
 /* SH part of the backward for up to HGS_MAX_DEFERRED_VIEWS views of the SAME Gaussians in one pass (gradient
  * accumulation over the views of one optimiser step / of one data-parallel rank): the [P,M,3] coefficients are read
  * once and dL_dshs is written once, instead of once per view.  Each view ran hgs_raster_bwd with
