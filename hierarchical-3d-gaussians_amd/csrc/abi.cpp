@@ -473,6 +473,31 @@ int hgs_raster_contrib(const hgs_raster_args* a, const void* geom_ws, const void
   return launch_raster_contrib(*a, g, b, w, L, pixel_mask, slot_of_row, n_slots, wmax, wsum, count, s);
 }
 
+size_t hgs_raster_attribute_tmp_bytes(uint32_t L) { return AttributeWs::bytes(L); }
+
+int hgs_raster_attribute(const hgs_raster_args* a, const void* geom_ws, const void* bin_ws, const void* img_ws,
+                         uint32_t L, const float* image, int32_t channels, const uint8_t* pixel_mask,
+                         const int32_t* slot_of_row, int64_t n_slots, double* out, double* wsum, void* tmp,
+                         hgs_stream_t stream, int device) {
+  int rc = validate(a);
+  if (rc) return rc;
+  if (a->lod_per_pixel != 0) { set_error("hgs_raster_attribute: lod_per_pixel = %d is not built (the weights follow the per-Gaussian remap only)", a->lod_per_pixel); return HGS_ERR_INVALID; }
+  if (channels < 1 || channels > 3) { set_error("hgs_raster_attribute: channels = %d, need 1..3", channels); return HGS_ERR_INVALID; }
+  if (!image) { set_error("hgs_raster_attribute: null image"); return HGS_ERR_INVALID; }
+  if (!out) { set_error("hgs_raster_attribute: null output (out)"); return HGS_ERR_INVALID; }
+  if (n_slots < 1) { set_error("hgs_raster_attribute: n_slots = %lld, need >= 1", (long long)n_slots); return HGS_ERR_INVALID; }
+  if (!slot_of_row && n_slots < a->P) { set_error("hgs_raster_attribute: n_slots = %lld < P = %d without slot_of_row (the identity map)", (long long)n_slots, a->P); return HGS_ERR_INVALID; }
+  if (a->P == 0 || L == 0) return HGS_OK;
+  if (!geom_ws || !bin_ws || !img_ws || !tmp) { set_error("hgs_raster_attribute: null workspace (geom / bin / img / tmp)"); return HGS_ERR_INVALID; }
+  HGS_HIP(hipSetDevice(device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int T = grid_x(a->width) * grid_y(a->height);
+  const GeomWs g = GeomWs::carve_from(const_cast<void*>(geom_ws), a->P);
+  const BinWs b = BinWs::carve_from(const_cast<void*>(bin_ws), L, T);
+  const AttributeWs w = AttributeWs::carve_from(tmp, L);
+  return launch_raster_attribute(*a, g, b, w, L, image, channels, pixel_mask, slot_of_row, n_slots, out, wsum, s);
+}
+
 int hgs_raster_sh_bwd_batched(const hgs_sh_bwd_view* views, int32_t n_views, int32_t P, int32_t M, int32_t sh_degree,
                               const float* means3D, const float* shs, float* dL_dshs, float* dL_dmeans3D,
                               int32_t accumulate, hgs_stream_t stream, int device) {

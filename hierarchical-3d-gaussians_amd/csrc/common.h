@@ -130,6 +130,15 @@ struct ContribWs {
   static ContribWs carve_from(void* base, uint32_t L) { Carver c(base); return layout(c, L); }
 };
 
+// Scratch of the image attribution (attribute.hip): one 16-byte record per (tile, Gaussian) instance, in emission
+// order like ContribWs::inst; written whole by the tile kernel, so it needs no clearing
+struct AttributeWs {
+  float* inst;             // [L,4] (A0, A1, A2, sum of weights)
+  static AttributeWs layout(Carver& c, uint32_t L);    // attribute.hip
+  static size_t bytes(uint32_t L) { Carver c(nullptr); layout(c, L); return c.bytes(kAlign); }
+  static AttributeWs carve_from(void* base, uint32_t L) { Carver c(base); return layout(c, L); }
+};
+
 inline int grid_x(int W) { return (W + kTile - 1) / kTile; }
 inline int grid_y(int H) { return (H + kTile - 1) / kTile; }
 inline int tile_bits(int T) {
@@ -275,6 +284,11 @@ int launch_render_bwd(const hgs_raster_args& a, const GeomWs& g, const BinWs& b,
 int launch_raster_contrib(const hgs_raster_args& a, const GeomWs& g, const BinWs& b, const ContribWs& w, uint32_t L,
                           const uint8_t* pixel_mask, const int32_t* slot_of_row, int64_t n_slots, float* wmax,
                           double* wsum, int64_t* count, hipStream_t s);
+// a planar [channels, H, W] image attributed to the rows that blend it, on the forward whose workspaces g / b are
+// (attribute.hip); channels in 1..3, L: what w was carved with
+int launch_raster_attribute(const hgs_raster_args& a, const GeomWs& g, const BinWs& b, const AttributeWs& w, uint32_t L,
+                            const float* image, int channels, const uint8_t* pixel_mask, const int32_t* slot_of_row,
+                            int64_t n_slots, double* out, double* wsum, hipStream_t s);
 // L: the frame's instance count (a frame of long runs sums them with kernels of their own in front of K8a; w.inst_grads
 // is consumed: they leave every segment's sums over the segment's first records)
 int launch_preprocess_bwd(const hgs_raster_args& a, const GeomWs& g, const BwdWs& w, const hgs_raster_grads& out, uint32_t L,

@@ -629,6 +629,62 @@ def raster_contributions(call, wmax, wsum, count, slot_of_row=None, pixel_mask=N
                                       _stream(dev), dev.index or 0), "hgs_raster_contrib")
 
 
+def raster_attribute(call, image, out, wsum=None, slot_of_row=None, pixel_mask=None):
+    """A per-pixel image attributed to the rows of the forward that returned ``call`` (hgs_raster_attribute; DESIGN.md
+    section 7, f-23), accumulated IN PLACE: ``out[slot, c] += sum_p w(p) * image[c, p]`` and, when given,
+    ``wsum[slot] += sum_p w(p)`` over the counted pixels the row is blended at, ``w = alpha * T`` as K6 blends it.
+    ``image``: float32 [C, H, W] with C in 1..3, or [H, W] for C = 1, on the forward's device; ``out``: float64 [S, C], or
+    [S] for C = 1; ``wsum``: float64 [S]; ``slot_of_row`` and ``pixel_mask`` as for ``raster_contributions``.  Entries
+    of rows that are blended nowhere keep their bits: zero-fill once, call once per view."""
+    lib = _lib.lib()
+    dev, P = call.device, call.P
+    if not torch.is_tensor(image) or not image.is_cuda or image.device != dev:
+        raise RuntimeError(f"image must be a tensor on the forward's device {dev}")
+    if image.dtype != torch.float32 or image.dim() not in (2, 3):
+        raise RuntimeError("image must be a float32 tensor [C, H, W], or [H, W] for one channel")
+    Cn = 1 if image.dim() == 2 else int(image.shape[0])
+    if not 1 <= Cn <= 3:
+        raise RuntimeError(f"image must have 1 to 3 channels, got {Cn}")
+    if tuple(image.shape[-2:]) != (call.H, call.W):
+        raise RuntimeError(f"image must be [C, {call.H}, {call.W}] like the forward's, got {tuple(image.shape)}")
+    image = image.contiguous()
+    outs = ((out, "out"),) if wsum is None else ((out, "out"), (wsum, "wsum"))
+    for t, name in outs:
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != dev:
+            raise RuntimeError(f"{name} must be a tensor on the forward's device {dev}")
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise RuntimeError(f"{name} must be a contiguous {torch.float64} tensor (it is written in place)")
+    if not (out.dim() == 2 and out.shape[1] == Cn) and not (out.dim() == 1 and Cn == 1):
+        raise RuntimeError(f"out must be [S, {Cn}]" + (" or [S]" if Cn == 1 else "") + f", got {tuple(out.shape)}")
+    S = int(out.shape[0])
+    if S < 1 or (wsum is not None and (wsum.dim() != 1 or wsum.numel() != S)):
+        raise RuntimeError(f"out / wsum must have the same length >= 1 (got {S}, {None if wsum is None else tuple(wsum.shape)})")
+    if slot_of_row is None:
+        if S < P:
+            raise RuntimeError(f"{S} slots for {P} op rows: pass slot_of_row, or arrays of at least {P} entries")
+    else:
+        if not torch.is_tensor(slot_of_row) or slot_of_row.device != dev or slot_of_row.dtype != torch.int32:
+            raise RuntimeError(f"slot_of_row must be an int32 tensor on {dev}")
+        if slot_of_row.numel() != P:
+            raise RuntimeError(f"slot_of_row must hold one entry per op row ({P}), got {slot_of_row.numel()}")
+        slot_of_row = slot_of_row.contiguous()
+    if pixel_mask is not None:
+        if not torch.is_tensor(pixel_mask) or pixel_mask.device != dev or pixel_mask.dtype != torch.uint8:
+            raise RuntimeError(f"pixel_mask must be a uint8 tensor on {dev}")
+        if pixel_mask.numel() != call.W * call.H:
+            raise RuntimeError(f"pixel_mask must hold H * W = {call.W * call.H} entries, got {pixel_mask.numel()}")
+        pixel_mask = pixel_mask.contiguous()
+    if P == 0 or call.L == 0:
+        return
+    # the instance scratch comes from the arena like every other workspace (uninitialised: the tile kernel writes
+    # every record)
+    tmp = _arena(int(lib.hgs_raster_attribute_tmp_bytes(call.L_ws)), dev)
+    p = _lib.ptr
+    _lib.check(lib.hgs_raster_attribute(C.byref(call.args), call.p_geom, call.p_bin, call.p_img, call.L_ws, p(image), Cn,
+                                        p(pixel_mask), p(slot_of_row), S, p(out), p(wsum), p(tmp), _stream(dev),
+                                        dev.index or 0), "hgs_raster_attribute")
+
+
 def mark_visible(means3D, viewmatrix, projmatrix):
     """Frustum test used by the upstream API (z > 0.2 in view space)."""
     means3D = _require_gpu(means3D, "means3D")

@@ -184,3 +184,177 @@ def low_contribution_mask(nodes, scores: Scores, max_weight_below=None, sum_belo
     if unseen == "remove":
         low |= ~seen
     return (leaf & low).to(torch.uint8)
+
+
+# ---- attribution of per-pixel images (csrc/attribute.hip) -----------------------------------------
+@dataclass
+class Attribution:
+    """``acc[s, c] = sum over views and pixels of w * f_c`` for S slots and C channels, the weights' own sum and, as in
+    ``Scores``, in how many views the slot was an op row::
+
+        err = lod_error_hierarchy(h, cameras, tau_px=3.0)        # Attribution over the N nodes, C = 1
+        worst = err.mean()[:, 0].argsort(descending=True)        # the nodes that stand in worst for what is below them
+    """
+    acc: torch.Tensor        # float64 [S, C]
+    wsum: torch.Tensor       # float64 [S]
+    entries: torch.Tensor    # int64 [S]
+    views: int = 0
+
+    @staticmethod
+    def zeros(S, device, channels=1) -> "Attribution":
+        if not 1 <= int(channels) <= 3:
+            raise ValueError(f"1 to 3 channels can be attributed, not {channels}")
+        return Attribution(torch.zeros(int(S), int(channels), dtype=torch.float64, device=device),
+                           torch.zeros(int(S), dtype=torch.float64, device=device),
+                           torch.zeros(int(S), dtype=torch.int64, device=device), 0)
+
+    def merge(self, other: "Attribution") -> "Attribution":
+        """The attribution over both view sets (sums); a new object."""
+        if other.acc.shape != self.acc.shape:
+            raise ValueError(f"an Attribution of shape {tuple(other.acc.shape)} cannot be merged into {tuple(self.acc.shape)}")
+        return Attribution(self.acc + other.acc, self.wsum + other.wsum, self.entries + other.entries,
+                           self.views + other.views)
+
+    def mean(self) -> torch.Tensor:
+        """``acc / wsum``, the weighted mean of the image under every slot; 0 where ``wsum == 0``.  float64 [S, C]."""
+        seen = self.wsum != 0
+        return torch.where(seen[:, None], self.acc / torch.where(seen, self.wsum, torch.ones_like(self.wsum))[:, None],
+                           torch.zeros_like(self.acc))
+
+    def numpy(self) -> dict:
+        return dict(acc=self.acc.cpu().numpy(), wsum=self.wsum.cpu().numpy(), entries=self.entries.cpu().numpy(),
+                    views=np.int64(self.views))
+
+
+def attribute_view(att: Attribution, raster_settings, image, means3D, opacities, shs=None, colors_precomp=None,
+                   scales=None, rotations=None, cov3D_precomp=None, slot_of_row=None, pixel_mask=None, skybox_points=0):
+    """One view into ``att`` (in place): the no-grad forward ``score_view`` makes, on either of its routes, then the
+    attribution call on its workspaces.  ``image``: float32 [C, H, W] (or [H, W] for C = 1) on the device, or a callable
+    that takes the forward's rendered [3, H, W] and returns such a tensor -- an error image of the same forward without
+    a second render.  ``slot_of_row``, ``pixel_mask``, ``skybox_points`` as for ``score_view``.  Returns the forward's
+    ``call``."""
+    from diff_gaussian_rasterization import _C
+    rs = raster_settings
+    lod = rs.render_indices is not None and rs.render_indices.numel() > 0
+    with torch.no_grad():
+        if lod:
+            if colors_precomp is not None or cov3D_precomp is not None:
+                raise RuntimeError("in-op LOD interpolation needs shs and scales/rotations (no precomputed colours/covariances)")
+            n, K = int(rs.render_indices.numel()), int(skybox_points)
+            w, kids = rs.interpolation_weights, rs.num_node_kids
+            if K > 0:
+                w = torch.cat((w[:n], torch.ones(K, dtype=w.dtype, device=w.device)))
+                kids = torch.cat((kids[:n], torch.ones(K, dtype=kids.dtype, device=kids.device)))
+            empty = rs.render_indices.new_empty(0)
+            res = _C.rasterize_gaussians(
+                rs.bg, means3D, None, opacities, scales, rotations, rs.scale_modifier, None, rs.viewmatrix, rs.projmatrix,
+                rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, shs, rs.sh_degree, rs.campos, rs.prefiltered,
+                rs.debug, empty, empty, w, kids, rs.do_depth, prepare_backward=False,
+                lod=(rs.render_indices, rs.parent_indices, K))
+            if slot_of_row is None:
+                slot_of_row = torch.cat((rs.render_indices.to(torch.int32),
+                                         torch.full((K,), -1, dtype=torch.int32, device=rs.render_indices.device)))
+        else:
+            res = _C.rasterize_gaussians(
+                rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3D_precomp,
+                rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, shs, rs.sh_degree,
+                rs.campos, rs.prefiltered, rs.debug, rs.render_indices, rs.parent_indices, rs.interpolation_weights,
+                rs.num_node_kids, rs.do_depth, prepare_backward=False)
+        color, call = res[1], res[-1]
+        f = image(color) if callable(image) else image
+        _C.raster_attribute(call, f, att.acc, wsum=att.wsum, slot_of_row=slot_of_row, pixel_mask=pixel_mask)
+        S = att.entries.shape[0]
+        if slot_of_row is None:
+            att.entries[:call.P] += 1
+        else:
+            s = slot_of_row.long()
+            s = s[(s >= 0) & (s < S)]
+            att.entries[s] += 1             # (distinct by the precondition)
+        att.views += 1
+    return call
+
+
+def _nodes_only(h):
+    N = h.num_nodes
+    return h if h.xyz.shape[0] == N else type(h)(h.xyz[:N], h.shs[:N], h.alpha[:N], h.log_scales[:N], h.rots[:N], h.nodes, h.boxes)
+
+
+def abs_error_image(target):
+    """-> the callable ``attribute_view`` takes: the forward's render -> mean over the three channels of
+    ``|render - target|``, float32 [1, H, W]."""
+    return lambda color: (color - target).abs().mean(dim=0, keepdim=True)
+
+
+def error_hierarchy(h, cameras, targets, tau_px=0.0, frustum=True, pixel_masks=None) -> Attribution:
+    """Per-node photometric error of ``h`` over ``cameras`` against ``targets`` (one float32 [3, H, W] per camera, moved
+    to the device): per camera ``score_hierarchy``'s cut and render, ``e = mean over the three channels of |render -
+    target|`` (C = 1), attributed to the cut's ``render_indices``: ``acc[n, 0] = sum over views and pixels of w_n e``.
+    ``mean()`` is the error an average pixel under node n shows."""
+    if not h.nodes.is_cuda:
+        raise RuntimeError("error_hierarchy works on the GPU: upload the hierarchy first (there is no CPU path)")
+    dev, N = h.nodes.device, h.num_nodes
+    cameras, targets = list(cameras), list(targets)
+    if len(targets) != len(cameras):
+        raise ValueError(f"{len(targets)} targets for {len(cameras)} cameras")
+    if pixel_masks is not None and len(pixel_masks) != len(cameras):
+        raise ValueError(f"{len(pixel_masks)} pixel masks for {len(cameras)} cameras")
+    for k, (cam, t) in enumerate(zip(cameras, targets)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (3, int(cam.image_height), int(cam.image_width)):
+            raise ValueError(f"target {k} must be a float32 tensor [3, {int(cam.image_height)}, {int(cam.image_width)}]")
+    hn = _nodes_only(h)
+    rows = activated(hn)
+    bounds = None
+    if frustum:
+        from .frustum import cull_bounds
+        bounds = cull_bounds(h.nodes, rows["means3D"], rows["scales"])
+    att = Attribution.zeros(N, dev, channels=1)
+    for k, cam in enumerate(cameras):
+        ri, pi, w, kids = view_cut(hn, cam, tau_of(tau_px, cam.tanfovx, cam.image_width), frustum, bounds)
+        if ri.numel() == 0:              # nothing of the hierarchy in this view
+            att.views += 1
+            continue
+        attribute_view(att, _settings(cam, dev, ri.contiguous(), pi.contiguous(), w.contiguous(), kids.contiguous()),
+                       abs_error_image(targets[k].to(dev)),
+                       pixel_mask=None if pixel_masks is None else pixel_masks[k], **rows)
+    return att
+
+
+def render_hierarchy(h, cam, tau_px=0.0, frustum=True, bounds=None):
+    """The no-grad render [3, H, W] of ``h``'s node rows at the cut of ``tau_px`` pixels on the in-op LOD route, as
+    ``score_hierarchy`` renders it (a clone: a later forward cannot touch it); black when the cut is empty.  ``bounds``:
+    ``hgs.frustum.cull_bounds`` of the hierarchy when the caller has them already."""
+    from diff_gaussian_rasterization import _C
+    dev = h.nodes.device
+    hn = _nodes_only(h)
+    rows = activated(hn)
+    if frustum and bounds is None:
+        from .frustum import cull_bounds
+        bounds = cull_bounds(h.nodes, rows["means3D"], rows["scales"])
+    ri, pi, w, kids = view_cut(hn, cam, tau_of(tau_px, cam.tanfovx, cam.image_width), frustum, bounds)
+    if ri.numel() == 0:
+        return torch.zeros(3, int(cam.image_height), int(cam.image_width), device=dev)
+    rs = _settings(cam, dev, ri.contiguous(), pi.contiguous(), w.contiguous(), kids.contiguous())
+    empty = ri.new_empty(0)
+    with torch.no_grad():
+        color = _C.rasterize_gaussians(
+            rs.bg, rows["means3D"], None, rows["opacities"], rows["scales"], rows["rotations"], rs.scale_modifier, None,
+            rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, rows["shs"],
+            rs.sh_degree, rs.campos, rs.prefiltered, rs.debug, empty, empty, rs.interpolation_weights, rs.num_node_kids,
+            rs.do_depth, prepare_backward=False, lod=(rs.render_indices, rs.parent_indices, 0))[1]
+    return color.clone()
+
+
+def lod_error_hierarchy(h, cameras, tau_px, ref_tau_px=0.0, frustum=True) -> Attribution:
+    """Where do the interior rows of ``h`` misrepresent what is below them?  ``error_hierarchy`` at ``tau_px`` whose
+    targets are the same hierarchy rendered at the finer ``ref_tau_px`` (default 0: the leaves), no grad, each target
+    cloned before the second forward.  With ``ref_tau_px == tau_px`` the error is zero everywhere."""
+    if not h.nodes.is_cuda:
+        raise RuntimeError("lod_error_hierarchy works on the GPU: upload the hierarchy first (there is no CPU path)")
+    cameras = list(cameras)
+    bounds = None
+    if frustum:
+        from .frustum import cull_bounds
+        rows = activated(_nodes_only(h))
+        bounds = cull_bounds(h.nodes, rows["means3D"], rows["scales"])
+    targets = [render_hierarchy(h, cam, ref_tau_px, frustum, bounds) for cam in cameras]
+    return error_hierarchy(h, cameras, targets, tau_px=tau_px, frustum=frustum)

@@ -243,6 +243,36 @@ int hgs_raster_contrib(const hgs_raster_args* a, const void* geom_ws, const void
                        uint32_t L, const uint8_t* pixel_mask, const int32_t* slot_of_row, int64_t n_slots,
                        float* wmax, double* wsum, int64_t* count, void* tmp, hgs_stream_t stream, int device);
 
+/* A per-pixel image attributed to the Gaussians that blend it, on ONE forward whose workspaces are intact (DESIGN.md
+ * section 7, f-23): for every row i < P of the op that the forward blended into at least one counted pixel, with
+ * s = slot_of_row[i],
+ *     out[s * channels + c] += sum over the counted pixels p the row is blended at of  w(p) * image[c][p]      float64
+ *     wsum[s]               += sum of w over the same pixels (when wsum is given)                            float64
+ * with w = alpha * T_before exactly as hgs_raster_contrib states it ("blended" is K6's decision on the same records in
+ * the same float32 expressions), and every other entry keeps its bits: zero-fill once, call once per view.  wsum
+ * equals hgs_raster_contrib's bit for bit, and so does a channel of ones.  w * image is one rounded float32 product per
+ * pixel; a pixel that is not counted, or at which the row is not blended, contributes a selected zero and its image value
+ * is not multiplied in (masked-out and outside pixels are not read at all): a NaN or infinity there reaches no output.
+ * Stands in for nothing upstream; in this library it replaces dL / d colors_precomp of hgs_raster_bwd seeded with the
+ * image -- the whole backward, refused on the in-op LOD route and without a slot map.
+ *   image        device float32, planar [channels, H, W] (the layout the rasterizer returns); channels in 1..3
+ *   pixel_mask   NULL (all pixels) or device uint8 [H*W], non-zero = counted
+ *   slot_of_row  NULL (identity; then n_slots >= P) or device int32 [P]; a negative entry ignores the row, and so does
+ *                an entry >= n_slots (bounded in the kernel: never written through).  PRECONDITION: the entries in
+ *                [0, n_slots) are distinct -- slots are updated with plain read-modify-writes.
+ *   out          device float64 [n_slots, channels];  wsum: device float64 [n_slots] or NULL
+ *   tmp          hgs_raster_attribute_tmp_bytes(L) bytes of device scratch, uninitialised; L as for hgs_raster_contrib.
+ * Asynchronous on `stream`, no host wait, no atomics: the same inputs give the same bits on every run.  L == 0 or
+ * P == 0 returns HGS_OK and writes nothing.  Refused with HGS_ERR_INVALID before any HIP call (hgs_last_error names
+ * it): everything hgs_raster_contrib refuses (the forward's argument check, lod_per_pixel != 0, n_slots < 1,
+ * n_slots < P without slot_of_row, a null workspace or tmp), channels outside 1..3, a null image, a null out.
+ * lod_half_rows is ALLOWED: none of the forward's attribute rows is read. */
+size_t hgs_raster_attribute_tmp_bytes(uint32_t L);
+int hgs_raster_attribute(const hgs_raster_args* a, const void* geom_ws, const void* bin_ws, const void* img_ws,
+                         uint32_t L, const float* image, int32_t channels, const uint8_t* pixel_mask,
+                         const int32_t* slot_of_row, int64_t n_slots, double* out /* [n_slots, channels] */,
+                         double* wsum /* [n_slots] or NULL */, void* tmp, hgs_stream_t stream, int device);
+
 /* SH part of the backward for up to HGS_MAX_DEFERRED_VIEWS views of the SAME Gaussians in one pass (gradient
  * accumulation over the views of one optimiser step / of one data-parallel rank): the [P,M,3] coefficients are read
  * once and dL_dshs is written once, instead of once per view.  Each view ran hgs_raster_bwd with
