@@ -498,6 +498,30 @@ int hgs_raster_attribute(const hgs_raster_args* a, const void* geom_ws, const vo
   return launch_raster_attribute(*a, g, b, w, L, image, channels, pixel_mask, slot_of_row, n_slots, out, wsum, s);
 }
 
+int hgs_raster_pixels(const hgs_raster_args* a, const void* geom_ws, const void* bin_ws, const void* img_ws, uint32_t L,
+                      const int32_t* slot_of_row, int64_t n_slots, const hgs_raster_pixel_planes* out,
+                      hgs_stream_t stream, int device) {
+  int rc = validate(a);
+  if (rc) return rc;
+  if (a->lod_per_pixel != 0) { set_error("hgs_raster_pixels: lod_per_pixel = %d is not built (the readout follows the per-Gaussian remap only)", a->lod_per_pixel); return HGS_ERR_INVALID; }
+  if (!out || (!out->alpha && !out->count && !out->front && !out->back && !out->heaviest && !out->wmax && !out->median && !out->median_depth)) {
+    set_error("hgs_raster_pixels: null planes (at least one of alpha / count / front / back / heaviest / wmax / median / median_depth is needed)");
+    return HGS_ERR_INVALID;
+  }
+  if (slot_of_row && n_slots < 1) { set_error("hgs_raster_pixels: n_slots = %lld with slot_of_row, need >= 1", (long long)n_slots); return HGS_ERR_INVALID; }
+  const bool empty = a->P == 0 || L == 0;
+  if (!empty && (!geom_ws || !bin_ws || !img_ws)) { set_error("hgs_raster_pixels: null workspace (geom / bin / img)"); return HGS_ERR_INVALID; }
+  HGS_HIP(hipSetDevice(device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  GeomWs g{};
+  BinWs b{};
+  if (!empty) {
+    g = GeomWs::carve_from(const_cast<void*>(geom_ws), a->P);
+    b = BinWs::carve_from(const_cast<void*>(bin_ws), L, grid_x(a->width) * grid_y(a->height));
+  }
+  return launch_raster_pixels(*a, g, b, empty, slot_of_row, n_slots, *out, s);
+}
+
 int hgs_raster_sh_bwd_batched(const hgs_sh_bwd_view* views, int32_t n_views, int32_t P, int32_t M, int32_t sh_degree,
                               const float* means3D, const float* shs, float* dL_dshs, float* dL_dmeans3D,
                               int32_t accumulate, hgs_stream_t stream, int device) {

@@ -289,6 +289,10 @@ int launch_raster_contrib(const hgs_raster_args& a, const GeomWs& g, const BinWs
 int launch_raster_attribute(const hgs_raster_args& a, const GeomWs& g, const BinWs& b, const AttributeWs& w, uint32_t L,
                             const float* image, int channels, const uint8_t* pixel_mask, const int32_t* slot_of_row,
                             int64_t n_slots, double* out, double* wsum, hipStream_t s);
+// the per-pixel readout of the forward whose workspaces g / b are (pixels.hip); `empty`: no instance was rendered, no
+// workspace is read and the planes take the "nothing" values
+int launch_raster_pixels(const hgs_raster_args& a, const GeomWs& g, const BinWs& b, bool empty,
+                         const int32_t* slot_of_row, int64_t n_slots, const hgs_raster_pixel_planes& out, hipStream_t s);
 // L: the frame's instance count (a frame of long runs sums them with kernels of their own in front of K8a; w.inst_grads
 // is consumed: they leave every segment's sums over the segment's first records)
 int launch_preprocess_bwd(const hgs_raster_args& a, const GeomWs& g, const BwdWs& w, const hgs_raster_grads& out, uint32_t L,

@@ -685,6 +685,49 @@ def raster_attribute(call, image, out, wsum=None, slot_of_row=None, pixel_mask=N
                                         dev.index or 0), "hgs_raster_attribute")
 
 
+PIXEL_PLANES = _lib.PIXEL_PLANES
+_FLOAT_PLANES = ("alpha", "wmax", "median_depth")
+
+
+def raster_pixels(call, slot_of_row=None, n_slots=None, want=PIXEL_PLANES):
+    """What every pixel of the forward that returned ``call`` shows (hgs_raster_pixels): a
+    dict of [H, W] tensors on the forward's device, one per name in ``want`` -- ``alpha`` float32 (1 - final_T),
+    ``count`` int32 (rows blended), ``front`` / ``back`` int32 (first / last blended row), ``heaviest`` int32 and
+    ``wmax`` float32 (the row of the largest weight alpha * T and that weight), ``median`` int32 and ``median_depth``
+    float32 (the first row after which T < 0.5 and its view-space depth).  Ids are op rows, or ``slot_of_row[row]``
+    (int32 [P]) when that lies in [0, ``n_slots``) and -2 when it does not (``n_slots`` defaults to 2^31 - 1: every
+    non-negative entry names the row); -1 where no row answers.  Every pixel is written."""
+    dev, P = call.device, call.P
+    if isinstance(want, str):
+        want = (want,)
+    want = tuple(want)
+    if not want:
+        raise RuntimeError(f"want must name at least one plane of {PIXEL_PLANES}")
+    for name in want:
+        if name not in PIXEL_PLANES:
+            raise RuntimeError(f"unknown plane {name!r}: want takes names of {PIXEL_PLANES}")
+    if slot_of_row is None:
+        if n_slots is not None:
+            raise RuntimeError("n_slots bounds slot_of_row: pass both, or neither (ids are then the op rows)")
+        S = 0
+    else:
+        if not torch.is_tensor(slot_of_row) or slot_of_row.device != dev or slot_of_row.dtype != torch.int32:
+            raise RuntimeError(f"slot_of_row must be an int32 tensor on {dev}")
+        if slot_of_row.numel() != P:
+            raise RuntimeError(f"slot_of_row must hold one entry per op row ({P}), got {slot_of_row.numel()}")
+        S = 2 ** 31 - 1 if n_slots is None else int(n_slots)
+        if S < 1:
+            raise RuntimeError(f"n_slots must be >= 1, got {S}")
+        slot_of_row = slot_of_row.contiguous()
+    out = {name: torch.empty((call.H, call.W), dtype=torch.float32 if name in _FLOAT_PLANES else torch.int32, device=dev)
+           for name in want}
+    planes = _lib.RasterPixelPlanes(**{name: t.data_ptr() for name, t in out.items()})
+    _lib.check(_lib.lib().hgs_raster_pixels(C.byref(call.args), call.p_geom, call.p_bin, call.p_img, call.L_ws,
+                                     _lib.ptr(slot_of_row), S, C.byref(planes), _stream(dev), dev.index or 0),
+               "hgs_raster_pixels")
+    return out
+
+
 def mark_visible(means3D, viewmatrix, projmatrix):
     """Frustum test used by the upstream API (z > 0.2 in view space)."""
     means3D = _require_gpu(means3D, "means3D")

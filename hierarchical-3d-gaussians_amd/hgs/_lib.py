@@ -152,6 +152,14 @@ class DensifyTensor(C.Structure):
 DENSIFY_COPY, DENSIFY_XYZ, DENSIFY_SCALING = 0, 1, 2
 
 
+# hgs_raster_pixel_planes: the field order is the order of the planes everywhere (PIXEL_PLANES)
+PIXEL_PLANES = ("alpha", "count", "front", "back", "heaviest", "wmax", "median", "median_depth")
+
+
+class RasterPixelPlanes(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in PIXEL_PLANES]
+
+
 class StepArgs(C.Structure):
     _fields_ = [("P", C.c_int64), ("n", C.c_int64), ("radii", C.c_void_p), ("indices", C.c_void_p),
                 ("visible", C.c_void_p), ("means2D_grad", C.c_void_p), ("max_radii2D", C.c_void_p),
@@ -197,6 +205,8 @@ SIGNATURES = {
     "hgs_raster_attribute_tmp_bytes": (C.c_size_t, [C.c_uint32]),
     "hgs_raster_attribute": (C.c_int, [C.POINTER(RasterArgs), _P, _P, _P, C.c_uint32, _P, C.c_int32, _P, _P, C.c_int64,
                                        _P, _P, _P, _P, C.c_int]),
+    "hgs_raster_pixels": (C.c_int, [C.POINTER(RasterArgs), _P, _P, _P, C.c_uint32, _P, C.c_int64,
+                                    C.POINTER(RasterPixelPlanes), _P, C.c_int]),
     "hgs_raster_views_get": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _P, _P, _P,
                                        C.POINTER(RasterViews)]),
     "hgs_sort_tmp_bytes": (C.c_size_t, [C.c_uint32]),

@@ -44,6 +44,40 @@ class Scores:
                     entries=self.entries.cpu().numpy(), views=np.int64(self.views))
 
 
+def _view_forward(rs, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, slot_of_row,
+                  skybox_points):
+    """The forward ``score_view``, ``attribute_view`` and ``hgs.picking.read_view`` make (call it under no_grad):
+    ``prepare_backward`` off; the in-op LOD route when ``rs.render_indices`` is non-empty, with the last
+    ``skybox_points`` rows appended as the product path appends them.  -> (the op's result tuple, slot_of_row); a
+    ``slot_of_row`` of None becomes, on the LOD route, the cut's ``render_indices`` with -1 for the skybox rows."""
+    from diff_gaussian_rasterization import _C
+    lod = rs.render_indices is not None and rs.render_indices.numel() > 0
+    if lod:
+        if colors_precomp is not None or cov3D_precomp is not None:
+            raise RuntimeError("in-op LOD interpolation needs shs and scales/rotations (no precomputed colours/covariances)")
+        n, K = int(rs.render_indices.numel()), int(skybox_points)
+        w, kids = rs.interpolation_weights, rs.num_node_kids
+        if K > 0:
+            w = torch.cat((w[:n], torch.ones(K, dtype=w.dtype, device=w.device)))
+            kids = torch.cat((kids[:n], torch.ones(K, dtype=kids.dtype, device=kids.device)))
+        empty = rs.render_indices.new_empty(0)
+        res = _C.rasterize_gaussians(
+            rs.bg, means3D, None, opacities, scales, rotations, rs.scale_modifier, None, rs.viewmatrix, rs.projmatrix,
+            rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, shs, rs.sh_degree, rs.campos, rs.prefiltered,
+            rs.debug, empty, empty, w, kids, rs.do_depth, prepare_backward=False,
+            lod=(rs.render_indices, rs.parent_indices, K))
+        if slot_of_row is None:
+            slot_of_row = torch.cat((rs.render_indices.to(torch.int32),
+                                     torch.full((K,), -1, dtype=torch.int32, device=rs.render_indices.device)))
+    else:
+        res = _C.rasterize_gaussians(
+            rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3D_precomp,
+            rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, shs, rs.sh_degree,
+            rs.campos, rs.prefiltered, rs.debug, rs.render_indices, rs.parent_indices, rs.interpolation_weights,
+            rs.num_node_kids, rs.do_depth, prepare_backward=False)
+    return res, slot_of_row
+
+
 def score_view(scores: Scores, raster_settings, means3D, opacities, shs=None, colors_precomp=None, scales=None,
                rotations=None, cov3D_precomp=None, slot_of_row=None, pixel_mask=None, skybox_points=0):
     """One view into ``scores`` (in place): a no-grad forward of the rasterizer as ``GaussianRasterizer`` makes it
@@ -53,32 +87,10 @@ def score_view(scores: Scores, raster_settings, means3D, opacities, shs=None, co
     cut's entries and -1 (ignored) for the skybox rows.  ``pixel_mask``: uint8 [H*W], non-zero = counted.  Returns the
     forward's ``call``."""
     from diff_gaussian_rasterization import _C
-    rs = raster_settings
-    lod = rs.render_indices is not None and rs.render_indices.numel() > 0
     with torch.no_grad():
-        if lod:
-            if colors_precomp is not None or cov3D_precomp is not None:
-                raise RuntimeError("in-op LOD interpolation needs shs and scales/rotations (no precomputed colours/covariances)")
-            n, K = int(rs.render_indices.numel()), int(skybox_points)
-            w, kids = rs.interpolation_weights, rs.num_node_kids
-            if K > 0:
-                w = torch.cat((w[:n], torch.ones(K, dtype=w.dtype, device=w.device)))
-                kids = torch.cat((kids[:n], torch.ones(K, dtype=kids.dtype, device=kids.device)))
-            empty = rs.render_indices.new_empty(0)
-            call = _C.rasterize_gaussians(
-                rs.bg, means3D, None, opacities, scales, rotations, rs.scale_modifier, None, rs.viewmatrix, rs.projmatrix,
-                rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, shs, rs.sh_degree, rs.campos, rs.prefiltered,
-                rs.debug, empty, empty, w, kids, rs.do_depth, prepare_backward=False,
-                lod=(rs.render_indices, rs.parent_indices, K))[-1]
-            if slot_of_row is None:
-                slot_of_row = torch.cat((rs.render_indices.to(torch.int32),
-                                         torch.full((K,), -1, dtype=torch.int32, device=rs.render_indices.device)))
-        else:
-            call = _C.rasterize_gaussians(
-                rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3D_precomp,
-                rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, shs, rs.sh_degree,
-                rs.campos, rs.prefiltered, rs.debug, rs.render_indices, rs.parent_indices, rs.interpolation_weights,
-                rs.num_node_kids, rs.do_depth, prepare_backward=False)[-1]
+        res, slot_of_row = _view_forward(raster_settings, means3D, opacities, shs, colors_precomp, scales, rotations,
+                                         cov3D_precomp, slot_of_row, skybox_points)
+        call = res[-1]
         _C.raster_contributions(call, scores.wmax, scores.wsum, scores.count, slot_of_row=slot_of_row,
                                 pixel_mask=pixel_mask)
         S = scores.entries.shape[0]
@@ -234,32 +246,9 @@ def attribute_view(att: Attribution, raster_settings, image, means3D, opacities,
     a second render.  ``slot_of_row``, ``pixel_mask``, ``skybox_points`` as for ``score_view``.  Returns the forward's
     ``call``."""
     from diff_gaussian_rasterization import _C
-    rs = raster_settings
-    lod = rs.render_indices is not None and rs.render_indices.numel() > 0
     with torch.no_grad():
-        if lod:
-            if colors_precomp is not None or cov3D_precomp is not None:
-                raise RuntimeError("in-op LOD interpolation needs shs and scales/rotations (no precomputed colours/covariances)")
-            n, K = int(rs.render_indices.numel()), int(skybox_points)
-            w, kids = rs.interpolation_weights, rs.num_node_kids
-            if K > 0:
-                w = torch.cat((w[:n], torch.ones(K, dtype=w.dtype, device=w.device)))
-                kids = torch.cat((kids[:n], torch.ones(K, dtype=kids.dtype, device=kids.device)))
-            empty = rs.render_indices.new_empty(0)
-            res = _C.rasterize_gaussians(
-                rs.bg, means3D, None, opacities, scales, rotations, rs.scale_modifier, None, rs.viewmatrix, rs.projmatrix,
-                rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, shs, rs.sh_degree, rs.campos, rs.prefiltered,
-                rs.debug, empty, empty, w, kids, rs.do_depth, prepare_backward=False,
-                lod=(rs.render_indices, rs.parent_indices, K))
-            if slot_of_row is None:
-                slot_of_row = torch.cat((rs.render_indices.to(torch.int32),
-                                         torch.full((K,), -1, dtype=torch.int32, device=rs.render_indices.device)))
-        else:
-            res = _C.rasterize_gaussians(
-                rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3D_precomp,
-                rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, shs, rs.sh_degree,
-                rs.campos, rs.prefiltered, rs.debug, rs.render_indices, rs.parent_indices, rs.interpolation_weights,
-                rs.num_node_kids, rs.do_depth, prepare_backward=False)
+        res, slot_of_row = _view_forward(raster_settings, means3D, opacities, shs, colors_precomp, scales, rotations,
+                                         cov3D_precomp, slot_of_row, skybox_points)
         color, call = res[1], res[-1]
         f = image(color) if callable(image) else image
         _C.raster_attribute(call, f, att.acc, wsum=att.wsum, slot_of_row=slot_of_row, pixel_mask=pixel_mask)

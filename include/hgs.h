@@ -273,6 +273,39 @@ int hgs_raster_attribute(const hgs_raster_args* a, const void* geom_ws, const vo
                          const int32_t* slot_of_row, int64_t n_slots, double* out /* [n_slots, channels] */,
                          double* wsum /* [n_slots] or NULL */, void* tmp, hgs_stream_t stream, int device);
 
+/* Per-pixel readout of ONE forward whose workspaces are intact: what a pixel shows.  For
+ * every pixel p inside the image take the rows K6 blended there, front to back, k = 1..n ("blended" is K6's decision on
+ * the same records in the same float32 expressions, as hgs_raster_contrib states it), with w_k = alpha_k * T_{k-1} and
+ * T_k as K6 computes them.  Each plane is a device array [H*W] or NULL; at least one must be given.
+ *     alpha         float32  1.0f - T_n (one float32 subtraction; the bits of 1 - final_T); 0 where n = 0
+ *     count         int32    n
+ *     front, back   int32    id of row k = 1 / k = n
+ *     heaviest      int32    id of the row with the largest w_k, the front-most one on equal bits;  wmax: that weight
+ *     median        int32    id of the first k with T_k < 0.5f;  median_depth: the view-space depth K1 stored for that
+ *                            row (bits copied); no such k: id -1, depth 0
+ * The id of op row i is slot_of_row[i] when that lies in [0, n_slots), i itself when slot_of_row is NULL, and -2 when
+ * the map ignores the row (negative or >= n_slots): an ignored row still occludes and counts in `count` and `alpha`, it
+ * only cannot be named.  Where there is no row the id is -1, wmax 0 and median_depth 0.  Every pixel inside the image is
+ * written in every given plane: the caller need not pre-fill.
+ * One launch, asynchronous on `stream`, no host wait, no atomics, no scratch: the same inputs give the same bits on
+ * every run.  L == 0 or P == 0 fills the planes with the "nothing" values (no workspace is read then).  Refused with
+ * HGS_ERR_INVALID before any HIP call (hgs_last_error names it): what the forward's argument check refuses,
+ * lod_per_pixel != 0 (not built), all planes NULL, a null workspace, n_slots < 1 with a map.  lod_half_rows and the
+ * in-op LOD route are ALLOWED: only records, lists, ranges and depths are read. */
+typedef struct {
+  float* alpha;
+  int32_t* count;
+  int32_t* front;
+  int32_t* back;
+  int32_t* heaviest;
+  float* wmax;
+  int32_t* median;
+  float* median_depth;
+} hgs_raster_pixel_planes;
+int hgs_raster_pixels(const hgs_raster_args* a, const void* geom_ws, const void* bin_ws, const void* img_ws, uint32_t L,
+                      const int32_t* slot_of_row, int64_t n_slots, const hgs_raster_pixel_planes* out,
+                      hgs_stream_t stream, int device);
+
 /* SH part of the backward for up to HGS_MAX_DEFERRED_VIEWS views of the SAME Gaussians in one pass (gradient
  * accumulation over the views of one optimiser step / of one data-parallel rank): the [P,M,3] coefficients are read
  * once and dL_dshs is written once, instead of once per view.  Each view ran hgs_raster_bwd with
