@@ -451,26 +451,63 @@ int hgs_raster_bwd(const hgs_raster_args* a, const void* geom_ws, const void* bi
   return HGS_TIMED(ST_PREPROCESS_BWD, s, launch_preprocess_bwd(*a, g, w, gr, L, s));
 }
 
+// What the three calls that read a finished forward share (hgs_raster_contrib / _attribute / _pixels), in two halves
+// because a call's own argument checks stand between them in the documented order of refusals.
+// First half: the argument check and the lod_per_pixel refusal.
+static int check_forward_read(const char* fn, const char* follows, const hgs_raster_args* a) {
+  const int rc = validate(a);
+  if (rc) return rc;
+  if (a->lod_per_pixel != 0) { set_error("%s: lod_per_pixel = %d is not built (the %s the per-Gaussian remap only)", fn, a->lod_per_pixel, follows); return HGS_ERR_INVALID; }
+  return HGS_OK;
+}
+
+// Second half: the slot-count checks, the null-workspace check, the device and the carving of the forward's workspaces.
+// `arrays`: n_slots is the length of per-slot output arrays (the identity map then needs P of them); otherwise it only
+// bounds slot_of_row.  An empty forward (P == 0 or L == 0) has nothing carved, and only a call that still has planes to
+// fill (`runs_empty`) selects the device for it; the others are done (f.empty, HGS_OK).
+struct ForwardRead {
+  GeomWs g{};
+  BinWs b{};
+  hipStream_t s = nullptr;
+  bool empty = true;
+};
+static int open_forward_read(const char* fn, const char* ws_names, const hgs_raster_args* a, const void* geom_ws,
+                             const void* bin_ws, const void* img_ws, bool tmp_missing, uint32_t L,
+                             const int32_t* slot_of_row, int64_t n_slots, bool arrays, bool runs_empty,
+                             hgs_stream_t stream, int device, ForwardRead& f) {
+  if (arrays) {
+    if (n_slots < 1) { set_error("%s: n_slots = %lld, need >= 1", fn, (long long)n_slots); return HGS_ERR_INVALID; }
+    if (!slot_of_row && n_slots < a->P) { set_error("%s: n_slots = %lld < P = %d without slot_of_row (the identity map)", fn, (long long)n_slots, a->P); return HGS_ERR_INVALID; }
+  } else if (slot_of_row && n_slots < 1) {
+    set_error("%s: n_slots = %lld with slot_of_row, need >= 1", fn, (long long)n_slots);
+    return HGS_ERR_INVALID;
+  }
+  f.empty = a->P == 0 || L == 0;
+  if (f.empty && !runs_empty) return HGS_OK;
+  if (!f.empty && (!geom_ws || !bin_ws || !img_ws || tmp_missing)) { set_error("%s: null workspace (%s)", fn, ws_names); return HGS_ERR_INVALID; }
+  HGS_HIP(hipSetDevice(device));
+  f.s = static_cast<hipStream_t>(stream);
+  if (!f.empty) {
+    f.g = GeomWs::carve_from(const_cast<void*>(geom_ws), a->P);
+    f.b = BinWs::carve_from(const_cast<void*>(bin_ws), L, grid_x(a->width) * grid_y(a->height));
+  }
+  return HGS_OK;
+}
+
 size_t hgs_raster_contrib_tmp_bytes(uint32_t L) { return ContribWs::bytes(L); }
 
 int hgs_raster_contrib(const hgs_raster_args* a, const void* geom_ws, const void* bin_ws, const void* img_ws,
                        uint32_t L, const uint8_t* pixel_mask, const int32_t* slot_of_row, int64_t n_slots,
                        float* wmax, double* wsum, int64_t* count, void* tmp, hgs_stream_t stream, int device) {
-  int rc = validate(a);
+  int rc = check_forward_read("hgs_raster_contrib", "statistics follow", a);
   if (rc) return rc;
-  if (a->lod_per_pixel != 0) { set_error("hgs_raster_contrib: lod_per_pixel = %d is not built (the statistics follow the per-Gaussian remap only)", a->lod_per_pixel); return HGS_ERR_INVALID; }
   if (!wmax || !wsum || !count) { set_error("hgs_raster_contrib: null output (wmax / wsum / count)"); return HGS_ERR_INVALID; }
-  if (n_slots < 1) { set_error("hgs_raster_contrib: n_slots = %lld, need >= 1", (long long)n_slots); return HGS_ERR_INVALID; }
-  if (!slot_of_row && n_slots < a->P) { set_error("hgs_raster_contrib: n_slots = %lld < P = %d without slot_of_row (the identity map)", (long long)n_slots, a->P); return HGS_ERR_INVALID; }
-  if (a->P == 0 || L == 0) return HGS_OK;
-  if (!geom_ws || !bin_ws || !img_ws || !tmp) { set_error("hgs_raster_contrib: null workspace (geom / bin / img / tmp)"); return HGS_ERR_INVALID; }
-  HGS_HIP(hipSetDevice(device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int T = grid_x(a->width) * grid_y(a->height);
-  const GeomWs g = GeomWs::carve_from(const_cast<void*>(geom_ws), a->P);
-  const BinWs b = BinWs::carve_from(const_cast<void*>(bin_ws), L, T);
-  const ContribWs w = ContribWs::carve_from(tmp, L);
-  return launch_raster_contrib(*a, g, b, w, L, pixel_mask, slot_of_row, n_slots, wmax, wsum, count, s);
+  ForwardRead f;
+  rc = open_forward_read("hgs_raster_contrib", "geom / bin / img / tmp", a, geom_ws, bin_ws, img_ws, !tmp, L, slot_of_row,
+                         n_slots, true, false, stream, device, f);
+  if (rc || f.empty) return rc;
+  return launch_raster_contrib(*a, f.g, f.b, ContribWs::carve_from(tmp, L), L, pixel_mask, slot_of_row, n_slots, wmax,
+                               wsum, count, f.s);
 }
 
 size_t hgs_raster_attribute_tmp_bytes(uint32_t L) { return AttributeWs::bytes(L); }
@@ -479,47 +516,33 @@ int hgs_raster_attribute(const hgs_raster_args* a, const void* geom_ws, const vo
                          uint32_t L, const float* image, int32_t channels, const uint8_t* pixel_mask,
                          const int32_t* slot_of_row, int64_t n_slots, double* out, double* wsum, void* tmp,
                          hgs_stream_t stream, int device) {
-  int rc = validate(a);
+  int rc = check_forward_read("hgs_raster_attribute", "weights follow", a);
   if (rc) return rc;
-  if (a->lod_per_pixel != 0) { set_error("hgs_raster_attribute: lod_per_pixel = %d is not built (the weights follow the per-Gaussian remap only)", a->lod_per_pixel); return HGS_ERR_INVALID; }
   if (channels < 1 || channels > 3) { set_error("hgs_raster_attribute: channels = %d, need 1..3", channels); return HGS_ERR_INVALID; }
   if (!image) { set_error("hgs_raster_attribute: null image"); return HGS_ERR_INVALID; }
   if (!out) { set_error("hgs_raster_attribute: null output (out)"); return HGS_ERR_INVALID; }
-  if (n_slots < 1) { set_error("hgs_raster_attribute: n_slots = %lld, need >= 1", (long long)n_slots); return HGS_ERR_INVALID; }
-  if (!slot_of_row && n_slots < a->P) { set_error("hgs_raster_attribute: n_slots = %lld < P = %d without slot_of_row (the identity map)", (long long)n_slots, a->P); return HGS_ERR_INVALID; }
-  if (a->P == 0 || L == 0) return HGS_OK;
-  if (!geom_ws || !bin_ws || !img_ws || !tmp) { set_error("hgs_raster_attribute: null workspace (geom / bin / img / tmp)"); return HGS_ERR_INVALID; }
-  HGS_HIP(hipSetDevice(device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int T = grid_x(a->width) * grid_y(a->height);
-  const GeomWs g = GeomWs::carve_from(const_cast<void*>(geom_ws), a->P);
-  const BinWs b = BinWs::carve_from(const_cast<void*>(bin_ws), L, T);
-  const AttributeWs w = AttributeWs::carve_from(tmp, L);
-  return launch_raster_attribute(*a, g, b, w, L, image, channels, pixel_mask, slot_of_row, n_slots, out, wsum, s);
+  ForwardRead f;
+  rc = open_forward_read("hgs_raster_attribute", "geom / bin / img / tmp", a, geom_ws, bin_ws, img_ws, !tmp, L,
+                         slot_of_row, n_slots, true, false, stream, device, f);
+  if (rc || f.empty) return rc;
+  return launch_raster_attribute(*a, f.g, f.b, AttributeWs::carve_from(tmp, L), L, image, channels, pixel_mask,
+                                 slot_of_row, n_slots, out, wsum, f.s);
 }
 
 int hgs_raster_pixels(const hgs_raster_args* a, const void* geom_ws, const void* bin_ws, const void* img_ws, uint32_t L,
                       const int32_t* slot_of_row, int64_t n_slots, const hgs_raster_pixel_planes* out,
                       hgs_stream_t stream, int device) {
-  int rc = validate(a);
+  int rc = check_forward_read("hgs_raster_pixels", "readout follows", a);
   if (rc) return rc;
-  if (a->lod_per_pixel != 0) { set_error("hgs_raster_pixels: lod_per_pixel = %d is not built (the readout follows the per-Gaussian remap only)", a->lod_per_pixel); return HGS_ERR_INVALID; }
   if (!out || (!out->alpha && !out->count && !out->front && !out->back && !out->heaviest && !out->wmax && !out->median && !out->median_depth)) {
     set_error("hgs_raster_pixels: null planes (at least one of alpha / count / front / back / heaviest / wmax / median / median_depth is needed)");
     return HGS_ERR_INVALID;
   }
-  if (slot_of_row && n_slots < 1) { set_error("hgs_raster_pixels: n_slots = %lld with slot_of_row, need >= 1", (long long)n_slots); return HGS_ERR_INVALID; }
-  const bool empty = a->P == 0 || L == 0;
-  if (!empty && (!geom_ws || !bin_ws || !img_ws)) { set_error("hgs_raster_pixels: null workspace (geom / bin / img)"); return HGS_ERR_INVALID; }
-  HGS_HIP(hipSetDevice(device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  GeomWs g{};
-  BinWs b{};
-  if (!empty) {
-    g = GeomWs::carve_from(const_cast<void*>(geom_ws), a->P);
-    b = BinWs::carve_from(const_cast<void*>(bin_ws), L, grid_x(a->width) * grid_y(a->height));
-  }
-  return launch_raster_pixels(*a, g, b, empty, slot_of_row, n_slots, *out, s);
+  ForwardRead f;
+  rc = open_forward_read("hgs_raster_pixels", "geom / bin / img", a, geom_ws, bin_ws, img_ws, false, L, slot_of_row,
+                         n_slots, false, true, stream, device, f);
+  if (rc) return rc;
+  return launch_raster_pixels(*a, f.g, f.b, f.empty, slot_of_row, n_slots, *out, f.s);    // empty: nothing carved
 }
 
 int hgs_raster_sh_bwd_batched(const hgs_sh_bwd_view* views, int32_t n_views, int32_t P, int32_t M, int32_t sh_degree,

@@ -121,23 +121,17 @@ struct BwdWs {
   static BwdWs carve_from(void* base, uint32_t L, int32_t P) { Carver c(base); return layout(c, L, P); }
 };
 
-// Scratch of the contribution statistics (contrib.hip): one 16-byte record per (tile, Gaussian) instance, in emission
-// order like BwdWs::inst_grads; written whole by the tile kernel, so it needs no clearing
-struct ContribWs {
-  float* inst;             // [L,4] (largest weight, sum of weights, pixel count as bits, 0)
-  static ContribWs layout(Carver& c, uint32_t L);      // contrib.hip
+// Scratch of the contribution statistics and of the image attribution (contrib.hip, attribute.hip; tile_walk.h): one
+// 16-byte record per (tile, Gaussian) instance, in emission order like BwdWs::inst_grads; written whole by the tile
+// kernel, so it needs no clearing
+struct InstRecWs {
+  float* inst;             // [L,4] contrib: (largest weight, sum of weights, pixel count as bits, 0); attribute: (A0, A1, A2, sum of weights)
+  static InstRecWs layout(Carver& c, uint32_t L) { return {c.take<float>((size_t)(L ? L : 1) * 4)}; }
   static size_t bytes(uint32_t L) { Carver c(nullptr); layout(c, L); return c.bytes(kAlign); }
-  static ContribWs carve_from(void* base, uint32_t L) { Carver c(base); return layout(c, L); }
+  static InstRecWs carve_from(void* base, uint32_t L) { Carver c(base); return layout(c, L); }
 };
-
-// Scratch of the image attribution (attribute.hip): one 16-byte record per (tile, Gaussian) instance, in emission
-// order like ContribWs::inst; written whole by the tile kernel, so it needs no clearing
-struct AttributeWs {
-  float* inst;             // [L,4] (A0, A1, A2, sum of weights)
-  static AttributeWs layout(Carver& c, uint32_t L);    // attribute.hip
-  static size_t bytes(uint32_t L) { Carver c(nullptr); layout(c, L); return c.bytes(kAlign); }
-  static AttributeWs carve_from(void* base, uint32_t L) { Carver c(base); return layout(c, L); }
-};
+using ContribWs = InstRecWs;
+using AttributeWs = InstRecWs;
 
 inline int grid_x(int W) { return (W + kTile - 1) / kTile; }
 inline int grid_y(int H) { return (H + kTile - 1) / kTile; }

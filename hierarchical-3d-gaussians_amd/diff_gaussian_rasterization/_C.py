@@ -586,6 +586,28 @@ def raster_views(call):
     }
 
 
+def _checked_slot_map(slot_of_row, dev, P):
+    """``slot_of_row`` of raster_contributions / raster_attribute / raster_pixels: int32 [P] on the forward's device."""
+    if not torch.is_tensor(slot_of_row) or slot_of_row.device != dev or slot_of_row.dtype != torch.int32:
+        raise RuntimeError(f"slot_of_row must be an int32 tensor on {dev}")
+    if slot_of_row.numel() != P:
+        raise RuntimeError(f"slot_of_row must hold one entry per op row ({P}), got {slot_of_row.numel()}")
+    return slot_of_row.contiguous()
+
+
+def _checked_pixel_mask(pixel_mask, call):
+    """``pixel_mask`` of raster_contributions / raster_attribute: None, or uint8 with H * W entries on the forward's
+    device."""
+    if pixel_mask is None:
+        return None
+    dev = call.device
+    if not torch.is_tensor(pixel_mask) or pixel_mask.device != dev or pixel_mask.dtype != torch.uint8:
+        raise RuntimeError(f"pixel_mask must be a uint8 tensor on {dev}")
+    if pixel_mask.numel() != call.W * call.H:
+        raise RuntimeError(f"pixel_mask must hold H * W = {call.W * call.H} entries, got {pixel_mask.numel()}")
+    return pixel_mask.contiguous()
+
+
 def raster_contributions(call, wmax, wsum, count, slot_of_row=None, pixel_mask=None):
     """Blending statistics of the forward that returned ``call`` (hgs_raster_contrib),
     accumulated IN PLACE into ``wmax`` float32, ``wsum`` float64 and ``count`` int64, all [S] on the forward's device:
@@ -607,17 +629,8 @@ def raster_contributions(call, wmax, wsum, count, slot_of_row=None, pixel_mask=N
         if S < P:
             raise RuntimeError(f"{S} slots for {P} op rows: pass slot_of_row, or arrays of at least {P} entries")
     else:
-        if not torch.is_tensor(slot_of_row) or slot_of_row.device != dev or slot_of_row.dtype != torch.int32:
-            raise RuntimeError(f"slot_of_row must be an int32 tensor on {dev}")
-        if slot_of_row.numel() != P:
-            raise RuntimeError(f"slot_of_row must hold one entry per op row ({P}), got {slot_of_row.numel()}")
-        slot_of_row = slot_of_row.contiguous()
-    if pixel_mask is not None:
-        if not torch.is_tensor(pixel_mask) or pixel_mask.device != dev or pixel_mask.dtype != torch.uint8:
-            raise RuntimeError(f"pixel_mask must be a uint8 tensor on {dev}")
-        if pixel_mask.numel() != call.W * call.H:
-            raise RuntimeError(f"pixel_mask must hold H * W = {call.W * call.H} entries, got {pixel_mask.numel()}")
-        pixel_mask = pixel_mask.contiguous()
+        slot_of_row = _checked_slot_map(slot_of_row, dev, P)
+    pixel_mask = _checked_pixel_mask(pixel_mask, call)
     if P == 0 or call.L == 0:
         return
     # the instance scratch comes from the arena like every other workspace (uninitialised: the tile kernel writes
@@ -663,17 +676,8 @@ def raster_attribute(call, image, out, wsum=None, slot_of_row=None, pixel_mask=N
         if S < P:
             raise RuntimeError(f"{S} slots for {P} op rows: pass slot_of_row, or arrays of at least {P} entries")
     else:
-        if not torch.is_tensor(slot_of_row) or slot_of_row.device != dev or slot_of_row.dtype != torch.int32:
-            raise RuntimeError(f"slot_of_row must be an int32 tensor on {dev}")
-        if slot_of_row.numel() != P:
-            raise RuntimeError(f"slot_of_row must hold one entry per op row ({P}), got {slot_of_row.numel()}")
-        slot_of_row = slot_of_row.contiguous()
-    if pixel_mask is not None:
-        if not torch.is_tensor(pixel_mask) or pixel_mask.device != dev or pixel_mask.dtype != torch.uint8:
-            raise RuntimeError(f"pixel_mask must be a uint8 tensor on {dev}")
-        if pixel_mask.numel() != call.W * call.H:
-            raise RuntimeError(f"pixel_mask must hold H * W = {call.W * call.H} entries, got {pixel_mask.numel()}")
-        pixel_mask = pixel_mask.contiguous()
+        slot_of_row = _checked_slot_map(slot_of_row, dev, P)
+    pixel_mask = _checked_pixel_mask(pixel_mask, call)
     if P == 0 or call.L == 0:
         return
     # the instance scratch comes from the arena like every other workspace (uninitialised: the tile kernel writes
@@ -711,14 +715,10 @@ def raster_pixels(call, slot_of_row=None, n_slots=None, want=PIXEL_PLANES):
             raise RuntimeError("n_slots bounds slot_of_row: pass both, or neither (ids are then the op rows)")
         S = 0
     else:
-        if not torch.is_tensor(slot_of_row) or slot_of_row.device != dev or slot_of_row.dtype != torch.int32:
-            raise RuntimeError(f"slot_of_row must be an int32 tensor on {dev}")
-        if slot_of_row.numel() != P:
-            raise RuntimeError(f"slot_of_row must hold one entry per op row ({P}), got {slot_of_row.numel()}")
+        slot_of_row = _checked_slot_map(slot_of_row, dev, P)
         S = 2 ** 31 - 1 if n_slots is None else int(n_slots)
         if S < 1:
             raise RuntimeError(f"n_slots must be >= 1, got {S}")
-        slot_of_row = slot_of_row.contiguous()
     out = {name: torch.empty((call.H, call.W), dtype=torch.float32 if name in _FLOAT_PLANES else torch.int32, device=dev)
            for name in want}
     planes = _lib.RasterPixelPlanes(**{name: t.data_ptr() for name, t in out.items()})
