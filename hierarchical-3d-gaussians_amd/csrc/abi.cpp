@@ -451,7 +451,7 @@ int hgs_raster_bwd(const hgs_raster_args* a, const void* geom_ws, const void* bi
   return HGS_TIMED(ST_PREPROCESS_BWD, s, launch_preprocess_bwd(*a, g, w, gr, L, s));
 }
 
-// What the three calls that read a finished forward share (hgs_raster_contrib / _attribute / _pixels), in two halves
+// What the four calls that read a finished forward share (hgs_raster_contrib / _attribute / _pixels / _values), in two halves
 // because a call's own argument checks stand between them in the documented order of refusals.
 // First half: the argument check and the lod_per_pixel refusal.
 static int check_forward_read(const char* fn, const char* follows, const hgs_raster_args* a) {
@@ -543,6 +543,24 @@ int hgs_raster_pixels(const hgs_raster_args* a, const void* geom_ws, const void*
                          n_slots, false, true, stream, device, f);
   if (rc) return rc;
   return launch_raster_pixels(*a, f.g, f.b, f.empty, slot_of_row, n_slots, *out, f.s);    // empty: nothing carved
+}
+
+int hgs_raster_values(const hgs_raster_args* a, const void* geom_ws, const void* bin_ws, const void* img_ws, uint32_t L,
+                      const float* values, int64_t value_stride, int channels, const int32_t* slot_of_row,
+                      int64_t n_slots, const float* background, float* out, float* wsum, hgs_stream_t stream,
+                      int device) {
+  int rc = check_forward_read("hgs_raster_values", "blend follows", a);
+  if (rc) return rc;
+  if (channels < 1 || channels > 4) { set_error("hgs_raster_values: channels = %d, need 1..4", channels); return HGS_ERR_INVALID; }
+  if (value_stride < channels) { set_error("hgs_raster_values: value_stride = %lld < channels = %d", (long long)value_stride, channels); return HGS_ERR_INVALID; }
+  if (!values) { set_error("hgs_raster_values: null values"); return HGS_ERR_INVALID; }
+  if (!out) { set_error("hgs_raster_values: null output (out)"); return HGS_ERR_INVALID; }
+  ForwardRead f;
+  rc = open_forward_read("hgs_raster_values", "geom / bin / img", a, geom_ws, bin_ws, img_ws, false, L, slot_of_row,
+                         n_slots, true, true, stream, device, f);
+  if (rc) return rc;
+  return launch_raster_values(*a, f.g, f.b, f.empty, values, value_stride, channels, slot_of_row, n_slots, background,
+                              out, wsum, f.s);                                            // empty: nothing carved
 }
 
 int hgs_raster_sh_bwd_batched(const hgs_sh_bwd_view* views, int32_t n_views, int32_t P, int32_t M, int32_t sh_degree,

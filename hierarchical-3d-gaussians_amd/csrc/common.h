@@ -287,6 +287,12 @@ int launch_raster_attribute(const hgs_raster_args& a, const GeomWs& g, const Bin
 // workspace is read and the planes take the "nothing" values
 int launch_raster_pixels(const hgs_raster_args& a, const GeomWs& g, const BinWs& b, bool empty,
                          const int32_t* slot_of_row, int64_t n_slots, const hgs_raster_pixel_planes& out, hipStream_t s);
+// per-slot values [n_slots, value_stride] blended into planar out [channels, H, W] (and the named rows' weights into
+// wsum [H*W], when given) with the weights of the forward whose workspaces g / b are (values.hip); channels in 1..4,
+// `empty` as for launch_raster_pixels: out takes the background, wsum zeros
+int launch_raster_values(const hgs_raster_args& a, const GeomWs& g, const BinWs& b, bool empty, const float* values,
+                         int64_t value_stride, int channels, const int32_t* slot_of_row, int64_t n_slots,
+                         const float* background, float* out, float* wsum, hipStream_t s);
 // L: the frame's instance count (a frame of long runs sums them with kernels of their own in front of K8a; w.inst_grads
 // is consumed: they leave every segment's sums over the segment's first records)
 int launch_preprocess_bwd(const hgs_raster_args& a, const GeomWs& g, const BwdWs& w, const hgs_raster_grads& out, uint32_t L,

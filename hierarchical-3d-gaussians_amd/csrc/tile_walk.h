@@ -1,6 +1,6 @@
-// The forward-side tile walk, ONCE, for the three files that read a finished forward without running the backward:
-// contrib.hip (f-22), attribute.hip (f-23) and pixels.hip (f-24).  Device only; included by those three files and by
-// nothing else (render.hip keeps its own K6 and K7).  The walk is a contract: a row counts at a pixel exactly when K6
+// The forward-side tile walk, ONCE, for the four files that read a finished forward without running the backward:
+// contrib.hip (f-22), attribute.hip (f-23), pixels.hip (f-24) and values.hip (f-26).  Device only; included by those
+// four files and by nothing else (render.hip keeps its own K6 and K7).  The walk is a contract: a row counts at a pixel exactly when K6
 // blended it there, with the weight K6 added to the colour -- so K6's decision stands here in one text, not three.
 //
 //  * ONE WAVE PER 16x16 TILE in K6's XCD-aware tile order (block_tile), so no barrier beyond those of a one-wave

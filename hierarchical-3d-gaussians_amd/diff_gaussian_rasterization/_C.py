@@ -728,6 +728,58 @@ def raster_pixels(call, slot_of_row=None, n_slots=None, want=PIXEL_PLANES):
     return out
 
 
+VALUE_CHANNELS = 4           # channels one hgs_raster_values launch blends
+
+
+def raster_values(call, values, slot_of_row=None, background=None, want_wsum=False):
+    """Per-row values painted into the picture of the forward that returned ``call`` (hgs_raster_values; DESIGN.md
+    section 7, f-26): ``out[c, p] = sum over the rows K6 blended at p of w * values[slot, c] + T_final * background[c]``
+    with ``w = alpha * T`` as K6 blends it, in float32 and in K6's order.  ``values``: float32 [S, C] (or [S] for
+    C = 1) on the forward's device, rows contiguous (a column slice of a wider table is taken as it is, through its row
+    stride); any C: more than four channels go through in groups of four on the same table, without a copy.
+    ``slot_of_row``: int32 [P]; default: the row itself (then S >= P); negative or >= S: the row occludes and adds
+    nothing.  ``background``: None (zeros) or C floats (a float32 tensor on the device, or a sequence).  Returns
+    ``out`` float32 [C, H, W], or ``(out, wsum)`` with ``want_wsum``: ``wsum`` float32 [H, W], the weights of the rows
+    that have a slot.  Every pixel is written."""
+    dev, P = call.device, call.P
+    if not torch.is_tensor(values) or not values.is_cuda or values.device != dev:
+        raise RuntimeError(f"values must be a tensor on the forward's device {dev}")
+    if values.dtype != torch.float32 or values.dim() not in (1, 2):
+        raise RuntimeError("values must be a float32 tensor [S, C], or [S] for one channel")
+    if values.dim() == 1:
+        values = values.contiguous().view(-1, 1)
+    S, Cn = int(values.shape[0]), int(values.shape[1])
+    if S < 1 or Cn < 1:
+        raise RuntimeError(f"values must hold at least one slot and one channel, got {tuple(values.shape)}")
+    if values.stride(1) != 1 or (S > 1 and values.stride(0) < Cn):
+        raise RuntimeError("values must have contiguous rows (stride 1 along the channels, a row stride >= C): it is read in place")
+    stride = int(values.stride(0)) if S > 1 else Cn
+    if slot_of_row is None:
+        if S < P:
+            raise RuntimeError(f"{S} slots for {P} op rows: pass slot_of_row, or values of at least {P} rows")
+    else:
+        slot_of_row = _checked_slot_map(slot_of_row, dev, P)
+    if background is not None:
+        if torch.is_tensor(background):
+            if background.device != dev or background.dtype != torch.float32:
+                raise RuntimeError(f"background must be a float32 tensor on {dev}, or a sequence of floats")
+            background = background.contiguous().reshape(-1)
+        else:
+            background = torch.tensor([float(v) for v in background], dtype=torch.float32, device=dev)
+        if background.numel() != Cn:
+            raise RuntimeError(f"background must hold one value per channel ({Cn}), got {background.numel()}")
+    out = torch.empty((Cn, call.H, call.W), dtype=torch.float32, device=dev)
+    wsum = torch.empty((call.H, call.W), dtype=torch.float32, device=dev) if want_wsum else None
+    lib, plane = _lib.lib(), call.H * call.W * 4
+    for c0 in range(0, Cn, VALUE_CHANNELS):
+        _lib.check(lib.hgs_raster_values(
+            C.byref(call.args), call.p_geom, call.p_bin, call.p_img, call.L_ws, values.data_ptr() + 4 * c0, stride,
+            min(VALUE_CHANNELS, Cn - c0), _lib.ptr(slot_of_row), S,
+            None if background is None else background.data_ptr() + 4 * c0, out.data_ptr() + plane * c0,
+            _lib.ptr(wsum) if c0 == 0 else None, _stream(dev), dev.index or 0), "hgs_raster_values")
+    return (out, wsum) if want_wsum else out
+
+
 def mark_visible(means3D, viewmatrix, projmatrix):
     """Frustum test used by the upstream API (z > 0.2 in view space)."""
     means3D = _require_gpu(means3D, "means3D")

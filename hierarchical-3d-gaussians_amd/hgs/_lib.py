@@ -207,6 +207,8 @@ SIGNATURES = {
                                        _P, _P, _P, _P, C.c_int]),
     "hgs_raster_pixels": (C.c_int, [C.POINTER(RasterArgs), _P, _P, _P, C.c_uint32, _P, C.c_int64,
                                     C.POINTER(RasterPixelPlanes), _P, C.c_int]),
+    "hgs_raster_values": (C.c_int, [C.POINTER(RasterArgs), _P, _P, _P, C.c_uint32, _P, C.c_int64, C.c_int, _P,
+                                    C.c_int64, _P, _P, _P, _P, C.c_int]),
     "hgs_raster_views_get": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _P, _P, _P,
                                        C.POINTER(RasterViews)]),
     "hgs_sort_tmp_bytes": (C.c_size_t, [C.c_uint32]),

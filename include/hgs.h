@@ -306,6 +306,35 @@ int hgs_raster_pixels(const hgs_raster_args* a, const void* geom_ws, const void*
                       const int32_t* slot_of_row, int64_t n_slots, const hgs_raster_pixel_planes* out,
                       hgs_stream_t stream, int device);
 
+/* Per-row values painted into the picture of ONE forward whose workspaces are intact: the
+ * dual of hgs_raster_attribute.  For every pixel p inside the image take the rows K6 blended there, front to back,
+ * k = 1..n ("blended" is K6's decision on the same records in the same float32 expressions, as hgs_raster_contrib
+ * states it), with w_k = alpha_k * T_{k-1} and T_n as K6 computes them, and with s_k the slot of row k:
+ *     out[c][p] = fma(T_n, background[c], acc_n),   acc_k = fma(w_k, values[s_k * value_stride + c], acc_{k-1}),  acc_0 = 0
+ *     wsum[p]   = sum over the NAMED rows, in the same order, of w_k                     (float32; when wsum is given)
+ * all float32, one fused multiply-add per row, in list order: with finite values these are the bits K6 gives a colour
+ * channel whose per-row colours are `values` (and, with a NULL background, its inverse-depth plane).  A row that is not
+ * blended at p is SKIPPED, not weighted by zero: a NaN or an infinity in a row's values reaches exactly the pixels the
+ * row is blended at.  The slot of op row i is slot_of_row[i] when that lies in [0, n_slots) -- the row is then NAMED --
+ * and i itself when slot_of_row is NULL; a row the map ignores (negative or >= n_slots) still occludes, its values are
+ * never read, and it adds nothing to out or wsum.  Stands in for nothing upstream; in this library it replaces a second
+ * whole forward with colors_precomp (K1, binning and sort again, three channels, no slot map).
+ *   values       device float32 [n_slots, value_stride], read at the first `channels` words of a row;  channels in 1..4,
+ *                value_stride >= channels (wider tables go through in groups of four by offsetting `values`)
+ *   slot_of_row  NULL (identity; then n_slots >= P) or device int32 [P] (the render_indices of a cut: values per node)
+ *   background   NULL (zeros: the stored bits are acc_n's) or device float32 [channels]
+ *   out          device float32, planar [channels, H, W];  wsum: device float32 [H*W] or NULL
+ * Every pixel inside the image is written in every given plane: the caller need not pre-fill.  One launch, asynchronous
+ * on `stream`, no host wait, no atomics, no scratch: the same inputs give the same bits on every run.  L == 0 or P == 0
+ * reads no workspace and no value: out takes the background and wsum zeros.  Refused with HGS_ERR_INVALID before any HIP
+ * call (hgs_last_error names it): what the forward's argument check refuses, lod_per_pixel != 0 (not built), channels
+ * outside 1..4, value_stride < channels, null values or out, n_slots < 1, n_slots < P without slot_of_row, a null
+ * workspace.  lod_half_rows and the in-op LOD route are ALLOWED: only records, lists and ranges are read. */
+int hgs_raster_values(const hgs_raster_args* a, const void* geom_ws, const void* bin_ws, const void* img_ws, uint32_t L,
+                      const float* values, int64_t value_stride, int channels /* 1..4 */,
+                      const int32_t* slot_of_row, int64_t n_slots, const float* background /* [channels] or NULL */,
+                      float* out /* [channels, H, W] */, float* wsum /* [H*W] or NULL */, hgs_stream_t stream, int device);
+
 /* SH part of the backward for up to HGS_MAX_DEFERRED_VIEWS views of the SAME Gaussians in one pass (gradient
  * accumulation over the views of one optimiser step / of one data-parallel rank): the [P,M,3] coefficients are read
  * once and dL_dshs is written once, instead of once per view.  Each view ran hgs_raster_bwd with
