@@ -34,7 +34,8 @@ class View:
     def __init__(self, nodes, boxes, viewpoint, bounds=None, planes=None, radius_scale=1.0):
         self.nodes = nodes = np.asarray(nodes)
         N = nodes.shape[0]
-        boxes = np.asarray(boxes, dtype=np.float32).reshape(N, 2, 4)
+        self.boxes = boxes = np.asarray(boxes, dtype=np.float32).reshape(N, 2, 4)
+        self.viewpoint = np.asarray(viewpoint, dtype=np.float32)
         self.s = lo.node_size(boxes, np.arange(N), viewpoint)
         par = nodes[:, 1].astype(np.int64)
         self.s_par = np.where(par >= 0, self.s[np.maximum(par, 0)], F(np.inf)).astype(np.float32)
