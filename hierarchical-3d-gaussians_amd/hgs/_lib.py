@@ -183,6 +183,20 @@ class PhotoArgs(C.Structure):
                 ("reserved", C.c_int32), ("lambda_dssim", C.c_double), ("depth_weight", C.c_double)]
 
 
+class TsdfVolume(C.Structure):
+    _fields_ = [("tsdf", C.c_void_p), ("weight", C.c_void_p), ("colour", C.c_void_p), ("lo", C.c_float * 3),
+                ("voxel", C.c_float), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("trunc", C.c_float),
+                ("max_weight", C.c_float)]
+
+
+class TsdfView(C.Structure):
+    _fields_ = [("depth", C.c_void_p), ("weight", C.c_void_p), ("rgb", C.c_void_p), ("W", C.c_int32), ("H", C.c_int32),
+                ("view", C.c_float * 12), ("tanfovx", C.c_float), ("tanfovy", C.c_float), ("z_min", C.c_float)]
+
+
+TSDF_MAX_VIEWS = 8              # views of one hgs_tsdf_integrate call
+
+
 # symbol -> (restype, argtypes); also the list the export test checks against include/hgs.h
 _P = C.c_void_p
 SIGNATURES = {
@@ -314,6 +328,10 @@ SIGNATURES = {
     "hgs_resid_fetch_half_slots": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P,
                                              C.POINTER(ResidRowsHalf), C.c_int32, _P, C.c_int]),
     "hgs_resid_pack_rows": (C.c_int, [C.POINTER(ResidRows), C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int]),
+    "hgs_tsdf_integrate": (C.c_int, [C.POINTER(TsdfVolume), C.POINTER(TsdfView), C.c_int32, _P, C.c_int]),
+    "hgs_tsdf_extract_tmp_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "hgs_tsdf_extract_plan": (C.c_int, [C.POINTER(TsdfVolume), C.c_float, _P, C.POINTER(C.c_int64), _P, C.c_int]),
+    "hgs_tsdf_extract_apply": (C.c_int, [C.POINTER(TsdfVolume), _P, _P, _P, _P, _P, _P, C.c_int]),
 }
 P2P_MAX_WORLD, P2P_HANDLE_BYTES, P2P_FLAG_BYTES = 8, 64, 256
 RESID_COUNTER_WORDS = 68

@@ -1248,6 +1248,58 @@ int hgs_resid_fetch_half_slots(const int32_t* miss_ids, uint32_t m, const int32_
 int hgs_resid_pack_rows(const hgs_resid_rows* src, int64_t G, int32_t M, int32_t half, void* host_rows_packed,
                         hgs_stream_t stream, int device);
 
+/* ---------------------------------------------------------------------------
+ * A surface from depth maps (csrc/tsdf.hip; the rules, once for host and device, in csrc/tsdf_rule.h; the spec is
+ * tests/tsdf_spec.py; hgs/meshing.py is the Python side): per-view depth maps -- hgs_raster_pixels' median_depth -- are
+ * fused into a truncated signed distance volume, and a triangle mesh is extracted from it by naive surface nets.
+ * Everything is float32 in a fixed operation order: the numpy restatement matches bit for bit.
+ *
+ * The volume: samples on the lattice x_a = lo_a + voxel * i_a, x fastest; tsdf [nz,ny,nx] in units of `trunc` (created
+ * as 1), weight [nz,ny,nx] (created as 0), colour [nz,ny,nx,3] (created as 0) or NULL.  A view: planar depth [H,W]
+ * (<= 0 or NaN: no surface at the pixel), weight [H,W] or NULL (1 everywhere), rgb [3,H,W] or NULL, the camera a centred
+ * pinhole: view[3 r + c] = world_view_transform[r][c] (row vectors, as the rasterizer takes it), r < 4, c < 3.
+ *   hgs_tsdf_integrate     applies views[0 .. n_views) in array order to every sample one of them sees: one call with V
+ *                          views leaves the bits of V calls with one view each.  One pass over the volume, asynchronous
+ *                          on `stream`; samples no view sees are neither read nor written.
+ *   hgs_tsdf_extract_plan  marks the active cells (8 samples with weight >= min_weight whose tsdf differ in sign), counts
+ *                          the quads, scans; waits once: totals_host[0] = vertices, totals_host[1] = quads (two
+ *                          triangles each).  tmp: hgs_tsdf_extract_tmp_bytes(nx, ny, nz) bytes, 256-byte aligned.
+ *   hgs_tsdf_extract_apply behind a successful plan on the same (device, tmp, dimensions) and an unchanged volume:
+ *                          vertices [V,3], normals [V,3] (unit, towards free space; 0 for a zero gradient), colours [V,3]
+ *                          or NULL, faces [2 Q,3]; vertices by ascending cell index, faces by ascending index of the
+ *                          edge's lower sample, then axis.  Asynchronous; with V = 0 nothing is written.
+ * Refused with HGS_ERR_INVALID before any HIP call (hgs_last_error names it): n_views outside 1..8; a dimension < 1 or
+ * more than 2^31 - 1 samples (an extraction: more than (2^32 - 1) / 3, the quad offsets are 32-bit -- the size query then
+ * answers 0); voxel, trunc or min_weight not positive and finite; max_weight <= 0 (infinity: never binds); W or H < 1 or more than 2^31 - 1 pixels; a
+ * null tsdf, weight, depth, tmp, vertices, normals or faces; rgb without colour; colours without colour; a pointer that
+ * is not 4-byte aligned, tmp not 256-byte aligned; apply without such a plan.
+ * ------------------------------------------------------------------------- */
+typedef struct hgs_tsdf_volume {
+  float* tsdf;
+  float* weight;
+  float* colour; /* or NULL */
+  float lo[3];
+  float voxel;
+  int32_t nx, ny, nz;
+  float trunc;
+  float max_weight;
+} hgs_tsdf_volume;
+typedef struct hgs_tsdf_view {
+  const float* depth;
+  const float* weight; /* or NULL */
+  const float* rgb;    /* or NULL */
+  int32_t W, H;
+  float view[12];
+  float tanfovx, tanfovy, z_min;
+} hgs_tsdf_view;
+int hgs_tsdf_integrate(const hgs_tsdf_volume* volume, const hgs_tsdf_view* views, int32_t n_views, hgs_stream_t stream,
+                       int device);
+size_t hgs_tsdf_extract_tmp_bytes(int32_t nx, int32_t ny, int32_t nz);
+int hgs_tsdf_extract_plan(const hgs_tsdf_volume* volume, float min_weight, void* tmp, int64_t totals_host[2],
+                          hgs_stream_t stream, int device);
+int hgs_tsdf_extract_apply(const hgs_tsdf_volume* volume, const void* tmp, float* vertices, float* normals,
+                           float* colours /* or NULL */, int32_t* faces, hgs_stream_t stream, int device);
+
 #ifdef __cplusplus
 }
 #endif
