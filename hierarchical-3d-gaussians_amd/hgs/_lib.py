@@ -194,7 +194,15 @@ class TsdfView(C.Structure):
                 ("view", C.c_float * 12), ("tanfovx", C.c_float), ("tanfovy", C.c_float), ("z_min", C.c_float)]
 
 
-TSDF_MAX_VIEWS = 8              # views of one hgs_tsdf_integrate call
+class TsdfSparse(C.Structure):
+    _fields_ = [("tsdf", C.c_void_p), ("weight", C.c_void_p), ("colour", C.c_void_p), ("block_of_slot", C.c_void_p),
+                ("table", C.c_void_p), ("lo", C.c_float * 3), ("voxel", C.c_float), ("nx", C.c_int32), ("ny", C.c_int32),
+                ("nz", C.c_int32), ("trunc", C.c_float), ("max_weight", C.c_float), ("n_blocks", C.c_int32),
+                ("capacity", C.c_int32)]
+
+
+TSDF_MAX_VIEWS = 8              # views of one hgs_tsdf_integrate / hgs_tsdf_sparse_mark / _integrate call
+TSDF_BLOCK = 8                  # samples per edge of a sparse volume's block
 
 
 # symbol -> (restype, argtypes); also the list the export test checks against include/hgs.h
@@ -332,6 +340,15 @@ SIGNATURES = {
     "hgs_tsdf_extract_tmp_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "hgs_tsdf_extract_plan": (C.c_int, [C.POINTER(TsdfVolume), C.c_float, _P, C.POINTER(C.c_int64), _P, C.c_int]),
     "hgs_tsdf_extract_apply": (C.c_int, [C.POINTER(TsdfVolume), _P, _P, _P, _P, _P, _P, C.c_int]),
+    "hgs_tsdf_sparse_table_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "hgs_tsdf_sparse_commit_tmp_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "hgs_tsdf_sparse_extract_tmp_bytes": (C.c_size_t, [C.c_int32]),
+    "hgs_tsdf_sparse_mark": (C.c_int, [C.POINTER(TsdfSparse), C.POINTER(TsdfView), C.c_int32, _P, C.c_int]),
+    "hgs_tsdf_sparse_commit_plan": (C.c_int, [C.POINTER(TsdfSparse), _P, C.POINTER(C.c_int64), _P, C.c_int]),
+    "hgs_tsdf_sparse_commit_apply": (C.c_int, [C.POINTER(TsdfSparse), _P, _P, C.c_int]),
+    "hgs_tsdf_sparse_integrate": (C.c_int, [C.POINTER(TsdfSparse), C.POINTER(TsdfView), C.c_int32, _P, C.c_int]),
+    "hgs_tsdf_sparse_extract_plan": (C.c_int, [C.POINTER(TsdfSparse), C.c_float, _P, C.POINTER(C.c_int64), _P, C.c_int]),
+    "hgs_tsdf_sparse_extract_apply": (C.c_int, [C.POINTER(TsdfSparse), _P, _P, _P, _P, _P, _P, _P, C.c_int]),
 }
 P2P_MAX_WORLD, P2P_HANDLE_BYTES, P2P_FLAG_BYTES = 8, 64, 256
 RESID_COUNTER_WORDS = 68

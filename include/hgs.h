@@ -1300,6 +1300,73 @@ int hgs_tsdf_extract_plan(const hgs_tsdf_volume* volume, float min_weight, void*
 int hgs_tsdf_extract_apply(const hgs_tsdf_volume* volume, const void* tmp, float* vertices, float* normals,
                            float* colours /* or NULL */, int32_t* faces, hgs_stream_t stream, int device);
 
+/* ---------------------------------------------------------------------------
+ * The same on a SPARSE volume (csrc/tsdf_sparse.hip; the allocation rule, once for host and device, in
+ * csrc/tsdf_block_rule.h; the spec is tests/tsdf_sparse_spec.py): the lattice of
+ * hgs_tsdf_volume is virtual -- a dimension may be anything up to 2^31 - 1 and the sample count anything --, storage is
+ * 8 x 8 x 8 blocks near the observed surface: tsdf [B,8,8,8], weight [B,8,8,8], colour [B,8,8,8,3] or NULL (created as
+ * 1 / 0 / 0 by the caller), block_of_slot int32 [B].  Block (bi, bj, bk) holds the samples 8 b .. 8 b + 7 per axis; the
+ * block grid is ceil(n / 8) per axis, x fastest, at most 2^31 - 1 blocks.  `table` is ONE allocation, created as 0 by
+ * the caller, dense over the block grid: hgs_tsdf_sparse_table_layout answers layout[0] = G blocks, slots int32 [G] at
+ * byte 0 (-1: none, final after the commit), marks uint8 [G] at byte layout[1], a refusal word at byte layout[2],
+ * layout[3] bytes in all.  n_blocks is -1 until the commit; afterwards the caller sets it to B.  On every lattice a dense
+ * volume can hold, views marked, committed and then integrated leave the bits of hgs_tsdf_integrate in every allocated
+ * sample, and the mesh is that of hgs_tsdf_extract_* in another order.
+ *   hgs_tsdf_sparse_table_layout, _commit_tmp_bytes, _extract_tmp_bytes   need no GPU; the byte counts are 0 for sizes that
+ *                          are refused.
+ *   hgs_tsdf_sparse_mark   marks the blocks that the bands of views[0 .. n_views)'s pixels pass through (depth and weight
+ *                          are read, rgb is not; a point up to one block outside the grid marks the border block next
+ *                          to it): plain stores, accumulating over calls.  Asynchronous.
+ *   hgs_tsdf_sparse_commit_plan   dilates the marks by the 3 x 3 x 3 block neighbourhood, counts, scans; waits once:
+ *                          *n_blocks_host = B.  tmp: hgs_tsdf_sparse_commit_tmp_bytes bytes, 256-byte aligned.
+ *   hgs_tsdf_sparse_commit_apply  with n_blocks = B and block_of_slot [capacity >= B], behind that plan on the same
+ *                          (device, tmp): numbers the slots by ascending linear block index.  Asynchronous.
+ *   hgs_tsdf_sparse_integrate     hgs_tsdf_integrate on the allocated blocks; a view that was not marked is legal and
+ *                          updates the allocated blocks only.  Asynchronous.
+ *   hgs_tsdf_sparse_extract_plan / _apply   as hgs_tsdf_extract_*; a cell or quad that needs a sample beyond the lattice
+ *                          or in no allocated block is not emitted; vertices by (slot, place of the cell in its block,
+ *                          64 k + 8 j + i), faces by (slot, place of the edge's lower sample, axis); cells int32 [V,3] =
+ *                          the lattice cell of every vertex.  tmp: hgs_tsdf_sparse_extract_tmp_bytes(n_blocks) bytes.
+ *                          With B = 0 nothing is launched or written.
+ * Refused with HGS_ERR_INVALID before any HIP call (hgs_last_error names it): what hgs_tsdf_* refuses (the sample limits
+ * apart); a block grid of more than 2^31 - 1 blocks; more than (2^32 - 1) / 3 / 512 blocks in an extraction; a null or
+ * misaligned table or tmp (256 bytes); tsdf / weight / colour not 16-byte aligned; a mark or commit plan of a committed
+ * volume (n_blocks != -1); commit apply, integrate or extract of one that is not (n_blocks < 0); capacity < n_blocks;
+ * a marked view whose tanfovx or tanfovy is not in (0, 1.5]; trunc of more than 4096 voxels; an apply without its plan.
+ * Refused by hgs_tsdf_sparse_commit_plan after its wait: a marked pixel whose footprint at d + trunc is more than
+ * 16 x 2 voxels wide ("sub-pixel grid").  That pixel was not marched and the refusal word stays set, so this table can
+ * never be committed: start again from a zeroed table, with a larger voxel or without that view.
+ * ------------------------------------------------------------------------- */
+typedef struct hgs_tsdf_sparse {
+  float* tsdf;            /* [capacity,8,8,8] */
+  float* weight;          /* [capacity,8,8,8] */
+  float* colour;          /* [capacity,8,8,8,3] or NULL */
+  int32_t* block_of_slot; /* [capacity] */
+  void* table;
+  float lo[3];
+  float voxel;
+  int32_t nx, ny, nz;
+  float trunc;
+  float max_weight;
+  int32_t n_blocks;       /* -1 before the commit, B after it */
+  int32_t capacity;       /* blocks the slot arrays have room for */
+} hgs_tsdf_sparse;
+int hgs_tsdf_sparse_table_layout(int32_t nx, int32_t ny, int32_t nz, int64_t layout[4]);
+size_t hgs_tsdf_sparse_commit_tmp_bytes(int32_t nx, int32_t ny, int32_t nz);
+size_t hgs_tsdf_sparse_extract_tmp_bytes(int32_t n_blocks);
+int hgs_tsdf_sparse_mark(const hgs_tsdf_sparse* volume, const hgs_tsdf_view* views, int32_t n_views, hgs_stream_t stream,
+                         int device);
+int hgs_tsdf_sparse_commit_plan(const hgs_tsdf_sparse* volume, void* tmp, int64_t* n_blocks_host, hgs_stream_t stream,
+                                int device);
+int hgs_tsdf_sparse_commit_apply(const hgs_tsdf_sparse* volume, const void* tmp, hgs_stream_t stream, int device);
+int hgs_tsdf_sparse_integrate(const hgs_tsdf_sparse* volume, const hgs_tsdf_view* views, int32_t n_views,
+                              hgs_stream_t stream, int device);
+int hgs_tsdf_sparse_extract_plan(const hgs_tsdf_sparse* volume, float min_weight, void* tmp, int64_t totals_host[2],
+                                 hgs_stream_t stream, int device);
+int hgs_tsdf_sparse_extract_apply(const hgs_tsdf_sparse* volume, const void* tmp, float* vertices, float* normals,
+                                  float* colours /* or NULL */, int32_t* faces, int32_t* cells, hgs_stream_t stream,
+                                  int device);
+
 #ifdef __cplusplus
 }
 #endif
